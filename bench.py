@@ -12,12 +12,21 @@ prefill -> 19 incremental decode steps with device-side greedy bookkeeping) over
 image with no data-path collective ("replicas only", SURVEY.md section 8e): every rank runs its own batch;
 torch.distributed (RCCL) is used only for the barriers and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ONE region of exactly K steps, writes the last
+step's outputs if --dump-outputs is given, and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step).  With --full the caption line also carries, each from runs of its own
+behind the timed steps (or, for the roofline, from events armed inside them):
+  timed regions -- a region shorter than 2 s is repeated (median of three regions of K steps each), plus one unarmed region
   roofline     -- for the dominant kernel (the 256x256x64 bf16 MFMA GEMM): algorithmic FLOPs of its launches
                   / their summed duration, measured live with hipEvents recorded on the launch stream around
-                  every such launch inside the timed region (vitcap_engine_timing_*).
+                  every such launch inside the timed region (vitcap_engine_timing_*), plus an isolated one-stream pass
+  extra        -- board power / clock / joules per step from an untimed >= 2 s pass
+  decode_phase_ms_per_batch -- the decode loop alone
   cpu_baseline -- the CPU oracle's restatement of the reference algorithm AS WRITTEN (full re-encode per
                   step, fp32 eager torch) timed on this host: a bounded sample of 1 image.
+
+  --dump-outputs DIR  writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64); the inputs
+                      are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -221,6 +230,7 @@ def bench_train(args, rank, world, local, dist, D):
         host_s += time.perf_counter() - h0          # time the HOST spends issuing a step (enqueue only: no synchronisation inside)
     barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dist, device='cuda')
+    dump_outputs(args.dump_outputs, out, rank)
     timing, ops.TIMING = (ops.TIMING or []), None
     roof_note = None
     if eng.use_graphs:
@@ -309,6 +319,7 @@ def bench_scst(args, rank, world, local, dist, D):
         out = tr.step(img, gts)
     barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dist, device='cuda')
+    dump_outputs(args.dump_outputs, out, rank)
     if rank == 0:
         value = D.whole_job_rate(B, args.steps, world, elapsed)
         emit({
@@ -340,11 +351,13 @@ def bench_stub(args, rank, world, D):
     if dist is not None:
         dist.barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     if dist is not None:
         dist.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0 + 1e-3 * rank, dist)
+    dump_outputs(args.dump_outputs, {'stub_sum': [last]}, rank)
     if rank == 0:
         emit({'metric': 'stub steps/sec (plumbing test, not a measurement)', 'value': round(D.whole_job_rate(1, args.steps, world, elapsed), 2),
                           'unit': 'steps/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -353,6 +366,32 @@ def bench_stub(args, rank, world, D):
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path returned in its last step.  Integer and float64 arrays are
+    written as float64 (token ids stay exact), everything else as float32."""
+    import numpy as np
+    if out_dir is None:
+        return
+    conv = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu()
+            a = (a.double() if a.dtype in (torch.float64, torch.int64, torch.int32, torch.int16, torch.uint8, torch.bool)
+                 else a.float()).numpy()
+        else:
+            a = np.asarray(a)
+            a = a.astype(np.float64 if a.dtype.kind in 'iub' or a.dtype == np.float64 else np.float32)
+        conv[name + ('_rank%d' % rank if rank else '')] = a
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_LIMIT_BYTES, '--dump-outputs: %d bytes exceed the 64 MB limit' % total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 _JSON_FD = None
@@ -381,16 +420,16 @@ def main():
     ap.add_argument('--steps', type=int, default=200, help='timed steps (200 x ~18 ms keeps the timed region above 3 s)')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=64, help='images per GPU per step (configs[1]: 64)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--power', type=int, default=1, help='1: an untimed pass of >= 2 s after the timed regions with rocm-smi sampled beside it (extra.board_power_w_median, sclk_mhz_median, joules_per_step); 0 skips it')
-    ap.add_argument('--single-region', action='store_true', help='time ONE region of K steps even when it is shorter than 2 s (profiling runs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--power', type=int, default=1, help='--full, 1: an untimed pass of >= 2 s after the timed regions with rocm-smi sampled beside it (extra.board_power_w_median, sclk_mhz_median, joules_per_step); 0 skips it')
+    ap.add_argument('--single-region', action='store_true', help='--full: time ONE region of K steps even when it is shorter than 2 s (profiling runs; a plain run always times one)')
     ap.add_argument('--mode', default='caption', choices=['caption', 'train', 'scst'],
                     help="'caption' = the headline metric; 'train' = cross-entropy training step (BASELINE configs[3])")
     ap.add_argument('--beams', type=int, default=1, help='num_beams (1 = greedy, the headline metric; 5 = BASELINE configs[2])')
     ap.add_argument('--graph', type=int, default=0,
                     help='1: the decode loop is captured once into a hipGraph inside the engine (vitcap_gen_opts.use_graph) and replayed')
     ap.add_argument('--gemm-tiles', type=int, default=0, help='one-stream runs: large GEMMs one tile per workgroup (+ forked tag branch)')
-    ap.add_argument('--isolated', type=int, default=1, help='1: after the timed region, an untimed one-stream pass measures the dominant kernel with the chip to itself (roofline.isolated); 0 skips it (profiling runs: keeps the rocprofv3 per-kernel averages those of the timed configuration)')
+    ap.add_argument('--isolated', type=int, default=1, help='--full, 1: after the timed region, an untimed one-stream pass measures the dominant kernel with the chip to itself (roofline.isolated); 0 skips it (profiling runs: keeps the rocprofv3 per-kernel averages those of the timed configuration)')
     ap.add_argument('--pipeline', type=int, default=1,
                     help='1: two-slot batch pipeline (encode+prefill of step i+1 overlaps the decode of step i on a second '
                          'stream; same results); 0: one stream, steps strictly back to back')
@@ -399,6 +438,12 @@ def main():
     ap.add_argument('--stub', action='store_true',
                     help='CPU stand-in for the workload (tests of the launch / barrier / max-over-ranks / JSON plumbing only: gloo, no '
                          'GPU, no kernels; never a measurement)')
+    ap.add_argument('--full', action='store_true',
+                    help='caption mode: besides the K timed steps, also the repeated / unarmed regions, the per-launch roofline and its '
+                         'isolated pass, the energy pass, the decode-phase pass and the CPU baseline (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / '
+                         'float64, at most 64 MB); ranks > 0 add a _rank<r> suffix')
     args = ap.parse_args()
 
     from vitcap_amd import dist_util as D
@@ -461,7 +506,8 @@ def main():
 
         # ---- timed region: exactly K steps, bracketed by barrier + synchronize on both sides ---------------
         TIMING_STRIDE = 7       # the large-GEMM launches of every 7th step carry events (whole steps: the busy-interval union stays meaningful)
-        check(lib.vitcap_engine_timing_sample(model._engine, TIMING_STRIDE), 'timing_sample')
+        if args.full:
+            check(lib.vitcap_engine_timing_sample(model._engine, TIMING_STRIDE), 'timing_sample')
 
         def region(armed):
             """One timed region of exactly args.steps steps -> wall seconds.  armed: the engine records two HIP events around
@@ -486,13 +532,14 @@ def main():
         # A region shorter than 2 s (the driver's K = 20 at B = 64 is 0.35 s) is repeated: three armed regions, the MEDIAN is
         # the reported one, the spread goes into `timed_regions_ms_per_step`; one more region with the per-launch events NOT armed
         # prices the instrumentation (`unarmed_ms_per_step`).  `steps` stays what was passed: every region is exactly K steps.
-        elapsed, (ids, lp) = region(True)
+        # All of that is --full only: a plain run times ONE unarmed region of K steps and stops there.
+        elapsed, (ids, lp) = region(args.full)
         regions = [elapsed]
         unarmed = None
         events_region = 0
         # every rank must take the same branch (each region holds barriers): the decision uses the MAX over ranks of the first region
         first = D.max_over_ranks(elapsed, dist, device='cuda')
-        if first < 2.0 and not args.single_region:
+        if args.full and first < 2.0 and not args.single_region:
             ms_keep = None
             for _ in range(2):
                 check(lib.vitcap_engine_timing_end_kernel(model._engine, (C.c_double * 12)(), (C.c_double * 12)(), (C.c_int * 12)(), None,
@@ -506,6 +553,9 @@ def main():
             # the events of the LAST armed region stay in the engine for the roofline below; one unarmed region first would lose
             # them, so the unarmed one runs after they have been read (see below)
             unarmed = 'pending'
+        # the last timed step's outputs, copied to the host before any pass below can reuse the output buffers
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'caption_ids': ids, 'caption_logprobs': lp}, rank)
 
         # ---- live per-launch timing of the dominant kernel (hipEvents on the launch stream around every large GEMM)
         ms = (C.c_double * 12)()
@@ -514,14 +564,15 @@ def main():
         busy = (C.c_double * 12)()
         kms = (C.c_double * 12)()
         kbusy = (C.c_double * 12)()
-        check(lib.vitcap_engine_timing_end_kernel(model._engine, ms, fl, ln, busy, kms, kbusy), 'timing_end')
+        if args.full:
+            check(lib.vitcap_engine_timing_end_kernel(model._engine, ms, fl, ln, busy, kms, kbusy), 'timing_end')
         if unarmed == 'pending':
             unarmed, _ = region(False)
         # ---- energy pass (rank 0 samples; every rank runs the steps): >= 2 s of the same steps, untimed for `value`
         energy = None
         # (never under a profiler: its preloaded library would be inherited by the rocm-smi children of the sampler thread)
         profiled = any('rocprof' in os.environ.get(k, '').lower() for k in ('LD_PRELOAD', 'ROCP_TOOL_LIBRARIES', 'ROCPROFILER_LIBRARY_PATH'))
-        if args.power and not profiled:
+        if args.full and args.power and not profiled:
             n_e = max(args.steps, int(2.0 / max(elapsed / args.steps, 1e-4)) + 1)
             n_e = int(D.max_over_ranks(n_e, dist, device='cuda'))
             save_steps, args.steps = args.steps, n_e
@@ -538,7 +589,7 @@ def main():
         # their launch durations are longer than the kernel alone needs.  A second, untimed pass of (at most 20 of) the same
         # steps on ONE stream gives the kernel's own rate (reported next to, not instead of, the timed-region figure).
         iso = None
-        if piped and args.isolated:
+        if args.full and piped and args.isolated:
             n_iso = min(args.steps, 20)
             ms2, fl2, ln2, km2 = (C.c_double * 12)(), (C.c_double * 12)(), (C.c_int * 12)(), (C.c_double * 12)()
             check(lib.vitcap_engine_timing_begin(model._engine, n_iso * 160), 'timing_begin')
@@ -551,7 +602,7 @@ def main():
             iso = (list(km2), list(fl2), list(ln2))
         # decode phase alone (one stream, after an encode + prefill): GPU time of the step loop per batch
         dec_ms = None
-        if args.beams >= 1:
+        if args.full and args.beams >= 1:
             ws, need = model._workspace(B, img.device, 0, opts)
             o_ids, o_lp = model._out_buffers(B, opts, img.device)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -575,36 +626,11 @@ def main():
         return
 
     value = D.whole_job_rate(B, args.steps, world, elapsed)
-    # kms: durations from HIP events bound to the kernel dispatches (kernel begins executing -> complete: what rocprofv3
-    # --kernel-trace reports); ms: stream-marker brackets around the launches (also hold the dispatch's wait behind the other stream)
-    tot_ms = sum(kms)
-    tot_fl = sum(fl)
-    dom = max(range(12), key=lambda i: kms[i])
-    gemm_all = (tot_fl / (tot_ms * 1e-3)) / 1e12 if tot_ms > 0 else 0.0
-    dom_tf = (fl[dom] / (kms[dom] * 1e-3)) / 1e12 if kms[dom] > 0 else 0.0
-    mark_tf = (fl[dom] / (ms[dom] * 1e-3)) / 1e12 if ms[dom] > 0 else 0.0
-    traffic = None
-    try:      # HBM bytes per launch of the dominant kernel from the committed PMC passes (tools/pmc_traffic.sh);
-        # FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts 128-B requests as 64 B), KiB -> bytes
-        four_wave = kernel_form(lib, B * 577 // (2 if (piped and B >= 32) else 1), dom, piped or args.gemm_tiles).startswith('4-wave')
-        tfile = TRAFFIC_FILE if B < 256 else TRAFFIC_FILE.replace('.json', '_b512.json')
-        with open(tfile) as f:
-            tab = json.load(f)
-        names = [n for n in tab if n.startswith(PMC_KERNEL_4W[dom])] if four_wave else [PMC_KERNEL[dom]]
-        traffic = max((tab[n] for n in names if n in tab), key=lambda e: e['launches'])['hbm_bytes_per_launch_corrected']
-        if B not in (64, 512):
-            traffic = None          # the committed passes are B = 64 and B = 512 runs
-    except Exception:
-        traffic = None
     out = {
         'metric': 'images/sec end-to-end greedy caption (20 tok), ViT-B/16-384' if args.beams == 1 else
                   'images/sec end-to-end beam=%d caption (20 tok), ViT-B/16-384' % args.beams,
         'value': round(value, 2), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
-        'timed_regions_ms_per_step': [round(r / args.steps * 1e3, 3) for r in regions],
-        'timed_regions_note': ('median of %d regions of exactly K = %d steps each (a single region is shorter than 2 s); value / ms_per_step are the median region\'s' % (len(regions), args.steps)) if len(regions) > 1 else 'one region of exactly K steps',
-        'unarmed_ms_per_step': None if not isinstance(unarmed, float) else round(unarmed / args.steps * 1e3, 3),
-        'unarmed_note': 'one more region of K steps WITHOUT the two HIP events the engine records around every large-GEMM launch for the roofline: the difference to ms_per_step is the cost of the instrumentation inside the timed region',
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16',
         'data': 'synthetic',
         'config': {'workload': ('BASELINE configs[1]: ViT-B/16-384 greedy decode (20 tok), batch %d bf16 per GPU, ' % B if args.beams == 1
@@ -615,53 +641,81 @@ def main():
                    'launch': ('2-slot batch pipeline (encode of step i+1 || decode of step i)' if piped else 'one stream, steps back to back') +
                              (', decode loop replayed from an engine-owned hipGraph' if args.graph else ', eager launches'),
                    'streams_per_gpu': 2 if piped else 1},
-        'decode_phase_ms_per_batch': None if dec_ms is None else round(dec_ms, 3),
-        'extra': energy,
         'end_to_end_tflops_algorithmic': round(value / world * FLOP_PER_IMAGE / 1e12, 2),
         'end_to_end_tflops_executed': round(value / world * (FLOP_EXECUTED_PER_IMAGE if args.beams == 1 else FLOP_EXECUTED_PER_IMAGE + 13.35e9) / 1e12, 2),
         'end_to_end_frac_of_bf16_peak': round(value / world * FLOP_PER_IMAGE / 1e12 / PEAK_BF16_TFLOPS, 4),
-        'roofline': {
-            'bound': 'mfma', 'kernel': VARIANT_NAMES.get(dom, 'gemm_nt variant %d' % dom),
-            'kernel_form': kernel_form(lib, B * 577 // (2 if (piped and B >= 32) else 1), dom, piped or args.gemm_tiles),
-            'encode_parts': int(os.environ['VITCAP_ENCODE_SPLIT']) if os.environ.get('VITCAP_ENCODE_SPLIT') else (2 if (piped and B >= 32) else 1),
-            'achieved': round(dom_tf, 2), 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
-            'frac': round(dom_tf / PEAK_BF16_TFLOPS, 4) if ln[dom] else None, 'traffic': traffic,
-            'note': None if ln[dom] else 'no large-GEMM launch (M >= 2048 rows) in this configuration: the per-launch events cover those only',
-            'traffic_note': ('HBM bytes per launch from a COMMITTED rocprofv3 PMC pass, not measured in this run: (2*FETCH_SIZE+WRITE_SIZE)*1024 '
-                             'in %s (tools/pmc_traffic.sh regenerates it)' % os.path.relpath(tfile, REPO)) if traffic else None,
-            'launches': int(ln[dom]), 'avg_launch_ms': round(kms[dom] / max(1, ln[dom]), 4),
-            'avg_launch_gflop': round(fl[dom] / max(1, ln[dom]) / 1e9, 3),
-            'timing': 'HIP events bound to each kernel dispatch (hipExtLaunchKernelGGL start / stop events on the launch stream: kernel '
-                      'begins executing -> kernel complete, the interval rocprofv3 --kernel-trace reports), every large-GEMM launch of '
-                      'the timed region',
-            'all_large_gemm_tflops': round(gemm_all, 2),
-            'stream_markers': {
-                'note': 'the same launches bracketed by hipEventRecord markers on the launch stream: the interval also holds the time '
-                        'the dispatch waited behind the other stream\'s (higher-priority) decode kernels, so with the 2-slot pipeline '
-                        'it is longer than the kernel ran',
-                'achieved': round(mark_tf, 2), 'frac': round(mark_tf / PEAK_BF16_TFLOPS, 4),
-                'avg_launch_ms': round(ms[dom] / max(1, ln[dom]), 4)},
-            'achieved_busy': round(fl[dom] / (kbusy[dom] * 1e-3) / 1e12, 2) if kbusy[dom] > 0 else None,
-            'frac_busy': round(fl[dom] / (kbusy[dom] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if kbusy[dom] > 0 else None,
-            'busy_note': 'flops / length of the UNION of this kernel\'s execution intervals; differs from `achieved` (flops / summed '
-                         'durations) because launches of the kernel overlap each other: the 4 tag blocks run on an engine side stream '
-                         'next to caption blocks 8-11, and with encode_parts > 1 the batch parts run as separate chains',
-            'isolated': None if iso is None or iso[0][dom] <= 0 else {
-                'note': 'up to 20 of the same steps as ONE chain on one stream (no co-running kernels), untimed second pass',
-                'achieved': round(iso[1][dom] / (iso[0][dom] * 1e-3) / 1e12, 2),
-                'frac': round(iso[1][dom] / (iso[0][dom] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                'all_large_gemm_tflops': round(sum(iso[1]) / (sum(iso[0]) * 1e-3) / 1e12, 2)},
-            # the sampled steps are 0, STRIDE, 2 STRIDE, ... of the region
-            'large_gemm_share_of_step_time': round(tot_ms / len(range(0, args.steps, TIMING_STRIDE)) / (elapsed / args.steps * 1e3), 4),
-            'timing_sample': 'the large-GEMM launches of every %dth step of the timed region carry the events (launches / ms are the sampled ones); on every step they would cost 2.6 %% of it' % TIMING_STRIDE,
-            'events_region': 'the per-launch events are those of timed region #%d of %d (the last armed one); value / ms_per_step are the median region\'s' % (events_region + 1, len(regions)),
-            'per_variant': {VARIANT_NAMES.get(i, str(i)): {'launches': int(ln[i]), 'ms': round(kms[i], 3),
-                                                            'tflops': round(fl[i] / (kms[i] * 1e-3) / 1e12, 2)}
-                            for i in range(12) if ln[i] > 0},
-        },
     }
-    if not args.no_cpu_baseline and world == 1:
-        out['cpu_baseline'] = cpu_baseline()
+    if args.full:
+        # kms: durations from HIP events bound to the kernel dispatches (kernel begins executing -> complete: what rocprofv3
+        # --kernel-trace reports); ms: stream-marker brackets around the launches (also hold the dispatch's wait behind the other stream)
+        tot_ms = sum(kms)
+        tot_fl = sum(fl)
+        dom = max(range(12), key=lambda i: kms[i])
+        gemm_all = (tot_fl / (tot_ms * 1e-3)) / 1e12 if tot_ms > 0 else 0.0
+        dom_tf = (fl[dom] / (kms[dom] * 1e-3)) / 1e12 if kms[dom] > 0 else 0.0
+        mark_tf = (fl[dom] / (ms[dom] * 1e-3)) / 1e12 if ms[dom] > 0 else 0.0
+        traffic = None
+        try:      # HBM bytes per launch of the dominant kernel from the committed PMC passes (tools/pmc_traffic.sh);
+            # FETCH_SIZE doubled (gfx950 counts 128-B requests as 64 B), KiB -> bytes
+            four_wave = kernel_form(lib, B * 577 // (2 if (piped and B >= 32) else 1), dom, piped or args.gemm_tiles).startswith('4-wave')
+            tfile = TRAFFIC_FILE if B < 256 else TRAFFIC_FILE.replace('.json', '_b512.json')
+            with open(tfile) as f:
+                tab = json.load(f)
+            names = [n for n in tab if n.startswith(PMC_KERNEL_4W[dom])] if four_wave else [PMC_KERNEL[dom]]
+            traffic = max((tab[n] for n in names if n in tab), key=lambda e: e['launches'])['hbm_bytes_per_launch_corrected']
+            if B not in (64, 512):
+                traffic = None          # the committed passes are B = 64 and B = 512 runs
+        except Exception:
+            traffic = None
+        out.update({
+            'timed_regions_ms_per_step': [round(r / args.steps * 1e3, 3) for r in regions],
+            'timed_regions_note': ('median of %d regions of exactly K = %d steps each (a single region is shorter than 2 s); value / ms_per_step are the median region\'s' % (len(regions), args.steps)) if len(regions) > 1 else 'one region of exactly K steps',
+            'unarmed_ms_per_step': None if not isinstance(unarmed, float) else round(unarmed / args.steps * 1e3, 3),
+            'unarmed_note': 'one more region of K steps WITHOUT the two HIP events the engine records around every large-GEMM launch for the roofline: the difference to ms_per_step is the cost of the instrumentation inside the timed region',
+            'decode_phase_ms_per_batch': None if dec_ms is None else round(dec_ms, 3),
+            'extra': energy,
+            'roofline': {
+                'bound': 'mfma', 'kernel': VARIANT_NAMES.get(dom, 'gemm_nt variant %d' % dom),
+                'kernel_form': kernel_form(lib, B * 577 // (2 if (piped and B >= 32) else 1), dom, piped or args.gemm_tiles),
+                'encode_parts': int(os.environ['VITCAP_ENCODE_SPLIT']) if os.environ.get('VITCAP_ENCODE_SPLIT') else (2 if (piped and B >= 32) else 1),
+                'achieved': round(dom_tf, 2), 'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s',
+                'frac': round(dom_tf / PEAK_BF16_TFLOPS, 4) if ln[dom] else None, 'traffic': traffic,
+                'note': None if ln[dom] else 'no large-GEMM launch (M >= 2048 rows) in this configuration: the per-launch events cover those only',
+                'traffic_note': ('HBM bytes per launch from a COMMITTED rocprofv3 PMC pass, not measured in this run: (2*FETCH_SIZE+WRITE_SIZE)*1024 '
+                                 'in %s (tools/pmc_traffic.sh regenerates it)' % os.path.relpath(tfile, REPO)) if traffic else None,
+                'launches': int(ln[dom]), 'avg_launch_ms': round(kms[dom] / max(1, ln[dom]), 4),
+                'avg_launch_gflop': round(fl[dom] / max(1, ln[dom]) / 1e9, 3),
+                'timing': 'HIP events bound to each kernel dispatch (hipExtLaunchKernelGGL start / stop events on the launch stream: kernel '
+                          'begins executing -> kernel complete, the interval rocprofv3 --kernel-trace reports), every large-GEMM launch of '
+                          'the timed region',
+                'all_large_gemm_tflops': round(gemm_all, 2),
+                'stream_markers': {
+                    'note': 'the same launches bracketed by hipEventRecord markers on the launch stream: the interval also holds the time '
+                            'the dispatch waited behind the other stream\'s (higher-priority) decode kernels, so with the 2-slot pipeline '
+                            'it is longer than the kernel ran',
+                    'achieved': round(mark_tf, 2), 'frac': round(mark_tf / PEAK_BF16_TFLOPS, 4),
+                    'avg_launch_ms': round(ms[dom] / max(1, ln[dom]), 4)},
+                'achieved_busy': round(fl[dom] / (kbusy[dom] * 1e-3) / 1e12, 2) if kbusy[dom] > 0 else None,
+                'frac_busy': round(fl[dom] / (kbusy[dom] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if kbusy[dom] > 0 else None,
+                'busy_note': 'flops / length of the UNION of this kernel\'s execution intervals; differs from `achieved` (flops / summed '
+                             'durations) because launches of the kernel overlap each other: the 4 tag blocks run on an engine side stream '
+                             'next to caption blocks 8-11, and with encode_parts > 1 the batch parts run as separate chains',
+                'isolated': None if iso is None or iso[0][dom] <= 0 else {
+                    'note': 'up to 20 of the same steps as ONE chain on one stream (no co-running kernels), untimed second pass',
+                    'achieved': round(iso[1][dom] / (iso[0][dom] * 1e-3) / 1e12, 2),
+                    'frac': round(iso[1][dom] / (iso[0][dom] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                    'all_large_gemm_tflops': round(sum(iso[1]) / (sum(iso[0]) * 1e-3) / 1e12, 2)},
+                # the sampled steps are 0, STRIDE, 2 STRIDE, ... of the region
+                'large_gemm_share_of_step_time': round(tot_ms / len(range(0, args.steps, TIMING_STRIDE)) / (elapsed / args.steps * 1e3), 4),
+                'timing_sample': 'the large-GEMM launches of every %dth step of the timed region carry the events (launches / ms are the sampled ones); on every step they would cost 2.6 %% of it' % TIMING_STRIDE,
+                'events_region': 'the per-launch events are those of timed region #%d of %d (the last armed one); value / ms_per_step are the median region\'s' % (events_region + 1, len(regions)),
+                'per_variant': {VARIANT_NAMES.get(i, str(i)): {'launches': int(ln[i]), 'ms': round(kms[i], 3),
+                                                                'tflops': round(fl[i] / (kms[i] * 1e-3) / 1e12, 2)}
+                                for i in range(12) if ln[i] > 0},
+            },
+        })
+        if not args.no_cpu_baseline and world == 1:
+            out['cpu_baseline'] = cpu_baseline()
     emit(out)
     if dist is not None:
         dist.barrier()

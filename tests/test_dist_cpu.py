@@ -264,3 +264,27 @@ def test_bench_self_launches_n_ranks():
     bad = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--stub', '--steps', '1'],
                          env=dict(env, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0'), capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and 'WORLD_SIZE' in bad.stderr
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's outputs as DIR/<name>.npy (float64 here), identical from run to run with
+    the same arguments; ranks > 0 write theirs with a _rank<r> suffix.  CPU stand-in workload (gloo)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    got = []
+    for run, gpus in enumerate(('1', '1', '2')):
+        d = tmp_path / ('run%d' % run)
+        out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', gpus, '--steps', '2', '--warmup', '1', '--stub',
+                              '--dump-outputs', str(d)], env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][0])
+        assert rec['steps'] == 2 and rec['ms_per_step'] > 0
+        got.append({f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    assert list(got[0]) == ['stub_sum.npy'] and got[0]['stub_sum.npy'].dtype == np.float64
+    assert np.array_equal(got[0]['stub_sum.npy'], got[1]['stub_sum.npy'])
+    assert list(got[2]) == ['stub_sum.npy', 'stub_sum_rank1.npy']
+    assert np.array_equal(got[2]['stub_sum_rank1.npy'], got[0]['stub_sum.npy'])

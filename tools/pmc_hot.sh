@@ -1,21 +1,23 @@
 #!/bin/bash
-# usage (GPU box): bash tools/pmc_hot.sh <tag>
-# MFMA-busy / instruction-mix / wait-fraction counters of the hot kernels -> gpurun_out/<tag>_mfma_busy_pmc.json
+# usage (on an MI355X): bash tools/pmc_hot.sh <tag>
+# MFMA-busy / instruction-mix / wait-fraction counters of the hot kernels -> $OUT/<tag>_mfma_busy_pmc.json (OUT defaults to out/)
 # (three `rocprofv3 --pmc` passes per workload, --kernel-trace only: SQ has 8 slots per pass).  Workloads: the greedy B=64
 # step on ONE stream (bench.py --pipeline 0) and one cross-entropy training step.
 TAG=${1:-r03}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+export OUT=${OUT:-$R/out}
+mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/pmc_${TAG}
+mkdir -p $OUT/pmc_${TAG}
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 P2="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVES"
 P3="SQ_INST_CYCLES_VMEM SQ_WAIT_INST_VMEM SQ_ACTIVE_INST_VMEM SQ_INSTS_VALU_TRANS SQ_INSTS_MFMA SQ_ACTIVE_INST_MISC SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"
 for wl in greedy train; do
-  if [ $wl = greedy ]; then ARGS="--steps 2 --warmup 1 --pipeline 0 --isolated 0 --no-cpu-baseline --single-region --power 0"; else ARGS="--mode train --steps 1 --warmup 1"; fi
+  if [ $wl = greedy ]; then ARGS="--full --steps 2 --warmup 1 --pipeline 0 --isolated 0 --no-cpu-baseline --single-region --power 0"; else ARGS="--mode train --steps 1 --warmup 1"; fi
   i=0
   for P in "$P1" "$P2" "$P3"; do
     i=$((i+1))
-    rocprofv3 --kernel-trace --pmc $P --output-format csv -d $R/gpurun_out/pmc_${TAG}/${wl}_p$i -o p -- python3 $R/bench.py $ARGS > $R/gpurun_out/pmc_${TAG}/${wl}_p$i.log 2>&1
+    rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/pmc_${TAG}/${wl}_p$i -o p -- python3 $R/bench.py $ARGS > $OUT/pmc_${TAG}/${wl}_p$i.log 2>&1
   done
 done
 cd $R
@@ -27,7 +29,7 @@ for wl in ('greedy', 'train'):
     per = collections.defaultdict(lambda: collections.defaultdict(list))
     dur = collections.defaultdict(list)
     for p in (1, 2, 3):
-        d = 'gpurun_out/pmc_%s/%s_p%d' % (tag, wl, p)
+        d = os.path.join(os.environ['OUT'], 'pmc_%s/%s_p%d' % (tag, wl, p))
         f = None
         for root, _, files in os.walk(d):
             for x in files:
@@ -69,7 +71,7 @@ for wl in ('greedy', 'train'):
             d['instruction_mix'] = {k[9:].lower(): round(v / tot, 4) for k, v in ins.items()}
         out[n] = d
     res[wl] = out
-json.dump(res, open('gpurun_out/%s_mfma_busy_pmc.json' % tag, 'w'), indent=1, sort_keys=True)
+json.dump(res, open(os.path.join(os.environ['OUT'], '%s_mfma_busy_pmc.json' % tag), 'w'), indent=1, sort_keys=True)
 for wl, out in res.items():
     print('==', wl)
     for n, d in sorted(out.items(), key=lambda x: -x[1]['counters_avg_per_launch'].get('SQ_BUSY_CYCLES', 0) * x[1]['counters_avg_per_launch']['launches_sampled'])[:14]:
