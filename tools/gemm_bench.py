@@ -31,7 +31,7 @@ def check(M, N, K, hint):
     return float((got - want).abs().max())
 
 if __name__ == '__main__':
-    hints = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 else [2, 3]
+    hints = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 else [2, 5]
     Ms = [int(x) for x in sys.argv[2].split(',')] if len(sys.argv) > 2 else [36928]
     for h in hints:
         print('hint', h, 'max err vs torch (M=1000,N=768,K=768):', check(1000, 768, 768, h), check(4099, 2304, 3072, h))

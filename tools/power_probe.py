@@ -3,8 +3,8 @@ in a side thread while ONE GEMM shape is launched back to back for a few seconds
 
     python tools/power_probe.py [seconds per arm] > profiles/r05_power_probe.txt
 
-Arms: idle; qkv shape (N 2304, K 768) at M = 36 928 and 295 424 with the 4-wave persistent kernel (tile_hint 42), the 8-wave kernel
-(32), the 8-wave ablation without LDS-DMA (7: same MFMA stream, no data movement; wrong results), each on uniform(-1, 1) operands and
+Arms: idle; qkv shape (N 2304, K 768) at M = 36 928 and 295 424 with the 4-wave persistent kernel (tile_hint 42) and the 8-wave kernel
+(32), each on uniform(-1, 1) operands and
 on zero operands (the guide's DVFS note: zero operands toggle no multiplier bits).  Reports TFLOP/s from torch events over the whole
 arm, and min / median / max of the sampled sclk and power."""
 import json
@@ -95,7 +95,7 @@ def main():
             bias = torch.rand(N, device='cuda')
             out = torch.empty(M, N, device='cuda', dtype=torch.bfloat16)
             gf = 2.0 * M * N * K / 1e9
-            for label, hint in (('4-wave persistent (42)', 42), ('8-wave 256-row tiles (32)', 32), ('8-wave, no LDS-DMA in the loop (7, ablation)', 7)):
+            for label, hint in (('4-wave persistent (42)', 42), ('8-wave 256-row tiles (32)', 32)):
                 run_arm('qkv M=%d %s, %s' % (M, fill, label), lambda: ops.gemm_bias_act(a, w, bias, act=0, out=out, tile_hint=hint), seconds, gf)
             del a, w, out
 

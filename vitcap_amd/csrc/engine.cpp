@@ -73,7 +73,6 @@ struct vitcap_engine {
   hipStream_t part[3] = {nullptr, nullptr, nullptr};   // streams of encoder parts 1..3 (part 0 runs on the caller's stream)
   hipEvent_t ev_pfork = nullptr, ev_pjoin[3] = {nullptr, nullptr, nullptr};
   bool full_last_tag_block = false;   // VITCAP_FULL_TAG_BLOCK=1: compute all 577 rows of tag_blocks[3] (parity taps / measurements)
-  bool fork_tag_branch = true;
   std::vector<GemmTiming> pool;
   size_t used = 0;
   std::vector<GraphEntry> graphs;     // captured decode loops (vitcap_gen_opts.use_graph)
@@ -181,7 +180,6 @@ struct Layout {
   size_t hd_f, hd_b, logits, rowstat;
   size_t ids, ids2, unf, sum_lp, cnt, margins, logprob, last_tok, live;
   size_t cand_val, cand_idx, lse, beam_scores, parent, done, has_hyp, hyp_score, hyp_len, hyp_tok, fin_ids, fin_lp;
-  size_t ln_cnt, ln_cnt_tag;   // row-block ticket counters of the GEMMs that normalise their own rows (main chain / tag branch); (4 B + 16) ints each
   size_t vt[4];      // beam search: per decoder layer the visual V rows transposed per (image, head) for vitcap_attn_decode_beams (0: unused)
   // tag rows visible to the caption (vitcap_gen_opts.tag_visible = n > 0): per embedding branch v in {A, B}
   size_t tagx_f[2], tagx_b[2], tqkv_c[2][4], jqkv, jout, jlse, tg_ctx, tg_sa_f, tg_sa_b, tg_mlp, tg_tmp;
@@ -205,7 +203,6 @@ struct Layout {
     for (int l = 0; l < 4; ++l) if (v.vt[l]) v.vt[l] += i * VT_BYTES;
     v.pool_in += i * D * 2; v.pooled += i * D * 2; v.tg_f += i * D * 4; v.tg_b += i * D * 2;
     v.tag_logits += i * VP * 4; v.tag_ids += i * TOPK * 8; v.tag_prob += i * TOPK * 4; v.tag_len += i * 8;
-    v.ln_cnt += i * 4 * 4; v.ln_cnt_tag += i * 4 * 4;      // a part of n images owns <= 3.01 n + 1 row blocks of 192+ rows
     return v;
   }
   Layout(int B, const vitcap_gen_opts& o) {
@@ -243,8 +240,6 @@ struct Layout {
     tag_ids = take(b * TOPK * 8);
     tag_prob = take(b * TOPK * 4);
     tag_len = take(b * 8);
-    ln_cnt = take((b * 4 + 16) * 4);
-    ln_cnt_tag = take((b * 4 + 16) * 4);
     xs_f = take(n * 2 * D * 4);
     xs_b = take(n * 2 * D * 2);
     sqkv = take(n * 2 * 3 * D * 2);
@@ -336,16 +331,9 @@ thread_local const int32_t* g_live = nullptr;    // live counter handed to the d
 // sets the per-call context (timing hook, GEMM launch form, early-exit counter) for the duration of one engine call
 // Zig-zag walk of the encoder / prefill chain (common.h: vc_tls_walk_rev): `zz()` after every streaming launch flips the direction
 // for the next one, so that each kernel starts on the rows its producer wrote last (still in the Infinity Cache).
-// VITCAP_ZIGZAG=0 keeps every kernel first-to-last (A/B measurements).
-static bool zigzag_on() {
-  static const bool on = [] { const char* e = getenv("VITCAP_ZIGZAG"); return e ? atoi(e) != 0 : true; }();
-  return on;
-}
-static inline void zz() {
-  if (zigzag_on()) vc_tls_walk_rev = !vc_tls_walk_rev;
-}
+static inline void zz() { vc_tls_walk_rev = !vc_tls_walk_rev; }
 struct WalkScope {        // the direction never leaks out of an engine call
-  WalkScope() { vc_tls_walk_rev = false; vc_tls_zigzag = zigzag_on(); }
+  WalkScope() { vc_tls_walk_rev = false; vc_tls_zigzag = true; }
   ~WalkScope() { vc_tls_walk_rev = false; vc_tls_zigzag = false; }
 };
 
@@ -383,9 +371,8 @@ int gemm_desc(const void* A, const void* W, const float* bias, const float* res,
     // Round 6: from 64k rows per launch on (B = 512) the bf16-output GEMMs (qkv, fc1) run the PERSISTENT 4-wave form, whose A-panel
     // prefetch exists for that size class (gemm4w.hip PF) -- +0.4-0.9 % images/s, -1 % joules per step at B = 512
     // (profiles/r06_prefetch_ab_b512.txt) -- but only next to a greedy decode chain: beside the 1 280-sequence chain of beam 5 x 256 the
-    // persistent grids cost -3.4 % (3 688 -> 3 562 img/s, profiles/r06_decode_forms_and_beam_ab.txt).  VITCAP_GEMM_4W_MIX_BIG=0 turns it off.
-    static const int mix_big = [] { const char* v = getenv("VITCAP_GEMM_4W_MIX_BIG"); return v ? atoi(v) : 1; }();
-    if (mix_big && g_light_decode && d.M >= 65536 && d.out_dtype == VITCAP_OUT_BF16 && !res && (d.N & 255) == 0 && d.K >= 192 && d.row_group == 0 &&
+    // persistent grids cost -3.4 % (3 688 -> 3 562 img/s, profiles/r06_decode_forms_and_beam_ab.txt).
+    if (g_light_decode && d.M >= 65536 && d.out_dtype == VITCAP_OUT_BF16 && !res && (d.N & 255) == 0 && d.K >= 192 && d.row_group == 0 &&
         !d.colsum && !d.rowstat)
       d.tile_hint = 42;
   }
@@ -418,10 +405,11 @@ int gemm(const void* A, int lda, const void* W, const float* bias, const float* 
   return gemm_desc(A, W, bias, res, C, d, s);
 }
 
-// residual GEMM (N = 768, fp32 out) + LayerNorm of its finished rows -> ln_b (bf16) / ln_f (fp32, optional): one launch where the
-// kernel normalises its own rows (vitcap_gemm_desc.ln_*), GEMM + LayerNorm launches otherwise; same bits either way
+// residual GEMM (N = 768, fp32 out) + LayerNorm of its finished rows -> ln_b (bf16) / ln_f (fp32, optional).  No ln_counters are handed
+// over, so vitcap_gemm_ex launches the LayerNorm kernel behind the GEMM: the in-kernel LayerNorm is bit-identical and SLOWER
+// (docs/LAB_r01_r04.md 4.3)
 int gemm_ln(const void* A, int lda, const void* W, const float* bias, const float* res, void* C, int M, int K, const float* g,
-            const float* beta, float eps, void* ln_b, float* ln_f, int32_t* cnt, void* s) {
+            const float* beta, float eps, void* ln_b, float* ln_f, void* s) {
   vitcap_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.abi = VITCAP_ABI_VERSION;
@@ -429,10 +417,7 @@ int gemm_ln(const void* A, int lda, const void* W, const float* bias, const floa
   d.lda = lda; d.ldw = K; d.ldc = D; d.ldr = D;
   d.act = VITCAP_ACT_NONE; d.out_dtype = VITCAP_OUT_F32;
   d.ln_gamma = g; d.ln_beta = beta; d.ln_eps = eps;
-  // the in-kernel LayerNorm (last arriver of a row block) is built, bit-identical and SLOWER than the separate launch (docs/LAB_r01_r04.md 4.3):
-  // the counters are handed over only under VITCAP_GEMM_LN_FUSE=1, otherwise vitcap_gemm_ex launches the LayerNorm kernel behind the GEMM
-  static const int fuse = [] { const char* e = getenv("VITCAP_GEMM_LN_FUSE"); return e ? atoi(e) : 0; }();
-  d.ln_out_bf16 = ln_b; d.ln_out_f32 = ln_f; d.ln_counters = fuse ? cnt : nullptr;
+  d.ln_out_bf16 = ln_b; d.ln_out_f32 = ln_f;
   return gemm_desc(A, W, bias, res, C, d, s);
 }
 
@@ -447,24 +432,20 @@ int gemm_split(const void* A, int lda, const void* W, void* partials, int M, int
   return gemm_desc(A, W, nullptr, nullptr, partials, d, s);
 }
 
-// Decode-step GEMMs with few rows (M <= 1024).  `hint` 20 / 21 / 22 name the "resident" kernel form (the whole 768-long k range of a
-// tile requested at once); see below for which form actually runs.
-int gemm_small(const void* A, int lda, const void* W, const float* bias, void* C, int ldc, int M, int N, int K, int act, int out,
-               int hint, void* s) {
+// Decode-step GEMMs with few rows (M <= 1024), K = 768 or a multiple of it: the 4-stage LDS-DMA ring on small tiles.
+int gemm_ring(const void* A, int lda, const void* W, const float* bias, void* C, int ldc, int M, int N, int K, int act, int out,
+              void* s) {
   vitcap_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.abi = VITCAP_ABI_VERSION;
   d.M = M; d.N = N; d.K = K;
   d.lda = lda; d.ldw = K; d.ldc = ldc;
   d.act = act; d.out_dtype = out;
-  d.tile_hint = hint;
-  // K = 768: the 4-stage LDS-DMA ring on 64x32 (32x32 for a handful of rows) tiles.  Round 2 used the resident whole-K form here
-  // too -- a workaround for the ring's counted waits having silently become vmcnt(0) (docs/LAB_r01_r04.md 4.2 i); with the waits real the
-  // ring wins at every batch size: decode phase 5.54 -> 5.28 ms at 64 images, 3.84 -> 3.59 at one, 8.65 -> 7.78 at 128.
-  if (K == 768 && hint >= 20 && hint <= 22) d.tile_hint = M <= 32 ? 14 : 13;
-  // K = 3072 (`output.dense`): the same ring with one raw fp32 slab per 768-long k range (hints 23 / 24 = the resident form's
-  // contract): decode phase 5.24 -> 5.13 ms at 64 images, 3.58 -> 3.48 at one
-  if (K > 768 && K % 768 == 0 && hint >= 20 && hint <= 22) d.tile_hint = M <= 32 ? 24 : 23;
+  // 64x32 (32x32 for a handful of rows) tiles.  The ring beats the resident whole-K form (tile_hint 20 / 21) at every batch size
+  // once its counted waits are real (docs/LAB_r01_r04.md 4.2 i): decode phase 5.54 -> 5.28 ms at 64 images, 3.84 -> 3.59 at one.
+  // K > 768 (`output.dense`, K = 3072): one raw fp32 slab per 768-long k range, summed by vitcap_sum_layernorm (5.24 -> 5.13 ms)
+  if (K == 768) d.tile_hint = M <= 32 ? 14 : 13;
+  else d.tile_hint = M <= 32 ? 24 : 23;
   return gemm_desc(A, W, bias, nullptr, C, d, s);
 }
 
@@ -506,8 +487,6 @@ extern "C" int vitcap_engine_create(vitcap_engine** out) {
   if (!out) return VITCAP_EINVAL;
   *out = new (std::nothrow) vitcap_engine();
   if (*out) {
-    const char* f = getenv("VITCAP_TAG_FORK");     // 0: keep the tag branch on the caller's stream
-    (*out)->fork_tag_branch = f ? atoi(f) != 0 : true;
     const char* t = getenv("VITCAP_FULL_TAG_BLOCK");
     (*out)->full_last_tag_block = t ? atoi(t) != 0 : false;
   }
@@ -697,7 +676,7 @@ static int check(vitcap_engine* e, int B, const vitcap_gen_opts& o, void* ws, si
 // output on the same chain, or null -- its norm1 then rides in this block's fc2 (-> h); norm2 always rides in proj.  Each fused
 // LayerNorm is the separate vitcap_layernorm_fwd launch's arithmetic on the same fp32 rows (vitcap_gemm_desc.ln_*).
 static int vit_block(const vitcap_vit_block_w& w, const float* x_in, float* x, void* h, void* qkv, void* mlp, int B, void* s,
-                     int32_t* cnt = nullptr, bool have_ln1 = false, const vitcap_vit_block_w* next = nullptr) {
+                     bool have_ln1 = false, const vitcap_vit_block_w* next = nullptr) {
   const int M = B * NV;
   // zz(): each streaming kernel walks the rows the other way round than the one before it (common.h: vc_tls_walk_rev); gemm_ln is two
   // launches (GEMM, then the LayerNorm of its rows) and flips between them itself
@@ -707,11 +686,11 @@ static int vit_block(const vitcap_vit_block_w& w, const float* x_in, float* x, v
   CK(vitcap_attn_dense_fwd(qkv, h, B, NV, 0.125f, s));
   zz();
   // proj reads h (the attention output) as A and its norm2 writes h: a row block's A rows are read by its own three tiles only
-  CK(gemm_ln(h, D, w.proj_w, w.proj_b, x_in, x, M, D, w.n2_g, w.n2_b, 1e-6f, h, nullptr, cnt, s));      // GEMM, LayerNorm: two flips = none
+  CK(gemm_ln(h, D, w.proj_w, w.proj_b, x_in, x, M, D, w.n2_g, w.n2_b, 1e-6f, h, nullptr, s));      // GEMM, LayerNorm: two flips = none
   CK(gemm(h, D, w.fc1_w, w.fc1_b, nullptr, 0, mlp, 4 * D, M, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16, s));
   zz();
   if (next) {
-    CK(gemm_ln(mlp, 4 * D, w.fc2_w, w.fc2_b, x, x, M, 4 * D, next->n1_g, next->n1_b, 1e-6f, h, nullptr, cnt, s));
+    CK(gemm_ln(mlp, 4 * D, w.fc2_w, w.fc2_b, x, x, M, 4 * D, next->n1_g, next->n1_b, 1e-6f, h, nullptr, s));
   } else {
     CK(gemm(mlp, 4 * D, w.fc2_w, w.fc2_b, x, D, x, D, M, D, 4 * D, VITCAP_ACT_NONE, VITCAP_OUT_F32, s));
     zz();
@@ -762,13 +741,8 @@ static int encode_part(vitcap_engine* e, const void* image, int image_is_bf16, i
   // a5: 12 blocks, fork before block 8, 4 tag blocks on the fork.  Run the fork on a side stream when the large GEMMs are
   // in their one-tile-per-workgroup form (batch pipeline) and the batch is small enough for tile-quantisation gaps to
   // matter: B=64 pipelined +2.3 %; with persistent GEMMs or at B=512 it costs 1-2 % (measured), so it stays serial there.
-  const bool fork = allow_fork && e->fork_tag_branch && o.gemm_mode == VITCAP_GEMM_TILES && B <= 128;
+  const bool fork = allow_fork && o.gemm_mode == VITCAP_GEMM_TILES && B <= 128;
   float* x2 = (float*)(ws + lo.x2);
-  // ticket counters of the GEMMs that normalise their own rows: zero before the first of them (the workspace is the caller's)
-  int32_t* cnt = (int32_t*)(ws + lo.ln_cnt);
-  // (exactly this part's 4 B counters: a batch part on another stream owns the ints behind them)
-  HIPCK(hipMemsetAsync(cnt, 0, (size_t)B * 4 * 4, (hipStream_t)s), "encode: counters");
-  HIPCK(hipMemsetAsync(ws + lo.ln_cnt_tag, 0, (size_t)B * 4 * 4, (hipStream_t)s), "encode: counters");
   for (int i = 0; i < 12; ++i) {
     if (i == 8 && fork) {
       // fork: the tag branch depends only on x (the output of block 7), which nobody writes from here on
@@ -787,8 +761,8 @@ static int encode_part(vitcap_engine* e, const void* image, int image_is_bf16, i
     }
     // norm1 of block i+1 rides in block i's fc2 (block 7 feeds block 8 that way; the tag branch normalises the fork state itself)
     const vitcap_vit_block_w* next = i + 1 < 12 ? &w.blocks[i + 1] : nullptr;
-    if (i < 8) CK(vit_block(w.blocks[i], x, x, ws + lo.h, ws + lo.qkv, ws + lo.mlp, B, s, cnt, i > 0, next));
-    else CK(vit_block(w.blocks[i], i == 8 ? x : x2, x2, ws + lo.h, ws + lo.qkv, ws + lo.mlp, B, s, cnt, true, next));
+    if (i < 8) CK(vit_block(w.blocks[i], x, x, ws + lo.h, ws + lo.qkv, ws + lo.mlp, B, s, i > 0, next));
+    else CK(vit_block(w.blocks[i], i == 8 ? x : x2, x2, ws + lo.h, ws + lo.qkv, ws + lo.mlp, B, s, true, next));
   }
   if (fork) {
     HIPCK(hipStreamWaitEvent((hipStream_t)s, e->ev_join, 0), "encode: join wait");
@@ -886,11 +860,10 @@ static int tag_branch(vitcap_engine* e, const Layout& lo, char* ws, int B, void*
   const vitcap_weights& w = e->w;
   float* xt = (float*)(ws + lo.xt);
   const float* xf = (const float*)(ws + lo.x);       // fork state (output of block 7)
-  int32_t* cnt = (int32_t*)(ws + lo.ln_cnt_tag);      // its own counters: the branch may run next to caption blocks 8-11
   for (int i = 0; i < 3; ++i)
-    CK(vit_block(w.tag_blocks[i], i == 0 ? xf : xt, xt, ws + lo.th, ws + lo.tqkv, ws + lo.tmlp, B, s, cnt, i > 0, &w.tag_blocks[i + 1]));
+    CK(vit_block(w.tag_blocks[i], i == 0 ? xf : xt, xt, ws + lo.th, ws + lo.tqkv, ws + lo.tmlp, B, s, i > 0, &w.tag_blocks[i + 1]));
   if (e->full_last_tag_block)
-    CK(vit_block(w.tag_blocks[3], xt, xt, ws + lo.th, ws + lo.tqkv, ws + lo.tmlp, B, s, cnt, true, nullptr));
+    CK(vit_block(w.tag_blocks[3], xt, xt, ws + lo.th, ws + lo.tqkv, ws + lo.tmlp, B, s, true, nullptr));
   else
     CK(vit_block_cls_only(w.tag_blocks[3], xt, ws + lo.th, ws + lo.tqkv, ws + lo.tmlp, ws + lo.pool_in, B, s, true));
   CK(vitcap_gather_rows_bf16(xt, NV, ws + lo.pool_in, B, D, s));
@@ -966,9 +939,6 @@ static int prefill_part(vitcap_engine* e, int B, const vitcap_gen_opts& o, const
   float* vis_f = (float*)(ws + lo.vis_f);
   void* vis_b = ws + lo.vis_b;
   CK(vitcap_assemble_visual((const float*)(ws + lo.x2), (const float*)(ws + lo.xt), vis_f, vis_b, B, NV, s));
-  // the ticket counters of the GEMMs that normalise their own rows are zero on exit of every completed launch; zero them here as well,
-  // so that a launch that was aborted (or a caller that runs prefill without encode) cannot poison the next one
-  HIPCK(hipMemsetAsync(ws + lo.ln_cnt, 0, (size_t)B * 4 * 4, (hipStream_t)s), "prefill: counters");
   for (int l = 0; l < 4; ++l) {
     const vitcap_bert_layer_w& lw = w.dec[l];
     void* dq = ws + lo.dqkv[l];
@@ -983,15 +953,14 @@ static int prefill_part(vitcap_engine* e, int B, const vitcap_gen_opts& o, const
     if (lo.vt[l]) CK(vitcap_attn_beam_vt(dq, ws + lo.vt[l], B, SV, s));
     CK(vitcap_attn_dense_fwd(dq, ws + lo.h, B, SV, 0.125f, s));
     zz();
-    // BertSelfOutput / BertOutput: dense + residual, then LayerNorm (post-LN) -- the LayerNorm rides in the GEMM
-    int32_t* cnt = (int32_t*)(ws + lo.ln_cnt);
+    // BertSelfOutput / BertOutput: dense + residual, then LayerNorm (post-LN)
     CK(gemm_ln(ws + lo.h, D, lw.ao_w, lw.ao_b, vis_f, ws + lo.dtmp, M, D, lw.ao_g, lw.ao_beta, 1e-12f, ws + lo.da_b,
-               (float*)(ws + lo.da_f), cnt, s));
+               (float*)(ws + lo.da_f), s));
     CK(gemm(ws + lo.da_b, D, lw.i_w, lw.i_b, nullptr, 0, ws + lo.mlp, 4 * D, M, 4 * D, D, VITCAP_ACT_GELU_ERF,
             VITCAP_OUT_BF16, s));
     zz();
     CK(gemm_ln(ws + lo.mlp, 4 * D, lw.o_w, lw.o_b, (const float*)(ws + lo.da_f), ws + lo.dtmp, M, 4 * D, lw.o_g, lw.o_beta, 1e-12f,
-               vis_b, vis_f, cnt, s));
+               vis_b, vis_f, s));
   }
   if (lo.NT > 0) CK(prefill_tags(e, B, o, lo, ws, s));
   return VITCAP_OK;
@@ -1035,29 +1004,27 @@ static int step_forward(const vitcap_weights& w, const Layout& lo, const vitcap_
   if (embed)          // otherwise the previous step's vitcap_greedy_select_embed already wrote this step's x
     CK(vitcap_embed_step(ids, L, t, o.mask_token_id, w.word_emb, w.pos_emb, w.type_emb, w.emb_ln_g, w.emb_ln_b, 1e-12f, xs_f, xs_b,
                          ns, s));
-  static const int force_old = [] { const char* e = getenv("VITCAP_DECODE_SPLITK"); return e ? atoi(e) : 0; }();   // A/B measurements
-  // small-tile LDS-DMA ring kernels (gemm_small) for batches of few rows; larger ones take the big-tile / split-K path.  The choice
+  // small-tile LDS-DMA ring kernels (gemm_ring) for batches of few rows; larger ones take the big-tile / split-K path.  The choice
   // follows the WHOLE batch, so that a sequence's arithmetic does not depend on how the batch is sliced.
-  // up to 1024 rows (512 sequences) the small-tile ring forms of gemm_small win (decode phase 13.2 -> 11.9 ms at 256 images,
+  // up to 1024 rows (512 sequences) the small-tile ring forms of gemm_ring win (decode phase 13.2 -> 11.9 ms at 256 images,
   // 20.4 -> 19.9 at 512); at 2560 rows (5 beams x 256 images) the 128x128 / 256x256 tiles do (21.4 against 23.8 ms)
-  const bool small = 2 * NS <= 1024 && !force_old;
-  static const int no_beam_attn = [] { const char* e = getenv("VITCAP_BEAM_ATTN_VALU"); return e ? atoi(e) : 0; }();   // A/B measurements
+  const bool small = 2 * NS <= 1024;
   for (int l = 0; l < 4; ++l) {
     const vitcap_bert_layer_w& lw = w.dec[l];
     char* tc = tcache + ((size_t)l * NS + pt.s0) * L * 2 * D * 2;
     const char* vis = ws + lo.dqkv[l] + (size_t)pt.i0 * SV * 3 * D * 2;
     if (small)
-      CK(gemm_small(xs_b, D, lw.qkv_w, lw.qkv_b, sqkv, 3 * D, R, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16, 20, s));
+      CK(gemm_ring(xs_b, D, lw.qkv_w, lw.qkv_b, sqkv, 3 * D, R, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16, s));
     else
       CK(gemm(xs_b, D, lw.qkv_w, lw.qkv_b, nullptr, 0, sqkv, 3 * D, R, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16, s));
     if (lo.NT > 0)
       CK(vitcap_attn_decode_step_tags(sqkv, vis, tc, sctx, ns, SV, t, L, K, 0.125f,
                                       ws + lo.tqkv_c[0][l] + (size_t)pt.i0 * lo.NT * 3 * D * 2, ws + lo.tqkv_c[1][l] + (size_t)pt.i0 * lo.NT * 3 * D * 2,
                                       lo.NT, (const int64_t*)(ws + lo.tag_len), s));
-    else if (lo.vt[l] && K >= 2 && K <= 8 && !no_beam_attn)
+    else if (lo.vt[l] && K >= 2 && K <= 8)
       // several sequences per image (beam search): all of an image's query rows against its visual rows on the matrix pipe
       CK(vitcap_attn_decode_beams(sqkv, vis, ws + lo.vt[l] + (size_t)pt.i0 * VT_BYTES, tc, sctx, ns / K, K, SV, t, L, 0.125f, s));
-    else if (lo.vt[l] && K > 8 && lo.group_k > 1 && !no_beam_attn)
+    else if (lo.vt[l] && K > 8 && lo.group_k > 1)
       // more than 8 sequences per image (constrained beam search: states x beams): groups of group_k sequences, K / group_k per image
       CK(vitcap_attn_decode_beam_groups(sqkv, vis, ws + lo.vt[l] + (size_t)pt.i0 * VT_BYTES, tc, sctx, ns / K, lo.group_k, K / lo.group_k, SV, t,
                                         L, 0.125f, s));
@@ -1072,18 +1039,18 @@ static int step_forward(const vitcap_weights& w, const Layout& lo, const vitcap_
     const int rows_all = 2 * NS;
     int s_ao = rows_all >= 2048 ? 1 : (rows_all >= 1024 ? 2 : SPLIT_AO), s_fc2 = rows_all >= 1024 ? 4 : SPLIT_FC2;
     if (small) {
-      CK(gemm_small(sctx, D, lw.ao_w, nullptr, part, D, R, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32, 21, s));
+      CK(gemm_ring(sctx, D, lw.ao_w, nullptr, part, D, R, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32, s));
       s_ao = 1;
     } else {
       CK(gemm_split(sctx, D, lw.ao_w, part, R, D, D, s_ao, s));
     }
     CK(vitcap_sum_layernorm(part, s_ao, (size_t)R * D, lw.ao_b, xs_f, D, 0, lw.ao_g, lw.ao_beta, 1e-12f, sa_b, sa_f, R, D, s));
     if (small)
-      CK(gemm_small(sa_b, D, lw.i_w, lw.i_b, smlp, 4 * D, R, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16, 20, s));
+      CK(gemm_ring(sa_b, D, lw.i_w, lw.i_b, smlp, 4 * D, R, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16, s));
     else
       CK(gemm(sa_b, D, lw.i_w, lw.i_b, nullptr, 0, smlp, 4 * D, R, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16, s));
     if (small) {
-      CK(gemm_small(smlp, 4 * D, lw.o_w, nullptr, part, D, R, D, 4 * D, VITCAP_ACT_NONE, VITCAP_OUT_F32, 20, s));
+      CK(gemm_ring(smlp, 4 * D, lw.o_w, nullptr, part, D, R, D, 4 * D, VITCAP_ACT_NONE, VITCAP_OUT_F32, s));
       s_fc2 = 4;
     } else {
       CK(gemm_split(smlp, 4 * D, lw.o_w, part, R, D, 4 * D, s_fc2, s));
@@ -1092,7 +1059,7 @@ static int step_forward(const vitcap_weights& w, const Layout& lo, const vitcap_
   }
   // LM head on the [MASK] rows (row 1 of every pair): A = xs_b + 768, lda = 1536
   if (small) {
-    CK(gemm_small(xs_b + D * 2, 2 * D, w.cls.dense_w, nullptr, part, D, ns, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32, 21, s));
+    CK(gemm_ring(xs_b + D * 2, 2 * D, w.cls.dense_w, nullptr, part, D, ns, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32, s));
     CK(vitcap_sum_layernorm(part, 1, (size_t)ns * D, w.cls.dense_b, nullptr, 0, 1, w.cls.ln_g, w.cls.ln_b, 1e-12f, hd_b, nullptr, ns, D, s));
   } else {
     const int s_hd = NS >= 2048 ? 1 : (NS >= 1024 ? 2 : SPLIT_AO);      // as above, by the whole batch's [MASK] rows
@@ -1131,8 +1098,7 @@ static int greedy_loop(vitcap_engine* e, const Layout& lo, const vitcap_gen_opts
   // Plain greedy decoding of a small batch: the vocabulary GEMM also emits per-piece (max, argmax, sum exp) of its rows, and ONE
   // kernel turns them into the token, its log-prob, the bookkeeping and the NEXT step's embedded rows -- instead of reading the
   // 30522-wide fp32 rows back (greedy_step 18.7 us) and a separate embedding launch per step.
-  static const int no_fuse = [] { const char* e = getenv("VITCAP_DECODE_NOFUSE"); return e ? atoi(e) : 0; }();
-  const bool fused = !o.sampling.do_sample && o.repetition_penalty == 1.0f && NS <= 128 && !no_fuse;
+  const bool fused = !o.sampling.do_sample && o.repetition_penalty == 1.0f && NS <= 128;
   // two slices on two streams (decode_streams = 2): measured at 64 sequences, eager and graph-replayed: 5.96 ms per batch against
   // 5.66 ms for one chain -- the ~4.5 us per dependent small kernel is not hidden by a second chain (the dispatch path is the
   // shared resource), so auto = 1; the option stays for experiments and is covered by tests (bit-identical results)

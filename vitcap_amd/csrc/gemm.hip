@@ -18,7 +18,6 @@
 
 #include "common.h"
 #include "gemm_args.h"
-#include <string.h>
 
 
 #include <algorithm>
@@ -28,14 +27,12 @@
 
 namespace {
 
-// width (in 256-column tiles) of the column groups the 256x256 kernels walk; VITCAP_GEMM_GROUP_N overrides (experiments)
+// width (in 256-column tiles) of the column groups the 256x256 kernels walk
 int tile_group_n(int tiles_n) {
-  static const int env_gn = [] { const char* e = getenv("VITCAP_GEMM_GROUP_N"); return e ? atoi(e) : 0; }();
-  // measured at M = 36928 (tools/group_sweep.sh): N = 3072 214 -> 199 us with groups of 2..6 tiles (W = 4.7 MB does not fit
+  // measured at M = 36928 (column-group width swept 1..6): N = 3072 214 -> 199 us with groups of 2..6 tiles (W = 4.7 MB does not fit
   // one XCD's 4 MB L2 next to the A tiles; HBM fetch 169 -> 152 MiB per launch); N = 2304 (W = 3.5 MB fits) same time with
   // 7 % MORE fetch when grouped, so only wider outputs are grouped
-  int g = env_gn > 0 ? env_gn : (tiles_n > 9 ? 3 : tiles_n);
-  return g > tiles_n ? tiles_n : g;
+  return tiles_n > 9 ? 3 : tiles_n;
 }
 
 }  // namespace
@@ -275,165 +272,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
 
 
 // ------------------------------------------------------------------------------------------------
-// Large-M kernel: 256 x 128 x 64 tile, 8 waves (4 along M x 2 along N, 64x64 per wave), THREE LDS
-// stages (3 x 48 KiB): the loads of k-tile t+2 are issued while tile t is multiplied, and tile t is
-// awaited with a COUNTED `s_waitcnt vmcnt(6)` (this wave's 6 newer LDS-DMA pieces stay in flight)
-// followed by a raw s_barrier -- no vmcnt(0) drain in the main loop (cdna guide T3/T4).
-// ------------------------------------------------------------------------------------------------
-template <int ACT, int OUT_F32, bool HAS_RES>
-__global__ __launch_bounds__(512) void gemm_nt_big_kernel(GemmArgs p) {
-  constexpr int BM = 256, BN = 128, BK = 64, WM = 4, WN = 4;
-  constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2, BUF_BYTES = A_BYTES + W_BYTES;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = w >> 1, wn = w & 1;
-
-  const int nwg = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  const int srow = lane >> 3;
-  const int schunk = (lane & 7) ^ (srow & 7);
-  const bf16_t* aptr[4];
-  const bf16_t* wptr[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int r = m0 + w * 32 + i * 8 + srow;
-    r = r < p.M ? r : p.M - 1;
-    aptr[i] = p.A + (size_t)r * p.lda + schunk * 8;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int r = n0 + w * 16 + i * 8 + srow;
-    r = r < p.N ? r : p.N - 1;
-    wptr[i] = p.W + (size_t)r * p.ldw + schunk * 8;
-  }
-#define STAGE(buf_, k0_)                                                                     \
-  do {                                                                                       \
-    char* sb_ = smem + (buf_) * BUF_BYTES;                                                   \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                            \
-        glds16(aptr[i] + (k0_), sb_ + (w * 32 + i * 8) * 128);                               \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                            \
-        glds16(wptr[i] + (k0_), sb_ + A_BYTES + (w * 16 + i * 8) * 128);                     \
-  } while (0)
-
-  f32x4 acc[WM][WN];
-#pragma unroll
-  for (int i = 0; i < WM; ++i)
-#pragma unroll
-    for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int frow = lane & 15;
-  const int fk = lane >> 4;
-  const int nk = p.K / BK;
-
-  STAGE(0, 0);
-  if (nk > 1) STAGE(1, BK);
-
-  int buf = 0;
-  for (int t = 0; t < nk; ++t) {
-    if (t + 1 < nk)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (t + 2 < nk) {
-      const int nb = buf >= 1 ? buf - 1 : 2;   // (buf + 2) % 3
-      STAGE(nb, (t + 2) * BK);
-    }
-    const char* la = smem + buf * BUF_BYTES + (wm * 64 + frow) * 128;
-    const char* lw = smem + buf * BUF_BYTES + A_BYTES + (wn * 64 + frow) * 128;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int coff = ((ks * 4 + fk) ^ (frow & 7)) * 16;
-      bf16x8 af[WM], wf[WN];
-#pragma unroll
-      for (int i = 0; i < WM; ++i) af[i] = *(const bf16x8*)(la + i * 16 * 128 + coff);
-#pragma unroll
-      for (int j = 0; j < WN; ++j) wf[j] = *(const bf16x8*)(lw + j * 16 * 128 + coff);
-#pragma unroll
-      for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-    }
-    buf = buf == 2 ? 0 : buf + 1;
-  }
-#undef STAGE
-
-#pragma unroll
-  for (int i = 0; i < WM; ++i) {
-    const int m = m0 + wm * 64 + i * 16 + frow;
-    if (m >= p.M) continue;
-    int orow = m, rrow = m;
-    if (p.row_group > 0) {
-      const int g = m / p.row_group, in = m - g * p.row_group;
-      orow = g * p.out_group_rows + p.out_row_off + in;
-      rrow = p.res_periodic ? in : orow;
-    }
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fk * 4;
-      if (n >= p.N) continue;
-      f32x4 v = acc[i][j];
-      if (p.bias) v += *(const f32x4*)(p.bias + n);
-      if (ACT == VITCAP_ACT_GELU_ERF) {
-        v = gelu_erf4(v);
-      } else if (ACT == VITCAP_ACT_TANH) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = tanhf(v[e]);
-      }
-      if (HAS_RES) v += *(const f32x4*)(p.res + (size_t)rrow * p.ldr + n);
-      if (OUT_F32) {
-        *(f32x4*)((float*)p.C + (size_t)orow * p.ldc + n) = v;
-      } else {
-        uint2 o;
-        o.x = pack2bf(v[0], v[1]);
-        o.y = pack2bf(v[2], v[3]);
-        *(uint2*)((bf16_t*)p.C + (size_t)orow * p.ldc + n) = o;
-      }
-    }
-  }
-}
-
-template <int ACT, int OUT_F32, bool HAS_RES>
-int launch_big(const GemmArgs& a, hipStream_t s) {
-  constexpr int smem = 3 * (256 + 128) * 64 * 2;
-  auto kern = gemm_nt_big_kernel<ACT, OUT_F32, HAS_RES>;
-  VC_FUNC_SMEM(kern, smem);
-  GemmArgs p = a;
-  p.tiles_m = (a.M + 255) / 256;
-  p.tiles_n = (a.N + 127) / 128;
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(512), smem, s, p);
-  VC_LAUNCH_CHECK("gemm_nt_big");
-  return VITCAP_OK;
-}
-
-int dispatch_big(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
-  const bool res = a.res != nullptr;
-#define CASE(ACT_, OUT_)                                                  \
-  if (act == ACT_ && out_f32 == OUT_)                                     \
-    return res ? launch_big<ACT_, OUT_, true>(a, s) : launch_big<ACT_, OUT_, false>(a, s);
-  CASE(VITCAP_ACT_NONE, 0)
-  CASE(VITCAP_ACT_NONE, 1)
-  CASE(VITCAP_ACT_GELU_ERF, 0)
-  CASE(VITCAP_ACT_GELU_ERF, 1)
-#undef CASE
-  vitcap_set_error("gemm(big): unsupported act %d / out %d", act, out_f32);
-  return VITCAP_EINVAL;
-}
-
-
-
-// ------------------------------------------------------------------------------------------------
 // 256 x 256 x 64 kernel, 8 waves, two LDS buffers of 64 KiB, role-alternating schedule.
 //
 // Waves 0-3 (group A) and 4-7 (group B) sit pairwise on the four SIMDs.  Every k-tile is processed in four
@@ -475,8 +313,7 @@ __device__ __forceinline__ void lane_tile_transpose(unsigned (&r)[4][NREG]) {
 
 // acc[NI][4]: the wave's (16*NI) x 64 block (NI row tiles of 16, 4 column tiles of 16); row0/col0 = its origin in C
 template <int ACT, int OUT_F32, bool HAS_RES, int NI>
-__device__ __forceinline__ void epilogue_direct(f32x4 (&acc)[NI][4], const GemmArgs& p, int row0, int col0, int lane,
-                                                bool no_store) {
+__device__ __forceinline__ void epilogue_direct(f32x4 (&acc)[NI][4], const GemmArgs& p, int row0, int col0, int lane) {
   const int frow = lane & 15, fk = lane >> 4;
   f32x4 bias4[4];
 #pragma unroll
@@ -485,7 +322,7 @@ __device__ __forceinline__ void epilogue_direct(f32x4 (&acc)[NI][4], const GemmA
     bias4[j] = (p.bias && n < p.N) ? *(const f32x4*)(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int ncol = col0 + fk * 16;                       // first of this lane's 16 consecutive columns after the transpose
-  const bool col_ok = ncol < p.N && !no_store;           // N % 16 == 0 on this path
+  const bool col_ok = ncol < p.N;                        // N % 16 == 0 on this path
   f32x4 rres[2][4];
 #define ISSUE_RES_D(i_)                                                                                    \
   if (HAS_RES) {                                                                                           \
@@ -547,6 +384,7 @@ __device__ __forceinline__ void epilogue_direct(f32x4 (&acc)[NI][4], const GemmA
 // One (64*MT) x 256 output tile at (m0, n0): MT = 4 is the 256 x 256 tile; MT = 3 / 2 are the 192- / 128-row tiles a mixed
 // launch uses for the rows behind the last full round of 256-row tiles (launch_256).  Same k order per output element and the
 // same epilogue arithmetic whatever MT, so the results do not depend on the tile height.
+// PH: build flags of the kernel -- 4 = always set, 8 = training extras (EXTRAS), 512 = in-kernel LayerNorm (LN)
 template <int ACT, int OUT_F32, bool HAS_RES, int PH, int MT>
 __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, const int m0, const int n0, const int cidx = 0) {
   constexpr int BK = 64;
@@ -556,12 +394,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
   constexpr int NP = MT + 4;                                       // LDS-DMA pieces (8 rows x 128 B per lane group) per wave and k-tile
   constexpr bool EXTRAS = (PH & 8) != 0;   // training extras (pre-activation copy `zout`, gelu' factor `aux`) compiled in: the
                                            // inference instantiations do not carry their 32 prefetch registers (222 instead of 226 VGPRs)
-  constexpr int ABL = (PH >> 4) & 31;   // timing ablations (tools/gemm_bench.py only; results are wrong when != 0)
-#ifndef LN_LOAD_AUX
-#define LN_LOAD_AUX 0
-#endif
   constexpr bool LN = (PH & 512) != 0;  // LayerNorm of the finished rows by the last of the row block's column tiles (GemmArgs.ln_*)
-  constexpr bool NO_DMA = ABL & 1, NO_LDS = ABL & 2, NO_MFMA = ABL & 4, NO_STORE = ABL & 8, NO_EPI = ABL & 16;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -634,7 +467,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
   __builtin_amdgcn_s_barrier()
 #define COMPUTE(mh_, nh_)                                                                               \
   __builtin_amdgcn_s_setprio(1);                                                                        \
-  if (!NO_MFMA)                                                                                         \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                      \
     _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                   \
       _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                  \
@@ -644,7 +476,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
 
   // prologue: k-tile 0 into buffer 0, first two pieces of k-tile 1 into buffer 1
   STAGE_PIECES(0, NP, 0, 0);
-  if (nk > 1 && !NO_DMA) {
+  if (nk > 1) {
     STAGE_SLOT(0, 1, BK);
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
   } else {
@@ -655,23 +487,23 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
 
   for (int t = 0; t < nk; ++t) {
     const int buf = t & 1;
-    const bool more = !NO_DMA && t + 1 < nk;
-    const bool more2 = !NO_DMA && t + 2 < nk;
-    const bool rd = !NO_LDS || t == 0;
+    const bool more = t + 1 < nk;
+    const bool more2 = t + 2 < nk;
     // ---- phase 0: quadrant (m-half 0, n-half 0)
-    if (rd) { LOAD_A(buf, 0); LOAD_B(buf, 0); }
+    LOAD_A(buf, 0);
+    LOAD_B(buf, 0);
     if (more) { STAGE_SLOT(1, buf ^ 1, (t + 1) * BK); }
     END_LOAD();
     COMPUTE(0, 0);
     __builtin_amdgcn_s_barrier();
     // ---- phase 1: (m-half 0, n-half 1)
-    if (rd) { LOAD_B(buf, 1); }
+    LOAD_B(buf, 1);
     if (more) { STAGE_SLOT(2, buf ^ 1, (t + 1) * BK); }
     END_LOAD();
     COMPUTE(0, 1);
     __builtin_amdgcn_s_barrier();
     // ---- phase 2: (m-half 1, n-half 1)
-    if (rd) { LOAD_A(buf, 1); }
+    LOAD_A(buf, 1);
     if (more) { STAGE_SLOT(3, buf ^ 1, (t + 1) * BK); }
     END_LOAD();
     COMPUTE(1, 1);
@@ -710,9 +542,8 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
   const int ncol = n0 + wn * 64 + ec;
   f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
   if (p.bias && ncol < p.N) bias4 = *(const f32x4*)(p.bias + ncol);
-  if (NO_EPI) return;                 // ablation: no epilogue at all
   // residual rows are requested one chunk (2*MT iterations = 8*MT rows) ahead of their use
-  const bool col_ok = ncol < p.N && !(NO_STORE && m0 >= 0);   // ablation: LDS staging and arithmetic but no global stores
+  const bool col_ok = ncol < p.N;
   f32x4 rres[2][2 * MT];
 #define ROWS_OF(m_, orow_, rrow_)                                             \
   int orow_ = (m_), rrow_ = (m_);                                             \
@@ -732,11 +563,11 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
     }                                                                                                        \
   }
   // plain rows, no aux / pre-activation copy, bf16 output without residual or fp32 output: straight from registers
-  // measured (tools/gemm_res_bench.py, VITCAP_GEMM_DIRECT_EPILOGUE=0/1): +4-5 % for the GELU epilogue (fc1), neutral for
+  // measured against the LDS-staged epilogue below: +4-5 % for the GELU epilogue (fc1), neutral for
   // plain bf16 (qkv), SLOWER for the fp32 + residual outputs (proj 0.078 -> 0.106 ms) -- so it is used for GELU only
-  if (p.direct_epilogue && ACT == VITCAP_ACT_GELU_ERF && !OUT_F32 && !HAS_RES && !(EXTRAS && p.zout) && !(EXTRAS && p.aux) && p.row_group == 0 &&
+  if (ACT == VITCAP_ACT_GELU_ERF && !OUT_F32 && !HAS_RES && !(EXTRAS && p.zout) && !(EXTRAS && p.aux) && p.row_group == 0 &&
       (p.N & 15) == 0 && (p.ldc & 7) == 0) {
-    epilogue_direct<ACT, OUT_F32, HAS_RES, NI>(acc, p, m0 + wm * WR, n0 + wn * 64, lane, NO_STORE);
+    epilogue_direct<ACT, OUT_F32, HAS_RES, NI>(acc, p, m0 + wm * WR, n0 + wn * 64, lane);
     return;
   }
   // bf16 output, plain rows, no residual: 8 columns per lane, one 16-byte store (8 lanes = one 128-byte line of the output
@@ -748,7 +579,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
     if (p.row_group == 0 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!(EXTRAS && p.zout) || (p.ldz & 7) == 0) && (!(EXTRAS && p.aux) || (p.ldaux & 7) == 0)) {
       const int wr = lane >> 3, wc = (lane & 7) * 8;
       const int ncw = n0 + wn * 64 + wc;
-      const bool okc = ncw < p.N && !(NO_STORE && m0 >= 0);
+      const bool okc = ncw < p.N;
       f32x4 b_lo = f32x4{0.f, 0.f, 0.f, 0.f}, b_hi = b_lo;
       f32x4 cs_lo = f32x4{0.f, 0.f, 0.f, 0.f}, cs_hi = cs_lo;      // EXTRAS && p.colsum: this lane's 8 columns summed over its 4*MT rows
       if (p.bias && ncw < p.N) {
@@ -934,7 +765,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
       for (int j = 0; j < RB; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i)           // rows past the block's end: the descriptor's range check returns zeros for the last block only
-          v[j][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ln_rc, (unsigned)((r0 + j) * p.ldc + i * 256 + lane * 4) * 4u, 0, LN_LOAD_AUX));
+          v[j][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ln_rc, (unsigned)((r0 + j) * p.ldc + i * 256 + lane * 4) * 4u, 0, 0));
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
         const int row = m0 + r0 + j;
@@ -993,10 +824,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(VC_GEMM256_VGPR
 // to the 256-row tile (a shorter tile has the same W traffic and per-phase overheads for fewer flops: measured, tools/gemm_bench.py).
 struct TilePlan { int tm_big, mts, tm_small; };
 TilePlan plan_tiles(int M, int tiles_n, int K) {
-  static const int mix_env = [] { const char* e = getenv("VITCAP_GEMM_MIX"); return e ? atoi(e) : -1; }();   // 0 = off; 3 / 2 = force height
-  static const int c3_env = [] { const char* e = getenv("VITCAP_GEMM_MIX_C3"); return e ? atoi(e) : 0; }();  // tile costs in permille (tuning)
-  static const int c2_env = [] { const char* e = getenv("VITCAP_GEMM_MIX_C2"); return e ? atoi(e) : 0; }();
-  static const int big_env = [] { const char* e = getenv("VITCAP_GEMM_MIX_BIG"); return e ? atoi(e) : -1; }(); // force the number of 256-row m-tiles
   static const int n_cu = [] {
     int dev = 0;
     hipDeviceProp_t prop;
@@ -1006,7 +833,6 @@ TilePlan plan_tiles(int M, int tiles_n, int K) {
   }();
   const int tm_full = (M + 255) / 256;
   TilePlan best{tm_full, 0, 0};
-  if (mix_env == 0) return best;
   struct Key { int M, tn, K; };
   static std::mutex mu;
   static std::vector<std::pair<Key, TilePlan>> cache;
@@ -1016,16 +842,14 @@ TilePlan plan_tiles(int M, int tiles_n, int K) {
       if (e.first.M == M && e.first.tn == tiles_n && e.first.K == K) return e.second;
   }
   // relative tile costs: main loop ~ (64 MT + overhead) cycles per phase, epilogue ~ MT; K = 768 tiles are about half epilogue
-  const float c3 = c3_env > 0 ? c3_env * 1e-3f : 0.80f, c2 = c2_env > 0 ? c2_env * 1e-3f : 0.60f;
+  const float c3 = 0.80f, c2 = 0.60f;
   float best_t = ceilf((float)(tm_full * tiles_n) / n_cu);
   const float need = best_t * 0.97f;                         // a plan must win 3 % to replace the plain grid
   const int span = (int)(2.5f * n_cu / tiles_n) + 2;         // rows worth ~2.5 rounds can move to short tiles
   std::vector<float> heap;
   for (int mts = 3; mts >= 2; --mts) {
-    if (mix_env > 0 && mix_env != mts) continue;
     const float cs = mts == 3 ? c3 : c2;
     for (int tb = tm_full - 1; tb >= 0 && tb >= tm_full - span; --tb) {
-      if (big_env >= 0 && tb != big_env) continue;
       const int rows_left = M - tb * 256;
       const int ts = (rows_left + 64 * mts - 1) / (64 * mts);
       const int nb = tb * tiles_n, ns = ts * tiles_n;
@@ -1067,16 +891,14 @@ int launch_256(const GemmArgs& a, hipStream_t s, int mix = 0) {
   p.tiles_n = (a.N + 255) / 256;
   p.group_n = tile_group_n(p.tiles_n);
   TilePlan pl{(a.M + 255) / 256, 0, 0};
-  if constexpr (((PH >> 4) & 31) == 0) {
-    if (a.aux || a.zout || a.colsum) mix = 0;
-    if (mix < 0) pl = plan_tiles(a.M, p.tiles_n, a.K);
-    else if (mix > 0) pl = TilePlan{0, mix, (a.M + 64 * mix - 1) / (64 * mix)};
-  }
+  if (a.aux || a.zout || a.colsum) mix = 0;
+  if (mix < 0) pl = plan_tiles(a.M, p.tiles_n, a.K);
+  else if (mix > 0) pl = TilePlan{0, mix, (a.M + 64 * mix - 1) / (64 * mix)};
   p.tiles_m = pl.tm_big;
   p.tiles_m_small = pl.tm_small;
   p.n_big = pl.tm_big * p.tiles_n;
   const int nwg = p.n_big + pl.tm_small * p.tiles_n;
-  if constexpr (((PH >> 4) & 31) == 0 && (PH & 512) == 0) {
+  if constexpr ((PH & 512) == 0) {
     if (a.aux || a.zout || a.colsum) return launch_256_t<ACT, OUT_F32, HAS_RES, PH | 8, 0>(p, nwg, s);   // training extras: 256-row tiles only
     if (pl.mts == 3) return launch_256_t<ACT, OUT_F32, HAS_RES, PH, 3>(p, nwg, s);
     if (pl.mts == 2) return launch_256_t<ACT, OUT_F32, HAS_RES, PH, 2>(p, nwg, s);
@@ -1099,320 +921,6 @@ int dispatch_256(const GemmArgs& a, int act, int out_f32, hipStream_t s, int mix
   return VITCAP_EINVAL;
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// Persistent variant of the 256x256x64 role-alternating kernel: one workgroup per CU walks the tile list.
-// Before a tile's epilogue the first k-tile of the NEXT tile is already being fetched by LDS-DMA into the free
-// k-tile buffer (the epilogue stages through the other one, 8 KiB per wave, XOR-swizzled instead of padded),
-// the output stores are not waited for, and there is no workgroup relaunch between tiles: the prologue latency
-// and most of the store drain disappear behind useful work.
-// ------------------------------------------------------------------------------------------------
-template <int ACT, int OUT_F32, bool HAS_RES>
-__global__ __launch_bounds__(512) void gemm_nt_256p_kernel(GemmArgs p) {
-  constexpr int BM = 256, BN = 256, BK = 64;
-  constexpr int A_BYTES = BM * BK * 2, BUF_BYTES = 2 * A_BYTES;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = w >> 2;
-  const int wm = w >> 2, wn = w & 3;
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int srow = lane >> 3;
-  const int schunk = (lane & 7) ^ (srow & 7);
-  const int frow = lane & 15;
-  const int fk = lane >> 4;
-  const int coff0 = ((0 * 4 + fk) ^ (frow & 7)) * 16;
-  const int coff1 = ((1 * 4 + fk) ^ (frow & 7)) * 16;
-  const int a_base = (wm * 128 + frow) * 128;
-  const int b_base = A_BYTES + (wn * 64 + frow) * 128;
-  const int nk = p.K / BK;
-
-  const bf16_t* aptr[4];
-  const bf16_t* wptr[4];
-#define TILE_COORDS(tile_, m0_, n0_)                                                         \
-  do {                                                                                       \
-    int bid_ = (tile_);                                                                      \
-    const int q_ = nwg >> 3, r_ = nwg & 7, xcd_ = bid_ & 7;                                  \
-    bid_ = (xcd_ < r_ ? xcd_ * (q_ + 1) : r_ * (q_ + 1) + (xcd_ - r_) * q_) + (bid_ >> 3);   \
-    /* column groups of group_n tiles: the 32 tiles an XCD works on at once span few W tiles (which then live in  */ \
-    /* its L2 for the whole walk down M) and 32/group_n A tiles, each fetched once for group_n consumers          */ \
-    const int per_g_ = p.tiles_m * p.group_n;                                                \
-    const int g_ = bid_ / per_g_;                                                            \
-    const int rem_ = bid_ - g_ * per_g_;                                                     \
-    const int left_ = p.tiles_n - g_ * p.group_n;                                            \
-    const int gw_ = left_ < p.group_n ? left_ : p.group_n;                                   \
-    const int tm_ = rem_ / gw_;                                                              \
-    m0_ = tm_ * BM;                                                                          \
-    n0_ = (g_ * p.group_n + rem_ - tm_ * gw_) * BN;                                          \
-  } while (0)
-#define TILE_PTRS(m0_, n0_)                                                                  \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
-    int r_ = (m0_) + w * 32 + i * 8 + srow;                                                  \
-    r_ = r_ < p.M ? r_ : p.M - 1;                                                            \
-    aptr[i] = p.A + (size_t)r_ * p.lda + schunk * 8;                                         \
-    int c_ = (n0_) + w * 32 + i * 8 + srow;                                                  \
-    c_ = c_ < p.N ? c_ : p.N - 1;                                                            \
-    wptr[i] = p.W + (size_t)c_ * p.ldw + schunk * 8;                                         \
-  }
-#define STAGE_A(buf_, k0_)                                                                   \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                              \
-      glds16(aptr[i] + (k0_), smem + (buf_) * BUF_BYTES + (w * 32 + i * 8) * 128)
-#define STAGE_W(buf_, k0_)                                                                   \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                              \
-      glds16(wptr[i] + (k0_), smem + (buf_) * BUF_BYTES + A_BYTES + (w * 32 + i * 8) * 128)
-#define STAGE2(base_, row0_, p0_, buf_, k0_)                                                 \
-  _Pragma("unroll") for (int i = (p0_); i < (p0_) + 2; ++i)                                  \
-      glds16((base_)[i] + (k0_), smem + (buf_) * BUF_BYTES + (row0_) + (w * 32 + i * 8) * 128)
-
-  bf16x8 afr[4][2];
-  bf16x8 bfr[2][2][2];
-#define LOAD_A(buf_, mh_)                                                                        \
-  _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                             \
-    const char* ra_ = smem + (buf_) * BUF_BYTES + a_base + ((mh_) * 4 + mt) * 16 * 128;          \
-    afr[mt][0] = *(const bf16x8*)(ra_ + coff0);                                                  \
-    afr[mt][1] = *(const bf16x8*)(ra_ + coff1);                                                  \
-  }
-#define LOAD_B(buf_, nh_)                                                                        \
-  _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                             \
-    const char* rb_ = smem + (buf_) * BUF_BYTES + b_base + ((nh_) * 2 + nt) * 16 * 128;          \
-    bfr[nh_][nt][0] = *(const bf16x8*)(rb_ + coff0);                                             \
-    bfr[nh_][nt][1] = *(const bf16x8*)(rb_ + coff1);                                             \
-  }
-#define END_LOAD()                                          \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        \
-  __builtin_amdgcn_sched_barrier(0);                        \
-  __builtin_amdgcn_s_barrier()
-#define COMPUTE(mh_, nh_)                                                                               \
-  __builtin_amdgcn_s_setprio(1);                                                                        \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                      \
-    _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                    \
-      _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                  \
-        acc[(mh_) * 4 + mt][(nh_) * 2 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                  \
-            bfr[nh_][nt][ks], afr[mt][ks], acc[(mh_) * 4 + mt][(nh_) * 2 + nt], 0, 0, 0);               \
-  __builtin_amdgcn_s_setprio(0)
-
-  int pb = 0;                       // LDS buffer holding k-tile 0 of the current tile
-  int tile = blockIdx.x;
-  int m0, n0;
-  TILE_COORDS(tile, m0, n0);
-  TILE_PTRS(m0, n0);
-  STAGE_A(0, 0);
-  STAGE_W(0, 0);
-
-  for (; tile < nwg; tile += gridDim.x) {
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // every wave has left the previous epilogue (its staging patch lives in buffer pb^1) before anyone DMAs into it
-    __builtin_amdgcn_s_barrier();
-    if (nk > 1) {
-      STAGE2(aptr, 0, 0, pb ^ 1, BK);
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // k-tile 0 (and the previous tile's stores) done
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();
-
-    for (int t = 0; t < nk; ++t) {
-      const int buf = (pb + t) & 1;
-      const bool more = t + 1 < nk;
-      const bool more2 = t + 2 < nk;
-      LOAD_A(buf, 0);
-      LOAD_B(buf, 0);
-      if (more) { STAGE2(aptr, 0, 2, buf ^ 1, (t + 1) * BK); }
-      END_LOAD();
-      COMPUTE(0, 0);
-      __builtin_amdgcn_s_barrier();
-      LOAD_B(buf, 1);
-      if (more) { STAGE2(wptr, A_BYTES, 0, buf ^ 1, (t + 1) * BK); }
-      END_LOAD();
-      COMPUTE(0, 1);
-      __builtin_amdgcn_s_barrier();
-      LOAD_A(buf, 1);
-      if (more) { STAGE2(wptr, A_BYTES, 2, buf ^ 1, (t + 1) * BK); }
-      END_LOAD();
-      COMPUTE(1, 1);
-      __builtin_amdgcn_s_barrier();
-      if (more2) { STAGE2(aptr, 0, 0, buf, (t + 2) * BK); }
-      if (grp == 1) {
-        if (more2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      COMPUTE(1, 0);
-      if (grp == 0) {
-        if (more2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();
-
-    // ---- prefetch k-tile 0 of the next tile into the buffer the last k-tile did NOT use
-    const int ep_buf = (pb + nk - 1) & 1;      // last k-tile's buffer: free now, used for epilogue staging
-    const int cm0 = m0, cn0 = n0;
-    pb = ep_buf ^ 1;
-    // ---- epilogue: 4 passes of 32 rows through this wave's 8 KiB patch (XOR-swizzled 16-byte chunks).
-    // The residual rows of pass g+1 are requested before pass g is processed, so their HBM latency hides behind a
-    // whole pass instead of stalling every 4 rows (proj / fc2: the fp32 residual + fp32 output stream IS the cost).
-    // bf16 output without residual: a lane converts 8 columns and issues ONE 16-byte store (8 lanes = one 128-byte
-    // line of the row) -- the store tail is issue-bound, so half the store instructions is what counts.
-    char* ep = smem + ep_buf * BUF_BYTES + w * 8192;
-    constexpr bool WIDE = !OUT_F32 && !HAS_RES;
-    if constexpr (WIDE) {
-      const int er = lane >> 3, ec = lane & 7;            // row within a group of 8, 8-column piece
-      const int ncol = cn0 + wn * 64 + ec * 8;
-      const bool col_ok = ncol < p.N;                      // N % 8 == 0 on this path (checked by the dispatcher)
-      f32x4 bias_lo = f32x4{0.f, 0.f, 0.f, 0.f}, bias_hi = bias_lo;
-      if (p.bias && col_ok) {
-        bias_lo = *(const f32x4*)(p.bias + ncol);
-        bias_hi = *(const f32x4*)(p.bias + ncol + 4);
-      }
-      if (tile + (int)gridDim.x < nwg) {
-        TILE_COORDS(tile + (int)gridDim.x, m0, n0);
-        TILE_PTRS(m0, n0);
-        STAGE_A(pb, 0);
-        STAGE_W(pb, 0);
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int row = i * 16 + frow;
-            *(f32x4*)(ep + row * 256 + (((j * 4 + fk) ^ (row & 15)) * 16)) = acc[g * 2 + i][j];
-          }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int rl = it * 8 + er;
-          f32x4 v0 = *(const f32x4*)(ep + rl * 256 + (((ec * 2) ^ (rl & 15)) * 16));
-          f32x4 v1 = *(const f32x4*)(ep + rl * 256 + (((ec * 2 + 1) ^ (rl & 15)) * 16));
-          const int m = cm0 + wm * 128 + g * 32 + rl;
-          v0 += bias_lo;
-          v1 += bias_hi;
-          if (ACT == VITCAP_ACT_GELU_ERF) {
-            v0 = gelu_erf4(v0);
-            v1 = gelu_erf4(v1);
-          }
-          if (m < p.M && col_ok) {
-            uint4 o;
-            o.x = pack2bf(v0[0], v0[1]);
-            o.y = pack2bf(v0[2], v0[3]);
-            o.z = pack2bf(v1[0], v1[1]);
-            o.w = pack2bf(v1[2], v1[3]);
-            *(uint4*)((bf16_t*)p.C + (size_t)m * p.ldc + ncol) = o;
-          }
-        }
-      }
-    } else {
-    const int er = lane >> 4, ec = lane & 15;
-    const int ncol = cn0 + wn * 64 + ec * 4;
-    const bool col_ok = ncol < p.N;
-    f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (p.bias && col_ok) bias4 = *(const f32x4*)(p.bias + ncol);
-    f32x4 rres[2][8];
-#define ISSUE_RES(g_)                                                                                     \
-  if (HAS_RES) {                                                                                          \
-    _Pragma("unroll") for (int it = 0; it < 8; ++it) {                                                    \
-      const int m_ = cm0 + wm * 128 + (g_) * 32 + it * 4 + er;                                            \
-      rres[(g_) & 1][it] = (m_ < p.M && col_ok) ? *(const f32x4*)(p.res + (size_t)m_ * p.ldr + ncol)    \
-                                                : f32x4{0.f, 0.f, 0.f, 0.f};                              \
-    }                                                                                                     \
-  }
-    ISSUE_RES(0);                      // ahead of the next tile's DMA in the memory pipeline
-    if (tile + (int)gridDim.x < nwg) {
-      TILE_COORDS(tile + (int)gridDim.x, m0, n0);
-      TILE_PTRS(m0, n0);
-      STAGE_A(pb, 0);
-      STAGE_W(pb, 0);
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      if (g + 1 < 4) { ISSUE_RES(g + 1); }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int row = i * 16 + frow;
-          *(f32x4*)(ep + row * 256 + (((j * 4 + fk) ^ (row & 15)) * 16)) = acc[g * 2 + i][j];
-        }
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int rl = it * 4 + er;
-        f32x4 v = *(const f32x4*)(ep + rl * 256 + ((ec ^ (rl & 15)) * 16));
-        const int m = cm0 + wm * 128 + g * 32 + rl;
-        v += bias4;
-        if (ACT == VITCAP_ACT_GELU_ERF) {
-          v = gelu_erf4(v);
-        }
-        if (HAS_RES) v += rres[g & 1][it];
-        if (m < p.M && col_ok) {
-          if (OUT_F32) {
-            *(f32x4*)((float*)p.C + (size_t)m * p.ldc + ncol) = v;
-          } else {
-            uint2 o;
-            o.x = pack2bf(v[0], v[1]);
-            o.y = pack2bf(v[2], v[3]);
-            *(uint2*)((bf16_t*)p.C + (size_t)m * p.ldc + ncol) = o;
-          }
-        }
-      }
-    }
-#undef ISSUE_RES
-    }
-  }
-#undef TILE_COORDS
-#undef TILE_PTRS
-#undef STAGE_A
-#undef STAGE_W
-#undef STAGE2
-#undef LOAD_A
-#undef LOAD_B
-#undef END_LOAD
-#undef COMPUTE
-}
-
-template <int ACT, int OUT_F32, bool HAS_RES>
-int launch_256p(const GemmArgs& a, hipStream_t s) {
-  constexpr int smem = 2 * 2 * 256 * 64 * 2;
-  auto kern = gemm_nt_256p_kernel<ACT, OUT_F32, HAS_RES>;
-  VC_FUNC_SMEM(kern, smem);
-  static const int n_cu = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      return prop.multiProcessorCount;
-    return 256;
-  }();
-  GemmArgs p = a;
-  p.tiles_m = (a.M + 255) / 256;
-  p.tiles_n = (a.N + 255) / 256;
-  const int nwg = p.tiles_m * p.tiles_n;
-  p.group_n = tile_group_n(p.tiles_n);
-  VC_LAUNCH_GEMM(kern, dim3(nwg < n_cu ? nwg : n_cu), dim3(512), smem, s, p);
-  VC_LAUNCH_CHECK("gemm_nt_256p");
-  return VITCAP_OK;
-}
-
-int dispatch_256p(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
-  const bool res = a.res != nullptr;
-#define CASE(ACT_, OUT_)                                                  \
-  if (act == ACT_ && out_f32 == OUT_)                                     \
-    return res ? launch_256p<ACT_, OUT_, true>(a, s) : launch_256p<ACT_, OUT_, false>(a, s);
-  CASE(VITCAP_ACT_NONE, 0)
-  CASE(VITCAP_ACT_NONE, 1)
-  CASE(VITCAP_ACT_GELU_ERF, 0)
-  CASE(VITCAP_ACT_GELU_ERF, 1)
-#undef CASE
-  vitcap_set_error("gemm(256p): unsupported act %d / out %d", act, out_f32);
-  return VITCAP_EINVAL;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Skinny kernel for the decode-step GEMMs (M = 2B or B rows: 64..256).  These are weight-streaming,
@@ -1646,39 +1154,33 @@ int dispatch(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
 
 }  // namespace
 
-// which kernel family runs a large GEMM under tile_hint `hint` (0 = auto, 5 = one tile per workgroup): -1 = the 8-wave kernel of this
-// file, 0..2 = a form of the 4-wave kernel (gemm4w.hip); see the measurements at the call site in vitcap_gemm_ex
-static int large_gemm_form(int M, int N, int hint, bool f32_or_res = true) {
-  static const int env_set = getenv("VITCAP_GEMM_4W") != nullptr;
-  static const int env_tiles = [] { const char* e = getenv("VITCAP_GEMM_4W"); return e ? atoi(e) : -1; }();
-  static const int env_auto = [] { const char* e = getenv("VITCAP_GEMM_4W"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : (e ? atoi(e) : -1); }();
-  const long long tiles256 = (long long)((M + 255) / 256) * ((N + 255) / 256);
+// Which kernel family runs a large GEMM under tile_hint `hint` (0 = auto, 5 = one tile per workgroup): -1 = the 8-wave kernel of this
+// file, 1 / 2 = the one-tile / persistent form of the 4-wave kernel (gemm4w.hip).  Measured end to end (docs/LAB_r01_r04.md 4.3):
+//   auto (one stream): the persistent 4-wave form, +1.8 % images/s at B = 64 and B = 512 against the 8-wave kernel + planned tile mix;
+//   tile_hint 5 (the 2-slot pipeline: another stream's small kernels must slip in between tiles): the 8-wave kernel -- a persistent
+//   grid owns every CU for the whole GEMM, and a 512-register workgroup leaves no room for a co-resident decode wave (B = 64: 3802
+//   vs 3517 img/s) -- except the bf16-output GEMMs without residual (qkv, fc1) below 64k rows, which gain on the 4-wave one-tile
+//   form (qkv alone 3 900, fc1 alone 3 907 against 3 856 / 3 866 img/s all 8-wave; proj / fc2 lose: 3 748;
+//   profiles/r05_pipeline_gemm_forms.txt).  From 64k rows per launch on that mix is a tie or slightly behind.
+static int large_gemm_form(int M, int hint, bool plain_bf16) {
   if (M < 2048) return -1;
-  // VITCAP_GEMM_4W_TILES_N=<N>[,<form>] (experiments): under tile_hint 5 the 4-wave kernel (form 1 unless given) for outputs N wide only
-  static const int only_n = [] { const char* e = getenv("VITCAP_GEMM_4W_TILES_N"); return e ? atoi(e) : 0; }();
-  static const int only_form = [] { const char* e = getenv("VITCAP_GEMM_4W_TILES_N"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 1; }();
-  if (hint == 5 && only_n > 0 && tiles256 < 8 * 256) return N == only_n ? only_form : -1;
-  // tile_hint 5 (another stream's kernels must slip in between tiles): the 8-wave kernel at every size.  Round 4 switched to the
-  // persistent 4-wave form from 8 rounds of tiles on (B = 512 greedy +1.3 %); with two encoder parts in flight (round 5 default) that
-  // is a tie there (4 096 / 4 122 vs 4 109 / 4 116 img/s) and it cost beam 5 x 256 -3 % (3 575 vs 3 692 img/s: the persistent grids lock
-  // the 1 280-sequence decode chain out) -- profiles/r05_split_beam_ab.txt
-  // What DOES pay inside the pipeline (round 5, 2 encoder parts, same box, interleaved; profiles/r05_pipeline_gemm_forms.txt): the 4-wave
-  // kernel in its one-tile-per-workgroup form for the bf16-output GEMMs only -- qkv alone 3 900, fc1 alone 3 907 against 3 856 / 3 866
-  // img/s all 8-wave -- while the fp32 + residual GEMMs (proj / fc2: 3 748) and the LDS-epilogue form (3 580 / 3 599) lose.
-  (void)tiles256;
-  static const int env_mix = [] { const char* e = getenv("VITCAP_GEMM_4W_MIX"); return e ? atoi(e) : 1; }();
-  // (from 64 k rows per launch on -- B = 512, beam 5 x 256 -- the mix is a tie or slightly behind: 8-wave there)
-  if (hint == 5) return env_set ? env_tiles : ((env_mix && !f32_or_res && M < 65536) ? 1 : -1);
-  if (hint == 0) return env_set ? env_auto : 2;
+  if (hint == 0) return 2;
+  if (hint == 5) return plain_bf16 && M < 65536 ? 1 : -1;
   return -1;
+}
+
+// the tile_hint values vitcap_gemm_ex knows (include/vitcap_hip.h)
+static bool known_tile_hint(int h) {
+  return h == 0 || h == 1 || h == 2 || h == 4 || h == 5 || (h >= 13 && h <= 15) || (h >= 20 && h <= 24) || (h >= 30 && h <= 33) ||
+         (h >= 40 && h <= 42);
 }
 
 extern "C" int vitcap_gemm_large_form(int M, int N, int K, int tile_hint) {
   // tile_hint | 0x100: the query is about a bf16-output GEMM without residual (under tile_hint 5 those run the 4-wave one-tile form)
   const bool plain_bf16 = (tile_hint & 0x100) != 0;
   tile_hint &= 0xff;
-  int form = large_gemm_form(M, N, tile_hint, !plain_bf16);
-  if (form < 0 || form > 2) return -1;
+  int form = large_gemm_form(M, tile_hint, plain_bf16);
+  if (form < 0) return -1;
   if (K < 128) return -1;                                   // vc_4w_supports
   // launch_4w's downgrade rules for plain rows (what the engine's large GEMMs use): the persistent pipeline needs three k-tiles and
   // whole 256-column tiles, the register epilogue 16-byte bf16 stores
@@ -1691,11 +1193,6 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
                               const vitcap_gemm_desc* d, const void* aux_bf16, int ldaux, void* zout_bf16, int ldz,
                               void* stream);
 
-// Persistent vs one-tile-per-workgroup form of the 256x256 GEMM is a PER-CALL choice (vitcap_gemm_desc.tile_hint 12 / 5;
-// 0 = auto = persistent where it wins).  Alone on the GPU the persistent form wins (+2..11 %); when another stream's small
-// kernels should slip in between (the batch pipeline of ImageCaptioning.generate_async) the non-persistent form wins,
-// because a persistent grid owns every CU for the whole GEMM (3277 vs 3133 img/s at B=64) -- the engine asks for it through
-// vitcap_gen_opts.gemm_mode.  There is no process-wide switch.
 extern "C" int vitcap_gemm_tile_plan(int M, int N, int K, int* plan3) {
   VC_REQUIRE(M > 0 && N > 0 && K > 0 && plan3, "gemm_tile_plan: bad arguments");
   const TilePlan pl = plan_tiles(M, (N + 255) / 256, K);
@@ -1742,18 +1239,11 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
   a.rev = vc_tls_walk_rev ? 1 : 0;
   a.rowstat = (float*)d->rowstat;
   a.ln_g = a.ln_b = nullptr; a.ln_eps = 0.f; a.ln_out = nullptr; a.ln_out_f = nullptr; a.ln_cnt = nullptr;
-  {
-    static const int direct = [] { const char* e = getenv("VITCAP_GEMM_DIRECT_EPILOGUE"); return e ? atoi(e) : 1; }();
-    a.direct_epilogue = direct;
-  }
   VC_REQUIRE(!(aux_bf16 && d->act != VITCAP_ACT_NONE), "gemm: aux (gelu') epilogue needs act == none");
   VC_REQUIRE(!zout_bf16 || d->act == VITCAP_ACT_GELU_ERF, "gemm: zout stores the GELU's derivative and needs act == gelu_erf");
-  VC_REQUIRE(!(aux_bf16 || zout_bf16) || (d->tile_hint != 3 && d->tile_hint != 12 && !(d->tile_hint >= 7 && d->tile_hint <= 17 && d->tile_hint != 13 && d->tile_hint != 14 && d->tile_hint != 15)),
-             "gemm: tile_hint %d selects a kernel without the training extras (aux / zout)", d->tile_hint);
+  VC_REQUIRE(known_tile_hint(d->tile_hint), "gemm: unknown tile_hint %d", d->tile_hint);
   hipStream_t s = (hipStream_t)stream;
-  // tile_hint: 0 auto, 1 = 64x64, 2 = 128x128, 3 = 256x128 (3-stage), 4 = skinny (register-fed, optional split-K),
-  //            5 = 256x256 role-alternating (the auto choice for M >= 2048)
-  const int hint = d->tile_hint;
+  const int hint = d->tile_hint;       // the values are listed at vitcap_gemm_desc.tile_hint (include/vitcap_hip.h)
   const int split_k = d->split_k > 1 ? d->split_k : 1;
   const bool plain_rows = d->row_group == 0;
   if (d->ln_out_bf16 || d->ln_out_f32) {
@@ -1763,15 +1253,13 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
     VC_REQUIRE(d->N == 768 && d->ldc == 768 && d->out_dtype == VITCAP_OUT_F32 && d->act == VITCAP_ACT_NONE && plain_rows && split_k == 1 &&
                    !aux_bf16 && !zout_bf16 && !d->rowstat && !d->colsum,
                "gemm(ln): needs N == ldc == 768, fp32 output, no activation / row remap / split-K / training extras");
-    // in-kernel only on request (ln_counters given) and under the 8-wave one-tile-per-workgroup form.  MEASURED A LOSS (docs/LAB_r01_r04.md
-    // 4.3: a row block's last arriver pulls its 786 KB back at ~20 GB/s, 40 us per block on one CU, against 31 us for the LayerNorm
-    // kernel over ALL rows on the whole chip): the engine does not ask for it unless VITCAP_GEMM_LN_FUSE=1
-    const bool fused = d->ln_counters && d->M >= 2048 && hint == 5 && large_gemm_form(d->M, d->N, hint) < 0;
+    // in-kernel only on request (ln_counters given) and under tile_hint 5 (an fp32 output runs the 8-wave kernel there).  MEASURED A LOSS
+    // (docs/LAB_r01_r04.md 4.3: a row block's last arriver pulls its 786 KB back at ~20 GB/s, 40 us per block on one CU, against 31 us
+    // for the LayerNorm kernel over ALL rows on the whole chip): the engine does not ask for it
+    const bool fused = d->ln_counters && d->M >= 2048 && hint == 5;
     if (fused) {
       a.ln_g = d->ln_gamma; a.ln_b = d->ln_beta; a.ln_eps = d->ln_eps;
       a.ln_out = (bf16_t*)d->ln_out_bf16; a.ln_out_f = d->ln_out_f32; a.ln_cnt = d->ln_counters;
-      static const int dbg = [] { const char* e = getenv("VITCAP_GEMM_LN_DEBUG"); return e ? atoi(e) : 0; }();   // 1: no LayerNorm pass (timing; wrong results)
-      if (dbg == 1) { a.ln_out = nullptr; a.ln_out_f = nullptr; }
       return residual ? launch_256<VITCAP_ACT_NONE, 1, true, 4 | 512>(a, s, 0) : launch_256<VITCAP_ACT_NONE, 1, false, 4 | 512>(a, s, 0);
     }
     vitcap_gemm_desc d2 = *d;
@@ -1796,9 +1284,9 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
     VC_REQUIRE(d->out_dtype == VITCAP_OUT_BF16 && !residual && plain_rows && split_k == 1 && d->M >= 2048 && d->N % 8 == 0 && d->ldc % 8 == 0 &&
                    (!aux_bf16 || ldaux % 8 == 0) && (!zout_bf16 || ldz % 8 == 0) && d->act != VITCAP_ACT_TANH,
                "gemm(colsum): needs bf16 output, no residual / row remap / split-K, M >= 2048, N, ldc (ldaux, ldz) multiples of 8");
-    // the persistent 4-wave kernel's register epilogue carries the column sums too (round 5): on request (tile_hint 42), or where the
-    // automatic choice allows it (vc_4w_extras_auto: off by default, slower inside the training step)
-    if ((hint == 42 || (hint == 0 && vc_4w_extras_auto(a) && large_gemm_form(d->M, d->N, hint, false) == 2)) && vc_4w_supports(a, d->act))
+    // the persistent 4-wave kernel's register epilogue carries the column sums too (round 5), on request only (tile_hint 42): inside
+    // the training step it is slower than the 8-wave kernel (profiles/r05_train_extras_ab.txt: 52.2 against 52.5 / 53.1 ms per step)
+    if (hint == 42 && vc_4w_supports(a, d->act))
       return vc_dispatch_4w(a, d->act, d->out_dtype, s, 2);
     return dispatch_256<4>(a, d->act, d->out_dtype, s, 0);
   }
@@ -1865,50 +1353,19 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
   }
   if (hint == 2 || (hint == 0 && (d->M < 2048 || d->act == VITCAP_ACT_TANH)))
     return dispatch<4, 4>(a, d->act, d->out_dtype, s);
-  if (hint == 3) return dispatch_big(a, d->act, d->out_dtype, s);
-  // the persistent kernel's bf16 epilogue stores 8 columns (16 bytes) per lane
-  const bool wide_ok = d->out_dtype == VITCAP_OUT_F32 || residual || (d->N % 8 == 0 && d->ldc % 8 == 0 && ((uintptr_t)C & 15) == 0);
-  if (hint == 12 && wide_ok) return dispatch_256p(a, d->act, d->out_dtype, s);
-  {
-    // The 4-wave kernel (gemm4w.hip) behind the two production hints, measured end to end (docs/LAB_r01_r04.md section 4.3):
-    //   auto (one stream): its persistent form, +1.8 % images/s at B = 64 and B = 512 against the 8-wave kernel + planned tile mix;
-    //   tile_hint 5 (the 2-slot pipeline: another stream's small kernels must slip in between tiles): the 8-wave kernel stays
-    //   (B = 64: 3802 vs 3703 img/s one-tile 4-wave, 3517 persistent -- a persistent grid owns every CU for the whole GEMM, and a
-    //   512-register workgroup leaves no room for a co-resident decode wave), at every size since round 5 (large_gemm_form).
-    // VITCAP_GEMM_4W = "<form for tile_hint 5>,<form for auto>" overrides (-1 = 8-wave kernel, 0..2 = form; experiments).
-    const int form = large_gemm_form(d->M, d->N, hint, d->out_dtype == VITCAP_OUT_F32 || residual != nullptr);
-    // training extras (aux / zout / colsum) ride in the persistent form's register epilogue only (round 5), and only where
-    // vc_4w_extras_auto says so
-    const bool extras = aux_bf16 || zout_bf16 || d->colsum;
-    if (form >= 0 && form <= 2 && d->M >= 2048 && (!extras || (form == 2 && d->out_dtype == VITCAP_OUT_BF16 && vc_4w_extras_auto(a))) &&
-        vc_4w_supports(a, d->act))
-      return vc_dispatch_4w(a, d->act, d->out_dtype, s, form);
-  }
-  if (hint >= 40 && hint <= 42) {
+  if (hint >= 40 && hint <= 42) {      // 4 waves x 128x128, one wave per SIMD (gemm4w.hip): 40 LDS epilogue, 41 register epilogue, 42 persistent
     VC_REQUIRE(!(aux_bf16 || zout_bf16 || d->colsum) || (hint == 42 && d->out_dtype == VITCAP_OUT_BF16),
                "gemm(4-wave): aux / zout / colsum need the persistent form (tile_hint 42) and a bf16 output");
     return vc_dispatch_4w(a, d->act, d->out_dtype, s, hint - 40);
-  }   // 4 waves x 128x128, one wave per SIMD (gemm4w.hip): 40 LDS epilogue, 41 register epilogue, 42 persistent
+  }
   if (hint == 30) return dispatch_256<4>(a, d->act, d->out_dtype, s, 3);    // every tile 192 x 256 (tile-cost measurement)
   if (hint == 31) return dispatch_256<4>(a, d->act, d->out_dtype, s, 2);    // every tile 128 x 256
-  if (hint == 5 || hint == 32) return dispatch_256<4>(a, d->act, d->out_dtype, s, 0);    // 256 x 256 tiles only (no short tail tiles)
-  if (hint == 33) return dispatch_256<4>(a, d->act, d->out_dtype, s, -1);   // 256-row tiles + the planned short tiles (what auto picks)
-  if (hint == 7) return launch_256<0, 0, false, 4 + 16 * 1>(a, s);   // ablation: no DMA in the loop
-  if (hint == 8) return launch_256<0, 0, false, 4 + 16 * 2>(a, s);   // ablation: no ds_read in the loop
-  if (hint == 9) return launch_256<0, 0, false, 4 + 16 * 4>(a, s);   // ablation: no MFMA
-  if (hint == 10) return launch_256<0, 0, false, 4 + 16 * 3>(a, s);  // ablation: MFMA + barriers only
-  if (hint == 11) return launch_256<0, 0, false, 4 + 16 * 6>(a, s);  // ablation: DMA + barriers only
-  if (hint == 16) return launch_256<0, 0, false, 4 + 16 * 8>(a, s);  // ablation: no global stores in the epilogue
-  if (hint == 17) return launch_256<0, 0, false, 4 + 16 * 16>(a, s); // ablation: no epilogue
-  // measured (tools/gemm_bench.py 5,12): the persistent variant wins without a residual operand (qkv +11 %, fc1 +6 %);
-  // with one, its residual rows are requested a pass ahead and before the next tile's DMA.
-  static const int env_persistent = [] { const char* e = getenv("VITCAP_GEMM_PERSISTENT"); return e ? atoi(e) : -1; }();
-  // auto = one tile per workgroup: since the direct (LDS-free) epilogue and the column-group tile order the persistent form no
-  // longer wins (tools/gemm_bench.py 0,5 at M = 36928 / 295424: qkv 148 / 1072 us persistent vs 145 / 1041, fc1 201 / 1645 vs
-  // 192 / 1537, fc2 and proj equal; end to end +1.0 % at B = 64, +2.4 % at B = 512).  tile_hint 12 still selects it.
-  const int use_persistent = env_persistent >= 0 ? env_persistent : 0;
-  // with a residual: long-K shapes (fc2) gain from the persistent form, short-K ones (proj) do not (gemm_res_bench.py)
-  if (hint == 0 && use_persistent && wide_ok && !aux_bf16 && !zout_bf16 && d->row_group == 0 && (!residual || d->K > 1024))
-    return dispatch_256p(a, d->act, d->out_dtype, s);
-  return dispatch_256<4>(a, d->act, d->out_dtype, s, -1);      // 256 x 256 tiles, short tiles in the last round where the plan wins
+  if (hint == 32) return dispatch_256<4>(a, d->act, d->out_dtype, s, 0);    // 256 x 256 tiles only (no short tail tiles)
+  if (hint == 33) return dispatch_256<4>(a, d->act, d->out_dtype, s, -1);   // 256-row tiles + the planned short tiles
+  // tile_hint 0 (M >= 2048) or 5: the 4-wave kernel where large_gemm_form says so and the launch carries none of the training extras
+  // (aux / zout / colsum: the 8-wave kernel's EXTRAS build unless tile_hint 42 asks otherwise), the 8-wave 256x256 kernel otherwise
+  const int form = large_gemm_form(d->M, hint, !(d->out_dtype == VITCAP_OUT_F32 || residual));
+  if (form >= 0 && !(aux_bf16 || zout_bf16 || d->colsum) && vc_4w_supports(a, d->act)) return vc_dispatch_4w(a, d->act, d->out_dtype, s, form);
+  // hint 5: 256 x 256 tiles only; auto: short tiles in the last round where the plan wins
+  return dispatch_256<4>(a, d->act, d->out_dtype, s, hint == 5 ? 0 : -1);
 }

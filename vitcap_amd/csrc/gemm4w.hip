@@ -43,17 +43,10 @@ __device__ __forceinline__ void mfma_zero(f32x4& c, const bf16x8& w, const bf16x
 }
 template <int OFF>
 __device__ __forceinline__ void ds_read16(bf16x8& d, uint32_t addr) {
-#if defined(VC_LOOP_ABL) && (VC_LOOP_ABL & 2)     // probe ablation: no fragment reads in the loop (wrong results)
-  asm volatile("" : "+v"(d));
-  return;
-#endif
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
 }
 // one LDS-DMA piece: 64 lanes x 16 B -> 1 KiB at the wave-uniform LDS byte address `lds`; global address = rsrc base + voff + soff
 __device__ __forceinline__ void dma16(uint32_t lds, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
-#if defined(VC_LOOP_ABL) && (VC_LOOP_ABL & 1)     // probe ablation: no LDS-DMA (wrong results)
-  if (soff != 0xffffffffu) return;
-#endif
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 
@@ -62,21 +55,6 @@ __device__ __forceinline__ void dma16(uint32_t lds, uint32_t voff, const i32x4& 
 __device__ __forceinline__ void pf64(uint32_t lds, uint32_t voff, const i32x4& rsrc, uint32_t soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
-#ifndef VC_4W_PF_AHEAD
-#define VC_4W_PF_AHEAD 2        // k-tiles between the slice a DMA requests and the slice prefetched next to it
-#endif
-
-// probe builds only (tools/probes/g4w_probe.hip defines VC_4W_STAMP): wave 0 of every workgroup records the shader clock at four
-// points into p.rowstat (reused as a uint64 buffer): start, main loop entry, main loop exit, end
-#ifdef VC_4W_STAMP
-#define STAMP(i_)                                                                                        \
-  if (w == 0 && lane == 0 && p.rowstat) ((unsigned long long*)p.rowstat)[blockIdx.x * 4 + (i_)] = __builtin_readcyclecounter()
-#define STAMP_AT(slot_, i_)                                                                              \
-  if (w == 0 && lane == 0 && p.rowstat) ((unsigned long long*)p.rowstat)[(slot_) * 4 + (i_)] = __builtin_readcyclecounter()
-#else
-#define STAMP(i_)
-#define STAMP_AT(slot_, i_)
-#endif
 
 struct Frags {
   bf16x8 a[2][8];   // [k-half][m-tile]
@@ -98,12 +76,6 @@ struct Src {
   i32x4 ra, rw;
 };
 __device__ __forceinline__ Src make_src(const GemmArgs& p, int m0, int n0) {
-#ifdef VC_4W_A_RESIDENT      // probe (wrong results): every tile reads one of 8 A panels (3 MB: L2 / Infinity-Cache resident) -- same stream, no HBM
-  m0 = (m0 >> 8 & 7) << 8;
-#endif
-#ifdef VC_4W_W_RESIDENT      // probe (wrong results): every tile reads one of 2 W panels
-  n0 = (n0 >> 8 & 1) << 8;
-#endif
   const bf16_t* abase = p.A + (size_t)m0 * p.lda;
   const bf16_t* wbase = p.W + (size_t)n0 * p.ldw;
   const long long arem = ((long long)(p.M - m0 - 1) * p.lda + p.K) * 2, wrem = ((long long)(p.N - n0 - 1) * p.ldw + p.K) * 2;
@@ -121,10 +93,6 @@ __device__ __forceinline__ Loop make_loop(const GemmArgs& p, uint32_t smem_base,
   const int srow = lane >> 3, schunk = (lane & 7) ^ srow;
   L.voff_a = (uint32_t)(srow * p.lda * 2 + schunk * 16);
   L.voff_w = (uint32_t)(srow * p.ldw * 2 + schunk * 16);
-#ifdef VC_4W_DMA64
-  L.voff_a = (uint32_t)((lane >> 2) * p.lda * 2 + (lane & 3) * 16);
-  L.voff_w = (uint32_t)((lane >> 2) * p.ldw * 2 + (lane & 3) * 16);
-#endif
   const int a_row0 = w * (8 * MI), w_row0 = w * 64;
   L.soff_a = (uint32_t)(a_row0 * p.lda * 2);
   L.soff_w = (uint32_t)(w_row0 * p.ldw * 2);
@@ -146,11 +114,6 @@ __device__ __forceinline__ Loop make_loop(const GemmArgs& p, uint32_t smem_base,
 template <int MI, int Q>
 __device__ __forceinline__ void dma_piece(const Loop& L, const Src& src, uint32_t bufoff, uint32_t kb) {
   // piece Q of a k-tile: Q < MI -> 8 rows of A, else 8 rows of W
-#ifdef VC_4W_DMA64     // probe (wrong results): every piece as 16 rows x 64 B (half lines) instead of 8 rows x 128 B -- same pieces, same bytes
-  if constexpr (Q < MI) dma16(L.lds_a + bufoff + Q * 1024, L.voff_a, src.ra, L.soff_a + (Q / 2) * 2 * L.pstep_a + (Q & 1) * 64 + kb);
-  else dma16(L.lds_w + bufoff + (Q - MI) * 1024, L.voff_w, src.rw, L.soff_w + ((Q - MI) / 2) * 2 * L.pstep_w + (Q & 1) * 64 + kb);
-  return;
-#endif
   if constexpr (Q < MI) dma16(L.lds_a + bufoff + Q * 1024, L.voff_a, src.ra, L.soff_a + Q * L.pstep_a + kb);
   else dma16(L.lds_w + bufoff + (Q - MI) * 1024, L.voff_w, src.rw, L.soff_w + (Q - MI) * L.pstep_w + kb);
 }
@@ -185,11 +148,7 @@ __device__ __forceinline__ void half_step(f32x4 (&acc)[MI][8], Frags& f, const L
   if constexpr (FIRST) mfma_zero(acc[S / 8][S % 8], f.w[H][S % 8], f.a[H][S / 8]);
   else mfma_acc(acc[S / 8][S % 8], f.w[H][S % 8], f.a[H][S / 8]);
   if constexpr (MODE == 1 || MODE == 4) {
-#ifdef VC_4W_DMA_DENSE          // probe: the tile's pieces behind the first MFMAs of the half (one per VC_4W_DMA_DENSE MFMAs) instead of spread over it
-    if constexpr (S % VC_4W_DMA_DENSE == 0 && S / VC_4W_DMA_DENSE < NOPS) dma_piece<MI, S / VC_4W_DMA_DENSE>(L, src, bufoff, kb);
-#else
     if constexpr (S % STRIDE == 0 && S / STRIDE < NOPS) dma_piece<MI, S / STRIDE>(L, src, bufoff, kb);
-#endif
   }
   if constexpr (MODE != 3 && MODE != 4) {
     constexpr int PH = STRIDE > 1 ? 1 : 0;
@@ -202,53 +161,6 @@ template <int MI, int MODE, bool FIRST, int... S>
 __device__ __forceinline__ void half_steps(f32x4 (&acc)[MI][8], Frags& f, const Loop& L, const Src& src, uint32_t rd_a, uint32_t rd_w, uint32_t bufoff,
                                            uint32_t kb, std::integer_sequence<int, S...>) {
   (half_step<MI, MODE, FIRST, S>(acc, f, L, src, rd_a, rd_w, bufoff, kb), ...);
-}
-
-// ---- schedule E ("early release", round 5).  With ONE rendezvous per k-tile the buffer of tile t is released at the tile's middle and
-// tile t+2's pieces, requested behind k-half 1's MFMAs, must have landed one k-tile later: a lead of 1.25-2 k-halves (1.3-2.0k cycles),
-// enough for operands that sit in the L2 / Infinity Cache (M = 36 928: the loop runs at 25.4k cycles per 12 k-tiles, the MFMA floor is
-// 24.6k), NOT for an A panel that streams from HBM under load (M = 295 424: 35.9k, profiles/r04_g4w_probe.txt).  Here the k-half-1
-// fragments of tile t are read behind the FIRST half of k-half 0's MFMAs, a first rendezvous (X) releases the buffer there, and the
-// pieces of tile t+2 follow behind the second half of k-half 0: requested half a k-tile earlier, still awaited at the mid-tile
-// rendezvous (Y) of tile t+1 with a COUNTED wait (the pieces requested in this tile stay in flight across it): lead 2.0-2.5 k-halves.
-// Same MFMA order, same operands: bit-identical results.
-constexpr int slot_of(int S, int N, int Q) {       // index r in [0, N) whose position (r * Q) / N is step S (Q >= N), else -1
-  const int r = (S * N + Q - 1) / Q;
-  return (S >= 0 && r < N && (r * Q) / N == S) ? r : -1;
-}
-//   H0: k-half 0 of tile t: reads of the tile's k-half-1 fragments in steps [0, QA), rendezvous X after step QA - 1 (DMA only), pieces
-//       of tile t+2 in steps [QA, STEPS)
-template <int MI, bool DMA, bool FIRST, int S>
-__device__ __forceinline__ void half0_step_e(f32x4 (&acc)[MI][8], Frags& f, const Loop& L, const Src& src, uint32_t rd_a, uint32_t rd_w,
-                                             uint32_t bufoff, uint32_t kb) {
-  constexpr int STEPS = MI * 8, NOPS = MI + 8, QA = STEPS / 2, QB = STEPS - QA;
-  if constexpr (FIRST) mfma_zero(acc[S / 8][S % 8], f.w[0][S % 8], f.a[0][S / 8]);
-  else mfma_acc(acc[S / 8][S % 8], f.w[0][S % 8], f.a[0][S / 8]);
-  if constexpr (S < QA) {
-    constexpr int R = slot_of(S, NOPS, QA);
-    if constexpr (R >= 0) read_frag<MI, 1, R>(f, rd_a, rd_w);
-    if constexpr (S == QA - 1 && DMA) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  } else if constexpr (DMA) {
-    constexpr int Q = slot_of(S - QA, NOPS, QB);
-    if constexpr (Q >= 0) dma_piece<MI, Q>(L, src, bufoff, kb);
-  }
-}
-template <int MI, bool DMA, bool FIRST, int... S>
-__device__ __forceinline__ void half0_steps_e(f32x4 (&acc)[MI][8], Frags& f, const Loop& L, const Src& src, uint32_t rd_a, uint32_t rd_w,
-                                              uint32_t bufoff, uint32_t kb, std::integer_sequence<int, S...>) {
-  (half0_step_e<MI, DMA, FIRST, S>(acc, f, L, src, rd_a, rd_w, bufoff, kb), ...);
-}
-// MODE1 as in k_tile: 1 = pieces + next tile's k-half-0 fragments, 2 = fragments only, 3 = neither, 4 = pieces only
-template <int MI, int MODE1, bool FIRST>
-__device__ __forceinline__ void k_tile_e(f32x4 (&acc)[MI][8], Frags& f, const Loop& L, const Src& src, uint32_t cur, uint32_t kb2) {
-  const uint32_t nxt = BUF_BYTES - cur;
-  constexpr bool DMA = MODE1 == 1 || MODE1 == 4;
-  half0_steps_e<MI, DMA, FIRST>(acc, f, L, src, L.a_rd[1] + cur, L.w_rd[1] + cur, cur, kb2, std::make_integer_sequence<int, MI * 8>{});
-  // Y: tile t+1 has landed (this wave's pieces: everything older than the MI + 8 pieces just requested), then every wave's
-  if constexpr (DMA) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(MI + 8) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  half_steps<MI, MODE1 == 3 || MODE1 == 4 ? 3 : 2, false>(acc, f, L, src, L.a_rd[0] + nxt, L.w_rd[0] + nxt, cur, kb2, std::make_integer_sequence<int, MI * 8>{});
-  if constexpr (MODE1 != 3 && MODE1 != 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
 // One k-tile t (cur = its buffer's byte offset): k-half 0, the mid-tile rendezvous, k-half 1 (whose DMA, MODE1 == 1, requests the
@@ -266,20 +178,12 @@ __device__ __forceinline__ void k_tile(f32x4 (&acc)[MI][8], Frags& f, const Loop
 template <int MI, int MODE1, bool FIRST, bool PF>
 __device__ __forceinline__ void k_tile(f32x4 (&acc)[MI][8], Frags& f, const Loop& L, const Src& src, uint32_t cur, uint32_t kb2,
                                        const Src& pf, uint32_t pf_soff) {
-#ifdef VC_4W_EARLY
-  k_tile_e<MI, MODE1, FIRST>(acc, f, L, src, cur, kb2);
-  return;
-#endif
   const uint32_t nxt = BUF_BYTES - cur;
   half_steps<MI, 0, FIRST>(acc, f, L, src, L.a_rd[1] + cur, L.w_rd[1] + cur, 0, 0, std::make_integer_sequence<int, MI * 8>{});
   // every wave has read the whole of buffer `cur` (lgkmcnt) and its own pieces of tile t+1 have landed (vmcnt): after the barrier
   // `cur` may be overwritten and buffer `nxt` may be read
-#if defined(VC_LOOP_ABL) && (VC_LOOP_ABL & 4)     // probe ablation: no mid-tile barrier (wrong results)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
   if constexpr (PF) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
   half_steps<MI, MODE1, false>(acc, f, L, src, L.a_rd[0] + nxt, L.w_rd[0] + nxt, cur, kb2, std::make_integer_sequence<int, MI * 8>{});
   if constexpr (PF) pf64(L.lds_pf, L.voff_pf, pf.ra, pf_soff);
   if constexpr (MODE1 != 3 && MODE1 != 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -378,9 +282,6 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[MI][8], const GemmArg
 // dropped by the range check, no predicate), one 32-bit per-lane offset serves the whole tile, the m-tile's row offset rides in
 // the scalar offset and the n-tile's in the immediate.  Same arithmetic per element.
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-#ifndef VC_4W_STORE_AUX
-#define VC_4W_STORE_AUX 0      // cache policy of the output stores (2 = nt)
-#endif
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* base, long long bytes) {
   const unsigned rec = bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes);
   return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, rec, 0x00020000);
@@ -408,18 +309,9 @@ __device__ __forceinline__ void epilogue_regs_fast(f32x4 (&acc)[MI][8], const Ge
         ve = gelu_erf4(ve);
         vo = gelu_erf4(vo);
       }
-#if defined(VC_EPI_ABL) && (VC_EPI_ABL & 2)       // probe ablation: no lane exchange (wrong results)
-      const u32x2_t s0 = u32x2_t{pack2bf(ve[0], ve[1]), pack2bf(vo[0], vo[1])};
-      const u32x2_t s1 = u32x2_t{pack2bf(ve[2], ve[3]), pack2bf(vo[2], vo[3])};
-#else
       const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[0], ve[1]), pack2bf(vo[0], vo[1]), false, false);
       const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[2], ve[3]), pack2bf(vo[2], vo[3]), false, false);
-#endif
-#if defined(VC_EPI_ABL) && (VC_EPI_ABL & 1)       // probe ablation: values kept alive, no store
-      asm volatile("" ::"v"(s0), "v"(s1));
-#else
-      __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{s0[0], s1[0], s0[1], s1[1]}, rc, voff + jj * 64, 0, VC_4W_STORE_AUX);
-#endif
+      __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{s0[0], s1[0], s0[1], s1[1]}, rc, voff + jj * 64, 0, 0);
     }
     voff += istep;
   }
@@ -479,7 +371,7 @@ __device__ __forceinline__ void epilogue_regs_fast_x(f32x4 (&acc)[MI][8], const 
           vo = gelu_erf4_grad(vo, dn);
           const u32x2_t z0 = __builtin_amdgcn_permlane16_swap(pack2bf(de[0], de[1]), pack2bf(dn[0], dn[1]), false, false);
           const u32x2_t z1 = __builtin_amdgcn_permlane16_swap(pack2bf(de[2], de[3]), pack2bf(dn[2], dn[3]), false, false);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{z0[0], z1[0], z0[1], z1[1]}, rz, voff_z + jj * 64, 0, VC_4W_STORE_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{z0[0], z1[0], z0[1], z1[1]}, rz, voff_z + jj * 64, 0, 0);
         } else {
           ve = gelu_erf4(ve);
           vo = gelu_erf4(vo);
@@ -488,7 +380,7 @@ __device__ __forceinline__ void epilogue_regs_fast_x(f32x4 (&acc)[MI][8], const 
       const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[0], ve[1]), pack2bf(vo[0], vo[1]), false, false);
       const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[2], ve[3]), pack2bf(vo[2], vo[3]), false, false);
       const u32x4_t o = u32x4_t{s0[0], s1[0], s0[1], s1[1]};
-      __builtin_amdgcn_raw_buffer_store_b128(o, rc, voff + jj * 64, 0, VC_4W_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(o, rc, voff + jj * 64, 0, 0);
       if (has_cs && row_ok) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -577,7 +469,7 @@ __device__ __forceinline__ void epilogue_regs_fast_defer(f32x4 (&acc)[MI][8], co
       const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[0], ve[1]), pack2bf(vo[0], vo[1]), false, false);
       const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(pack2bf(ve[2], ve[3]), pack2bf(vo[2], vo[3]), false, false);
       const u32x4_t o = u32x4_t{s0[0], s1[0], s0[1], s1[1]};
-      if (i < NI) __builtin_amdgcn_raw_buffer_store_b128(o, rc, voff + jj * 64, 0, VC_4W_STORE_AUX);
+      if (i < NI) __builtin_amdgcn_raw_buffer_store_b128(o, rc, voff + jj * 64, 0, 0);
       else pk.v[(i - NI) * 4 + jj] = o;
     }
     voff += istep;
@@ -640,7 +532,7 @@ __device__ __forceinline__ void epilogue_patch_fast(f32x4 (&acc)[MI][8], const G
       v += bias4;
       if (ACT == VITCAP_ACT_GELU_ERF) v = gelu_erf4(v);
       if (HAS_RES) v += rres[i & 1][it];
-      if (OUT_F32) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rc, voff_c, 0, VC_4W_STORE_AUX);
+      if (OUT_F32) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rc, voff_c, 0, 0);
       else __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])}, rc, voff_c, 0, 0);
       voff_c += cstep;
     }
@@ -805,14 +697,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nk = p.K / 64;      // >= 2 (launcher)
   constexpr auto PIECES = std::make_integer_sequence<int, MI + 8>{};
 
-  STAMP(0);
   // prologue: k-tiles 0 and 1 requested, tile 0 awaited, its k-half-0 fragments read
   dma_tile<MI>(L, src, 0, 0, PIECES);
   dma_tile<MI>(L, src, BUF_BYTES, 128, PIECES);
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(MI + 8) : "memory");
   read_frags<MI, 0>(f, L.a_rd[0], L.w_rd[0], PIECES);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  STAMP(1);
   uint32_t cur = BUF_BYTES;        // buffer of the tile about to run (after tile 0)
   if (nk == 2) {
     k_tile<MI, 2, true>(acc, f, L, src, 0, 0);
@@ -827,14 +717,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   k_tile<MI, 3, false>(acc, f, L, src, cur, 0);
   fence_accumulators<MI>(acc);
-  STAMP(2);
   const int row_w = m0 + (w >> 1) * (16 * MI), col_w = n0 + (w & 1) * 128;
   if constexpr (EPI == 1) {
     if constexpr (OUT_F32 || HAS_RES) epilogue_patch<ACT, OUT_F32, HAS_RES, MI>(acc, p, smem + 2 * BUF_BYTES + w * PATCH_BYTES, row_w, col_w, lane);
     else epilogue_regs<ACT, OUT_F32, HAS_RES, MI>(acc, p, row_w, col_w, lane);
   }
   else epilogue_lds<ACT, OUT_F32, HAS_RES, MI>(acc, p, smem + w * EP_WAVE, row_w, col_w, lane);
-  STAMP(3);
 }
 
 // ---- persistent form: one workgroup per CU walks its share of the tile list as ONE continuous software pipeline.  The k-tile
@@ -859,10 +747,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nslot = ((int)gridDim.x - xcd + 7) >> 3;
   int pos = c0 + ((int)blockIdx.x >> 3);
   if (pos >= c1) return;
-#ifdef VC_4W_STAMP
-  // probe: start the XCDs a fraction of a tile period apart (p.direct_epilogue = units of 64 cycles per XCD step)
-  for (int i = 0; i < ((int)blockIdx.x >> 3) * p.direct_epilogue; ++i) __builtin_amdgcn_s_sleep(1);
-#endif
   Loop L = make_loop<MI>(p, lds_addr(smem), lane, w);
   int tm, tn;
   tile_of(p, pos, tm, tn);
@@ -915,11 +799,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       // rows c, c + gw, c + 2 gw ...; k-tile t of THIS tile requests RPS of them, whole rows (nk lines of 128 B: one DRAM page).
       // lane -> (row within the chunk, line of the row)
       const int gw_ = p.group_n < p.tiles_n ? p.group_n : p.tiles_n;
-#ifdef VC_4W_PF_ALL
-      const int gwe = 1, c_ = 0;
-#else
       const int gwe = gw_, c_ = tn % gw_;
-#endif
       const int share = (32 * MI - c_ + gwe - 1) / gwe;
       const int rps = (share + nk - 1) / nk;
       const int Lq = w * 64 + lane;
@@ -929,14 +809,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 #define PF_ARGS(t_) , nsrc, (uint32_t)(t_) * pf_step
     // k-tiles 0 .. nk-3 request k-tiles 2 .. nk-1 of this tile; k-tiles nk-2, nk-1 request k-tiles 0, 1 of the next tile (nk >= 3)
-    STAMP_AT(pos, 0);
     int t_plain = 1;
     if constexpr (DEFER) {
       // k-tiles 0 .. NP-1 issue the previous tile's parked stores, one m-tile (4 stores) each
       constexpr int NP = Park<MI>::NP;
       k_tile_st<MI, 1, true, 0>(acc, f, L, src, cur, 2 * 128, pk, p, park_row);
       cur = BUF_BYTES - cur;
-      STAMP_AT(pos, 1);
       if constexpr (NP > 1) { k_tile_st<MI, 1, false, 4>(acc, f, L, src, cur, 3 * 128, pk, p, park_row); cur = BUF_BYTES - cur; }
       if constexpr (NP > 2) { k_tile_st<MI, 1, false, 8>(acc, f, L, src, cur, 4 * 128, pk, p, park_row); cur = BUF_BYTES - cur; }
       if constexpr (NP > 3) { k_tile_st<MI, 1, false, 12>(acc, f, L, src, cur, 5 * 128, pk, p, park_row); cur = BUF_BYTES - cur; }
@@ -944,7 +822,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     } else {
       k_tile<MI, 1, true, PF>(acc, f, L, src, cur, 2 * 128 PF_ARGS(0));
       cur = BUF_BYTES - cur;
-      STAMP_AT(pos, 1);
     }
     for (int t = t_plain; t < nk - 2; ++t) {
       k_tile<MI, 1, false, PF>(acc, f, L, src, cur, (uint32_t)(t + 2) * 128 PF_ARGS(t));
@@ -956,13 +833,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef PF_ARGS
     cur = BUF_BYTES - cur;
     fence_accumulators<MI>(acc);
-    STAMP_AT(pos, 2);
-#ifdef VC_4W_GENERAL_EPI
-    if constexpr (OUT_F32 || HAS_RES)
-      epilogue_patch<ACT, OUT_F32, HAS_RES, MI>(acc, p, smem + 2 * BUF_BYTES + w * PATCH_BYTES, m0 + (w >> 1) * (16 * MI), n0 + (w & 1) * 128, lane);
-    else
-      epilogue_regs<ACT, OUT_F32, HAS_RES, MI>(acc, p, m0 + (w >> 1) * (16 * MI), n0 + (w & 1) * 128, lane);
-#else
     if constexpr (OUT_F32 || HAS_RES)
       epilogue_patch_fast<ACT, OUT_F32, HAS_RES, MI>(acc, p, smem + 2 * BUF_BYTES + w * PATCH_BYTES, m0 + (w >> 1) * (16 * MI), n0 + (w & 1) * 128, lane);
     else
@@ -974,8 +844,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       else epilogue_regs_fast<ACT, MI>(acc, p, m0 + (w >> 1) * (16 * MI), n0 + (w & 1) * 128, lane);
     }
-#endif
-    STAMP_AT(pos, 3);
     if (!more) {
       if constexpr (DEFER) store_parked_all<MI>(pk, park_rsrc(p, park_row), std::make_integer_sequence<int, Park<MI>::NP * 4>{});      // the last tile flushes its own parked half
       break;
@@ -1002,20 +870,15 @@ int device_cus() {
   }();
   return n;
 }
-// workgroups of the persistent grid = CUs it occupies (512 registers per lane: one workgroup owns a CU).  VITCAP_GEMM_4W_RESERVE = R
-// leaves R CUs (a multiple of 8: the XCDs stay balanced) to whatever else runs on the GPU -- the batch pipeline's decode chain
-std::atomic<int> g_reserve_cus{0};       // vitcap_gemm_reserve_cus: set by the caller while a collective is in flight
+// workgroups of the persistent grid = CUs it occupies (512 registers per lane: one workgroup owns a CU), less the CUs (a multiple of
+// 8: the XCDs stay balanced) that vitcap_gemm_reserve_cus leaves to whatever else runs on the GPU while a collective is in flight
+std::atomic<int> g_reserve_cus{0};
 int persistent_cus() {
-  static const int env_reserve = [] { const char* e = getenv("VITCAP_GEMM_4W_RESERVE"); return e ? atoi(e) : 0; }();
-  const int run = g_reserve_cus.load(std::memory_order_relaxed);
-  const int reserve = run > env_reserve ? run : env_reserve;
-  const int n = device_cus() - (reserve > 0 ? reserve : 0);
+  const int n = device_cus() - g_reserve_cus.load(std::memory_order_relaxed);
   return n >= 8 ? n : 8;
 }
 
 int pick_mi(int M, int tiles_n, int form) {
-  static const int env_mi = [] { const char* e = getenv("VITCAP_GEMM4W_MI"); return e ? atoi(e) : 0; }();
-  if (env_mi >= 4 && env_mi <= 8 && env_mi != 5) return env_mi;
   const int n_cu = form == 2 ? persistent_cus() : device_cus();
   const float fixed = form == 2 ? 0.3f : 0.9f;       // per-tile cost that does not shrink with the tile: pipeline fill, barriers' skew, W traffic
   int best = 8;
@@ -1037,17 +900,7 @@ int launch_4w_mi(GemmArgs& p, hipStream_t s, int form) {
     const int n_cu = persistent_cus();
     const bool extras = p.aux || p.zout || p.colsum;        // training extras: the bf16 register epilogue's second form (vc_4w_supports)
     constexpr int smem = (OUT_F32 || HAS_RES) ? SMEM_4WP : 2 * BUF_BYTES;
-    // VITCAP_GEMM_4W_TIGHT=1 (experiments): the fewest workgroups (a multiple of 8: every XCD the same number) that finish in the same
-    // number of rounds as all CUs would -- 1305 tiles take 6 rounds on 256 CUs and on 224 -- leaving the other CUs to whatever else
-    // runs.  Measured (docs/LAB_r01_r04.md 4.3): no gain alone (19.55 vs 19.59 ms, B = 512 124.3 vs 123.3), and inside the batch pipeline only a
-    // CONSTANT reservation helps the decode chain (VITCAP_GEMM_4W_RESERVE=32 ties the 8-wave kernel there), so the default is off
-    static const int tight = [] { const char* e = getenv("VITCAP_GEMM_4W_TIGHT"); return e ? atoi(e) : 0; }();
-    int grid = p.n_big < n_cu ? p.n_big : n_cu;
-    if (tight && p.n_big > n_cu) {
-      const int rounds = (p.n_big + n_cu - 1) / n_cu;
-      const int need = ((p.n_big + rounds - 1) / rounds + 7) & ~7;
-      if (need < grid) grid = need;
-    }
+    const int grid = p.n_big < n_cu ? p.n_big : n_cu;
     // one call site per kernel: VC_FUNC_SMEM remembers per call site that the attribute was set
     bool launched = false;
     if constexpr (!OUT_F32 && !HAS_RES) {
@@ -1061,7 +914,6 @@ int launch_4w_mi(GemmArgs& p, hipStream_t s, int form) {
       // HBM and the same loop takes 32-37k instead of 25.4k cycles per tile; whole rows of the NEXT tile's panel, split over the column
       // siblings, requested one per k-tile bring it to 29.7k (qkv +3.6 %, fc1 +2.1 % wall at M = 295 424, docs/LAB_r05.md section 1).
       // Below the threshold the operands are cache-resident and the extra instruction only costs (+0.8 % loop cycles): plain form.
-      // VITCAP_GEMM_4W_PF: 0 = never, N > 1 = from N rows on (default 65536).
       // deferred stores (round 6): the upper half of every wave tile's stores ride behind the next tile's first k-tiles.  Measured
       // (profiles/r06_deferred_stores.txt): the epilogue shrinks as priced (qkv 8.7k -> 6.2k cycles per tile), but with ONE wave per
       // SIMD a store's issue (~150 cycles each) stalls the wave wherever it stands, so the next tile's loop pays what the epilogue
@@ -1081,8 +933,7 @@ int launch_4w_mi(GemmArgs& p, hipStream_t s, int form) {
         }
       }
       if constexpr (MI == 8) {
-        static const int pf_rows = [] { const char* e = getenv("VITCAP_GEMM_4W_PF"); return e ? atoi(e) : 65536; }();
-        if (!launched && pf_rows > 0 && p.M >= pf_rows && p.tiles_m > 1) {
+        if (!launched && p.M >= 65536 && p.tiles_m > 1) {
           auto kern = gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, false, true>;
           constexpr int smem_pf = 2 * BUF_BYTES + 1024;
           VC_FUNC_SMEM(kern, smem_pf);
@@ -1129,7 +980,6 @@ int launch_4w(const GemmArgs& a, hipStream_t s, int form) {
   switch (pick_mi(a.M, p.tiles_n, form)) {
     case 7: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 7>(p, s, form);
     case 6: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 6>(p, s, form);
-    case 4: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 4>(p, s, form);
     default: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 8>(p, s, form);
   }
 }
@@ -1144,19 +994,7 @@ extern "C" int vitcap_gemm_reserve_cus(int cus) {
 
 int vc_4w_pick_mi(int M, int tiles_n, int form) { return form == 0 ? 8 : pick_mi(M, tiles_n, form); }
 
-// Whether the AUTOMATIC choice hands a launch with training extras to the 4-wave kernel.  Measured inside the training step on one box
-// (profiles/r05_train_extras_ab.txt): every such launch on the 8-wave kernel 52.16 / 52.28 ms per step; zout launches (fc1 forward) on
-// the 4-wave kernel 52.47 / 52.44; aux + colsum launches (fc2 input gradient) as well 53.11 / 53.12 -- so the default is "none".
-// VITCAP_GEMM_4W_EXTRAS: bit 0 = launches with zout, bit 1 = with aux, bit 2 = with colsum may go (tile_hint 42 always does).
-bool vc_4w_extras_auto(const GemmArgs& a) {
-  static const int mask = [] { const char* e = getenv("VITCAP_GEMM_4W_EXTRAS"); return e ? atoi(e) : 0; }();
-  return !((a.zout && !(mask & 1)) || (a.aux && !(mask & 2)) || (a.colsum && !(mask & 4)));
-}
-
 bool vc_4w_supports(const GemmArgs& a, int act) {
-#ifdef VC_4W_STAMP
-  if (a.rowstat) return true;
-#endif
   if (a.aux || a.zout || a.colsum) {
     // training extras: the PERSISTENT form's bf16 register epilogue only (no downgrade of the form inside launch_4w: the caller checks
     // that the persistent form was chosen) -- plain rows, whole 256-column tiles, 16-byte aligned rows of every operand

@@ -21,7 +21,6 @@ struct GemmArgs {
   int ldaux;
   bf16_t* zout;        // gelu'(pre-activation) for the backward (act == GELU only; the factor a later launch takes as `aux`); bf16 [M][ldz]
   int ldz;
-  int direct_epilogue; // 256x256 kernels: register-transpose epilogue (1) or the LDS-staged one (0)
   int split_k;         // > 1: blockIdx.y = split, ragged k-tile ranges, fp32 partial slabs, no epilogue
   int kt_per_split;
   size_t slab;
@@ -36,7 +35,7 @@ struct GemmArgs {
   bf16_t* ln_out;              // [M][768] bf16 or null
   float* ln_out_f;             // [M][768] fp32 or null
   int32_t* ln_cnt;             // one counter per row block, zero on entry, zero again on exit
-  int rev;                     // 256-row-tile kernels: walk the tile list last-to-first (vc_tls_walk_rev / tile_hint flag 0x1000)
+  int rev;                     // 256-row-tile kernels: walk the tile list last-to-first (vc_tls_walk_rev)
 };
 
 // launch of a large-tile GEMM: with kernel-bound timing events when the engine's timing run asked for them (common.h)
@@ -56,6 +55,5 @@ int vc_tile_group_n(int tiles_n);
 // form: 0 = one tile per workgroup + LDS epilogue, 1 = one tile per workgroup + register epilogue, 2 = persistent
 int vc_dispatch_4w(const GemmArgs& a, int act, int out_f32, hipStream_t s, int form);
 bool vc_4w_supports(const GemmArgs& a, int act);
-bool vc_4w_extras_auto(const GemmArgs& a);     // policy: may the automatic choice give a launch with aux / zout / colsum to the 4-wave kernel
 // m-tiles of 16 rows per wave (8 / 7 / 6 -> 256- / 224- / 192-row tiles) the 4-wave kernel picks for a launch
 int vc_4w_pick_mi(int M, int tiles_n, int form);
