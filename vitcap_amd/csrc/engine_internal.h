@@ -1,0 +1,52 @@
+// The engine object, shared by engine.cpp (enqueue) and engine_timing.cpp (per-launch GEMM timing).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../include/vitcap_hip.h"
+#include "call_state.h"
+
+// Optional per-launch timing of the large-tile GEMM launches (bench.py's live roofline measurement):
+// hipEvents are recorded on the SAME stream right before/after each launch; the pool is grown outside
+// the timed region by vitcap_engine_timing_begin().
+struct GemmTiming {
+  hipEvent_t start, stop;     // stream markers right before / after the launch
+  hipEvent_t kstart, kstop;   // bound to the kernel dispatch itself (hipExtLaunchKernelGGL): what rocprofv3 --kernel-trace reports
+  bool kernel_bound;          // the launcher took kstart / kstop
+  int variant;      // act*4 + out_f32*2 + has_res
+  double flops;
+};
+
+struct GraphEntry {
+  int B;
+  void* ws;
+  vitcap_gen_opts opts;
+  hipGraph_t graph;
+  hipGraphExec_t exec;
+};
+
+struct vitcap_engine {
+  vitcap_weights w;
+  bool bound = false;
+  bool timing = false;
+  int timing_stride = 1;      // the large-GEMM launches of every timing_stride-th STEP (encode call) are timed (vitcap_engine_timing_sample)
+  long long timing_seen = 0;  // steps since timing_begin
+  bool timing_this_step = true;
+  // one enqueue at a time per engine: the side stream / fork-join events and the graph cache are shared by all callers
+  std::mutex mu;
+  // the tag branch of the encoder (4 tag blocks + tag head) runs on this side stream next to caption blocks 8-11
+  hipStream_t side = nullptr;
+  hipStream_t cap = nullptr;          // the decode loop is CAPTURED on this engine-owned stream (capture executes nothing), so the
+                                      // caller's stream may be any stream, the legacy default stream included
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipStream_t dec2 = nullptr;         // second stream of the split decode loop (vitcap_gen_opts.decode_streams = 2)
+  hipEvent_t ev_dfork = nullptr, ev_djoin = nullptr;
+  hipStream_t part[3] = {nullptr, nullptr, nullptr};   // streams of encoder parts 1..3 (part 0 runs on the caller's stream)
+  hipEvent_t ev_pfork = nullptr, ev_pjoin[3] = {nullptr, nullptr, nullptr};   // the parts share one fork event
+  bool full_last_tag_block = false;   // VITCAP_FULL_TAG_BLOCK=1: compute all 577 rows of tag_blocks[3] (parity taps / measurements)
+  std::vector<GemmTiming> pool;
+  size_t used = 0;
+  std::vector<GraphEntry> graphs;     // captured decode loops (vitcap_gen_opts.use_graph)
+};
