@@ -135,106 +135,20 @@ class ImageCaptioning(nn.Module):
     def _t(self, key):
         return self._params[key].detach()
 
-    def pack(self, device='cuda'):
-        """Re-lay the checkpoint tensors for the kernels (bf16 matrices, fused decoder QKV, padded vocab)."""
-        dev = torch.device(device)
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        keep = []
-
-        def bf(t):
-            o = t.to(device=dev, dtype=torch.float32).to(torch.bfloat16).contiguous()
-            keep.append(o)
-            return o
-
-        def f32(t):
-            o = t.to(device=dev, dtype=torch.float32).contiguous()
-            keep.append(o)
-            return o
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr())
-
-        def pad_vocab(t):
-            o = torch.zeros((L.VOCAB_PAD,) + tuple(t.shape[1:]), dtype=torch.float32)
-            o[:t.shape[0]] = t
-            return o
-
-        w = L.Weights()
-        ie = 'image_encoder.module.'
-        w.patch_w = ptr(bf(self._t(ie + 'patch_embed.proj.weight').reshape(768, 768)))
-        w.patch_b = ptr(f32(self._t(ie + 'patch_embed.proj.bias')))
-        w.cls_token = ptr(f32(self._t(ie + 'cls_token').reshape(768)))
-        w.pos_embed = ptr(f32(self._t(ie + 'pos_embed').reshape(577, 768)))
-
-        def vit_block(dst, p):
-            dst.qkv_w = ptr(bf(self._t(p + '.attn.qkv.weight')))
-            dst.qkv_b = ptr(f32(self._t(p + '.attn.qkv.bias')))
-            dst.proj_w = ptr(bf(self._t(p + '.attn.proj.weight')))
-            dst.proj_b = ptr(f32(self._t(p + '.attn.proj.bias')))
-            dst.fc1_w = ptr(bf(self._t(p + '.mlp.fc1.weight')))
-            dst.fc1_b = ptr(f32(self._t(p + '.mlp.fc1.bias')))
-            dst.fc2_w = ptr(bf(self._t(p + '.mlp.fc2.weight')))
-            dst.fc2_b = ptr(f32(self._t(p + '.mlp.fc2.bias')))
-            dst.n1_g = ptr(f32(self._t(p + '.norm1.weight')))
-            dst.n1_b = ptr(f32(self._t(p + '.norm1.bias')))
-            dst.n2_g = ptr(f32(self._t(p + '.norm2.weight')))
-            dst.n2_b = ptr(f32(self._t(p + '.norm2.bias')))
-
-        for i in range(12):
-            vit_block(w.blocks[i], 'module.bert.encoder.blocks.%d' % i)
-        for i in range(4):
-            vit_block(w.tag_blocks[i], 'module.bert.encoder.tag_blocks.%d' % i)
-        w.pooler_w = ptr(bf(self._t('module.bert.pooler.dense.weight')))
-        w.pooler_b = ptr(f32(self._t('module.bert.pooler.dense.bias')))
-
-        def lm_head(dst, p, dec_w_packed=None):
-            dst.dense_w = ptr(bf(self._t(p + '.predictions.transform.dense.weight')))
-            dst.dense_b = ptr(f32(self._t(p + '.predictions.transform.dense.bias')))
-            dst.ln_g = ptr(f32(self._t(p + '.predictions.transform.LayerNorm.weight')))
-            dst.ln_b = ptr(f32(self._t(p + '.predictions.transform.LayerNorm.bias')))
-            dw = dec_w_packed if dec_w_packed is not None else bf(pad_vocab(self._t(p + '.predictions.decoder.weight')))
-            dst.dec_w = ptr(dw)
-            dst.dec_b = ptr(f32(pad_vocab(self._t(p + '.predictions.bias'))))
-            return dw
-
-        lm_head(w.tag_logit, 'module.bert.tag_logit')
-        e = 'module.bert.embeddings'
-        word = bf(pad_vocab(self._t(e + '.word_embeddings.weight')))
-        w.word_emb = ptr(word)
-        w.pos_emb = ptr(bf(self._t(e + '.position_embeddings.weight')))
-        w.type_emb = ptr(bf(self._t(e + '.token_type_embeddings.weight')))
-        w.emb_ln_g = ptr(f32(self._t(e + '.LayerNorm.weight')))
-        w.emb_ln_b = ptr(f32(self._t(e + '.LayerNorm.bias')))
-        for i in range(4):
-            p = 'module.bert.decoder.layer.%d' % i
-            d = w.dec[i]
-            d.qkv_w = ptr(bf(torch.cat([self._t('%s.attention.self.%s.weight' % (p, n))
-                                        for n in ('query', 'key', 'value')], 0)))
-            d.qkv_b = ptr(f32(torch.cat([self._t('%s.attention.self.%s.bias' % (p, n))
-                                         for n in ('query', 'key', 'value')], 0)))
-            d.ao_w = ptr(bf(self._t(p + '.attention.output.dense.weight')))
-            d.ao_b = ptr(f32(self._t(p + '.attention.output.dense.bias')))
-            d.ao_g = ptr(f32(self._t(p + '.attention.output.LayerNorm.weight')))
-            d.ao_beta = ptr(f32(self._t(p + '.attention.output.LayerNorm.bias')))
-            d.i_w = ptr(bf(self._t(p + '.intermediate.dense.weight')))
-            d.i_b = ptr(f32(self._t(p + '.intermediate.dense.bias')))
-            d.o_w = ptr(bf(self._t(p + '.output.dense.weight')))
-            d.o_b = ptr(f32(self._t(p + '.output.dense.bias')))
-            d.o_g = ptr(f32(self._t(p + '.output.LayerNorm.weight')))
-            d.o_beta = ptr(f32(self._t(p + '.output.LayerNorm.bias')))
-        tied = self._params[W.TIED_DST] is self._params[W.TIED_SRC]
-        lm_head(w.cls, 'module.cls', dec_w_packed=word if tied else None)
-        if self.tagemb != 'cls':
-            # bert.extra_embeddings: the tag rows' embedding under branch B of modeling_bert.py:1484-1485 (only read when the tag
-            # tokens are visible to the caption, vitcap_gen_opts.tag_visible > 0)
-            x = 'module.bert.extra_embeddings'
-            w.xword_emb = ptr(bf(pad_vocab(self._t(x + '.word_embeddings.weight'))))
-            w.xpos_emb = ptr(bf(self._t(x + '.position_embeddings.weight')))
-            w.xtype_emb = ptr(bf(self._t(x + '.token_type_embeddings.weight')))
-            w.xemb_ln_g = ptr(f32(self._t(x + '.LayerNorm.weight')))
-            w.xemb_ln_b = ptr(f32(self._t(x + '.LayerNorm.bias')))
-
+    def bind_weights(self, source, keep, dev):
+        """Fills a vitcap_weights by walking W.weights_table() -- `source(field)` gives the device tensor behind a field, or None for
+        an optional field that stays null -- and binds it to the engine (created on first use).  `keep` holds what must outlive it."""
+        w, done = L.Weights(), {}
+        for f in W.weights_table():
+            t = done[f.tied_to] if (f.tied_to and self._params[W.TIED_DST] is self._params[W.TIED_SRC]) else source(f)
+            if t is None:
+                assert f.optional, f.path
+                continue
+            done[f.path] = t
+            dst = w
+            for step in f.path[:-1]:
+                dst = dst[step] if isinstance(step, int) else getattr(dst, step)
+            setattr(dst, f.path[-1], C.c_void_p(t.data_ptr()))
         if self._engine is None:
             h = C.c_void_p()
             check(lib.vitcap_engine_create(C.byref(h)), 'engine_create')
@@ -242,6 +156,32 @@ class ImageCaptioning(nn.Module):
         check(lib.vitcap_engine_bind_weights(self._engine, C.byref(w)), 'bind_weights')
         self._packed = (w, keep, dev)
         return self
+
+    def pack(self, device='cuda'):
+        """Re-lay the checkpoint tensors for the kernels (bf16 matrices, fused decoder QKV, padded vocab)."""
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        keep = []
+
+        def convert(f):
+            if f.optional and self.tagemb == 'cls':
+                # bert.extra_embeddings: the tag rows' embedding under branch B of modeling_bert.py:1484-1485 (only read when the tag
+                # tokens are visible to the caption, vitcap_gen_opts.tag_visible > 0)
+                return None
+            t = torch.cat([self._t(k) for k in f.keys], 0) if len(f.keys) > 1 else self._t(f.keys[0])
+            if f.shape is not None:
+                t = t.reshape(f.shape)
+            if f.pad is not None:
+                o = torch.zeros((f.pad,) + tuple(t.shape[1:]), dtype=torch.float32)
+                o[:t.shape[0]] = t
+                t = o
+            t = t.to(device=dev, dtype=torch.float32)
+            t = (t.to(torch.bfloat16) if f.kind == 'mat' else t).contiguous()
+            keep.append(t)
+            return t
+
+        return self.bind_weights(convert, keep, dev)
 
     def __del__(self):
         try:

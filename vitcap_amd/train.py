@@ -34,14 +34,11 @@ from . import weights as W
 from ._lib import check, lib
 
 CH = 1024           # optimizer chunk (elements)
-_FUSE_BIAS = os.environ.get('VITCAP_TRAIN_FUSED_BIAS', '1') != '0'      # A/B switch of the measurement in docs/LAB_r01_r04.md 7
-_TN_SUM = os.environ.get('VITCAP_TRAIN_TN_SUM', '0') != '0'             # 1: the splits of a weight gradient add themselves up inside the launch
-# (vitcap_gemm_tn_sum, bit-identical) instead of a reduce_slabs launch each -- measured SLOWER inside the graph-replayed step (48.85 vs 49.3 ms:
-# profiles/r05_train_attn_bwd_ab.txt): the ticket wait and the write-through slabs cost more than 80 cheap launches save
 NV = 577
 SV = 578
 T = 20
-LR = SV + T         # decoder rows per image
+LR = SV + T         # decoder rows per image (masked-token step)
+QLO = (SV // 128) * 128     # first 128-row query block of the decoder that holds text rows
 
 
 def _p(t):
@@ -223,6 +220,35 @@ class _FusedLoss(torch.autograd.Function):
         return None, None, None
 
 
+class _Rec(object):
+    """Plain record of views: one layer's weights, or one weight's w / wt / b / gw / gb (TrainEngine._bind_layers)."""
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Step(object):
+    """Per-step context of TrainEngine._fb_gen (the role Enq plays in csrc/engine.cpp): shapes, flags, dropout seeds and
+    probabilities, and the activations one phase of the step leaves for a later one (set by the phase that produces them)."""
+    def __init__(self, eng, batch, capture):
+        self.batch = batch
+        self.Be = batch['image'].shape[0]                # images the encoder runs on
+        self.KS = int(batch.get('seq_per_image', 1))     # decoder sequences per image (self-critical step: the samples of an image
+        self.B = self.Be * self.KS                       # share its encoder pass; their visual-row gradients are summed before its backward)
+        self.scst = 'sample_ids' in batch
+        self.TP = (T - 1) if self.scst else 0            # probe rows per sequence
+        self.TT = T + self.TP                            # text rows per sequence
+        self.LR = SV + self.TT                           # decoder rows per sequence
+        self.M, self.Md = self.Be * NV, self.B * self.LR
+        self.prune = eng.prune_dead_rows
+        self.ph, self.pd = eng.hidden_dropout, eng.attn_dropout
+        self.seed = mix32(eng.dropout_seed, 0 if capture else eng.step_no)
+        self.dseed = [mix32(self.seed, l) for l in range(4)]      # attention dropout: per step, per layer
+        self.saved, self.dsaved = {}, []                 # ViT activations by block record; decoder activations by layer
+
+    def hseed(self, l, site):
+        """Hidden dropout: per step, per layer (4 = embeddings), per site (1 attention.output, 2 output, 3 embeddings)."""
+        return mix32(mix32(self.seed, 16 + l), site)
+
 class TrainEngine(object):
     def __init__(self, model, device='cuda', base_lr=1e-4, weight_decay=0.05, lr_multiplier=0.1, clip=1.0, max_iter=1000,
                  label_smoothing=0.1, dist=None, attn_dropout=0.1, dropout_seed=0, tag_loss='focal', hidden_dropout=0.0):
@@ -273,6 +299,7 @@ class TrainEngine(object):
         self.nan_dump = None              # callable(name) that saves the context (the pipeline passes its Checkpointer.save); default: torch.save here
         self.nan_dump_dir = '.'
         self.refresh_weights()
+        self._bind_layers()
         self.reducer = BucketedAllReduce(self.G, grad_buckets(order, self.off, self.shape), GRAD_STAGES, dist)
         self._anchor = torch.zeros(1, device=self.dev, requires_grad=True)
         self._pending = False
@@ -284,7 +311,7 @@ class TrainEngine(object):
         """What ImageCaptioning.forward returns in training mode (..._bertemb.py:170-171)."""
         return {'masked_loss': _FusedLoss.apply(self._anchor, self, batch)}
 
-    def check_text_inputs(self, batch):
+    def check_text_inputs(self, batch, host_read=True):
         """The training kernels hard-wire the mask CaptionTensorizer.tensorize_ab builds for a caption without text_b
         (dataset.py:377-390, mask_type seq2seq): token row i attends the visual rows and token rows <= i; rows behind the
         caption's [SEP] are padding whose outputs the loss never reads.  A caller's `attention_mask` (B, L, L) is verified
@@ -293,11 +320,13 @@ class TrainEngine(object):
         being trained with a different mask than the caller asked for.
         Host tensors (what the loader yields) are checked on the host.  Tensors that already live on the device are checked
         with a host read on the first step only; afterwards the comparison runs on their stream into a device counter that is
-        read every 50 steps (a per-step read would be a device-to-host synchronisation in front of every step)."""
+        read every 50 steps (a per-step read would be a device-to-host synchronisation in front of every step).
+        host_read=False (the step is being captured into a graph): the device-side comparison only, read by flush_text_check
+        outside the graph."""
         ok = train_text_inputs_ok(batch)
         if ok is None:
             return
-        if not ok.is_cuda or not getattr(self, '_text_checked', False):
+        if host_read and (not ok.is_cuda or not getattr(self, '_text_checked', False)):
             self._text_checked = True
             if not bool(ok):
                 raise NotImplementedError(
@@ -305,11 +334,15 @@ class TrainEngine(object):
                     'real caption rows of the first %d slots, zeros elsewhere: tensorize_ab without text_b, mask_type seq2seq, '
                     'dataset.py:377-390)' % T)
             return
-        if getattr(self, '_text_bad', None) is None:
-            self._text_bad = torch.zeros((), dtype=torch.int32, device=ok.device)
-        self._text_bad += (~ok).to(torch.int32)
-        if self.step_no % 50 == 49:
+        self._text_counter(ok.device).add_((~ok).to(torch.int32))
+        if host_read and self.step_no % 50 == 49:
             self.flush_text_check()
+
+    def _text_counter(self, device):
+        """Device-side count of the batches whose text tensors the kernels do not implement (read by flush_text_check)."""
+        if getattr(self, '_text_bad', None) is None:
+            self._text_bad = torch.zeros((), dtype=torch.int32, device=device)
+        return self._text_bad
 
     def sync_from_rank0(self):
         """Parameters AND Adam moments of every rank := rank 0's (after a resume: a rank that read a stale or different snapshot would
@@ -368,9 +401,6 @@ class TrainEngine(object):
         n = int(torch.Size(self.shape[k]).numel())
         return self.G[self.off[k]:self.off[k] + n].view(self.shape[k])
 
-    def _flat(self, buf, k, n, shape):
-        return buf[self.off[k]:self.off[k] + n].view(shape)
-
     def state_dict(self):
         return {k: self.p(k).detach().clone() for k in W.state_dict_spec()}
 
@@ -403,27 +433,14 @@ class TrainEngine(object):
 
     # ------------------------------------------------------------------ bf16 operands of the GEMMs
     def _matrices(self):
-        """(name, first key, N, K, pad_N): GEMM weights; decoder q|k|v are one [2304,768] matrix in the flat layout."""
-        out = [('patch', 'image_encoder.module.patch_embed.proj.weight', 768, 768, 768)]
-        for pre in ['module.bert.encoder.blocks.%d' % i for i in range(12)] + \
-                   ['module.bert.encoder.tag_blocks.%d' % i for i in range(4)]:
-            out += [(pre + '.qkv', pre + '.attn.qkv.weight', 2304, 768, 2304), (pre + '.proj', pre + '.attn.proj.weight', 768, 768, 768),
-                    (pre + '.fc1', pre + '.mlp.fc1.weight', 3072, 768, 3072), (pre + '.fc2', pre + '.mlp.fc2.weight', 768, 3072, 768)]
-        for i in range(4):
-            pre = 'module.bert.decoder.layer.%d' % i
-            out += [(pre + '.qkv', pre + '.attention.self.query.weight', 2304, 768, 2304),
-                    (pre + '.ao', pre + '.attention.output.dense.weight', 768, 768, 768),
-                    (pre + '.i', pre + '.intermediate.dense.weight', 3072, 768, 3072),
-                    (pre + '.o', pre + '.output.dense.weight', 768, 3072, 768)]
-        out += [('pooler', 'module.bert.pooler.dense.weight', 768, 768, 768),
-                ('tag.t', 'module.bert.tag_logit.predictions.transform.dense.weight', 768, 768, 768),
-                ('tag.dec', 'module.bert.tag_logit.predictions.decoder.weight', 30522, 768, L.VOCAB_PAD),
-                ('cls.t', 'module.cls.predictions.transform.dense.weight', 768, 768, 768),
-                ('word', 'module.bert.embeddings.word_embeddings.weight', 30522, 768, L.VOCAB_PAD),
-                ('pos', 'module.bert.embeddings.position_embeddings.weight', 512, 768, 512),
-                ('type', 'module.bert.embeddings.token_type_embeddings.weight', 2, 768, 8)]
-        if not self.model.tie_weights:
-            out.append(('cls.dec', 'module.cls.predictions.decoder.weight', 30522, 768, L.VOCAB_PAD))
+        """(name, first key, N, K, pad_N): GEMM weights = the matrix rows of W.weights_table() this engine trains (decoder q|k|v are
+        one [2304,768] matrix in the flat layout; a tied caption decoder is the word embedding's pair)."""
+        spec, out = W.state_dict_spec(), []
+        for f in W.weights_table():
+            if f.kind != 'mat' or f.optional or (f.tied_to and self.model.tie_weights):
+                continue
+            N, K = f.rows_cols(spec)
+            out.append((f.name, f.keys[0], N, K, f.pad or (N + 7) // 8 * 8))
         return out
 
     def refresh_weights(self):
@@ -451,55 +468,15 @@ class TrainEngine(object):
         """Points the model's INFERENCE engine at this engine's own device buffers (bf16 matrices refreshed after every
         optimizer step, fp32 vectors = views of the master buffer): generate() then always decodes with the current
         weights, with no copy -- what the self-critical step needs between its sampling and its gradient pass."""
-        m, w = self.model, L.Weights()
-        P = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
-        vec = self.vec
-        ie = 'image_encoder.module.'
-        w.patch_w, w.patch_b = P(self.wb('patch')), P(vec(ie + 'patch_embed.proj.bias'))
-        w.cls_token, w.pos_embed = P(vec(ie + 'cls_token')), P(vec(ie + 'pos_embed'))
-
-        def vit_block(dst, pre):
-            dst.qkv_w, dst.qkv_b = P(self.wb(pre + '.qkv')), P(vec(pre + '.attn.qkv.bias'))
-            dst.proj_w, dst.proj_b = P(self.wb(pre + '.proj')), P(vec(pre + '.attn.proj.bias'))
-            dst.fc1_w, dst.fc1_b = P(self.wb(pre + '.fc1')), P(vec(pre + '.mlp.fc1.bias'))
-            dst.fc2_w, dst.fc2_b = P(self.wb(pre + '.fc2')), P(vec(pre + '.mlp.fc2.bias'))
-            dst.n1_g, dst.n1_b = P(vec(pre + '.norm1.weight')), P(vec(pre + '.norm1.bias'))
-            dst.n2_g, dst.n2_b = P(vec(pre + '.norm2.weight')), P(vec(pre + '.norm2.bias'))
-        for i in range(12):
-            vit_block(w.blocks[i], 'module.bert.encoder.blocks.%d' % i)
-        for i in range(4):
-            vit_block(w.tag_blocks[i], 'module.bert.encoder.tag_blocks.%d' % i)
-        w.pooler_w, w.pooler_b = P(self.wb('pooler')), P(vec('module.bert.pooler.dense.bias'))
-
-        def padded_bias(key):       # the master chunk behind a 30522-vector is zero-padded to 30720 >= VOCAB_PAD
-            o = self.off[key]
-            return self.P[o:o + L.VOCAB_PAD]
-
-        def lm_head(dst, pre, tname, dname):
-            dst.dense_w, dst.dense_b = P(self.wb(tname)), P(vec(pre + '.predictions.transform.dense.bias'))
-            dst.ln_g = P(vec(pre + '.predictions.transform.LayerNorm.weight'))
-            dst.ln_b = P(vec(pre + '.predictions.transform.LayerNorm.bias'))
-            dst.dec_w, dst.dec_b = P(self.wb(dname)), P(padded_bias(pre + '.predictions.bias'))
-        lm_head(w.tag_logit, 'module.bert.tag_logit', 'tag.t', 'tag.dec')
-        lm_head(w.cls, 'module.cls', 'cls.t', 'cls.dec')
-        e = 'module.bert.embeddings'
-        w.word_emb, w.pos_emb, w.type_emb = P(self.wb('word')), P(self.wb('pos')), P(self.wb('type'))
-        w.emb_ln_g, w.emb_ln_b = P(vec(e + '.LayerNorm.weight')), P(vec(e + '.LayerNorm.bias'))
-        for i in range(4):
-            pre, d = 'module.bert.decoder.layer.%d' % i, w.dec[i]
-            d.qkv_w, d.qkv_b = P(self.wb(pre + '.qkv')), P(self.qkv_bias(pre))
-            d.ao_w, d.ao_b = P(self.wb(pre + '.ao')), P(vec(pre + '.attention.output.dense.bias'))
-            d.ao_g, d.ao_beta = P(vec(pre + '.attention.output.LayerNorm.weight')), P(vec(pre + '.attention.output.LayerNorm.bias'))
-            d.i_w, d.i_b = P(self.wb(pre + '.i')), P(vec(pre + '.intermediate.dense.bias'))
-            d.o_w, d.o_b = P(self.wb(pre + '.o')), P(vec(pre + '.output.dense.bias'))
-            d.o_g, d.o_beta = P(vec(pre + '.output.LayerNorm.weight')), P(vec(pre + '.output.LayerNorm.bias'))
-        if m._engine is None:
-            h = C.c_void_p()
-            check(lib.vitcap_engine_create(C.byref(h)), 'engine_create')
-            m._engine = h
-        check(lib.vitcap_engine_bind_weights(m._engine, C.byref(w)), 'bind_weights')
-        m._packed = (w, [self], self.dev)
-        return m
+        def buffer(f):
+            if f.optional:
+                return None
+            if f.kind == 'mat':
+                return self.wb(f.name)
+            # q|k|v biases are contiguous in the flat layout; the master chunk behind a 30522-vector is zero-padded to 30720 >= VOCAB_PAD
+            o = self.off[f.keys[0]]
+            return self.P[o:o + (f.pad or sum(int(torch.Size(self.shape[k]).numel()) for k in f.keys))]
+        return self.model.bind_weights(buffer, [self], self.dev)
 
     def wb(self, name):
         return self._gemm_w[name][0]
@@ -510,17 +487,50 @@ class TrainEngine(object):
     def vec(self, k):
         return self.p(k).view(-1)
 
-    def qkv_bias(self, pre):      # decoder q|k|v biases are contiguous in the flat layout
-        o = self.off[pre + '.attention.self.query.bias']
-        return self.P[o:o + 2304]
+    # ------------------------------------------------------------------ parameters of the step, bound once
+    def _bind_layers(self):
+        """One record per layer with the views the step reads: P, G and the bf16 operand pairs are allocated once and refresh_weights
+        rewrites the pairs in place, so the views stay valid for the life of the engine.  Checkpoint keys are spelled here and in
+        W.weights_table() only; the step (everything from _fb_gen down) reads blk.fc1.w, blk.fc1.gb, lay.ao_n.g ..."""
+        def lin(name, key, rows=None):
+            """Dense layer: w = bf16 W[N][K], wt = W^T, b = fp32 bias, gw / gb = their gradients.  rows: N of a matrix that spans
+            several checkpoint tensors (decoder q|k|v, contiguous in the flat layout)."""
+            w = self.wb(name)
+            N, o, ob = rows or self.shape[key + '.weight'][0], self.off[key + '.weight'], self.off[key + '.bias']
+            K = w.shape[1]
+            return _Rec(w=w, wt=self.wt(name), b=self.P[ob:ob + N], gw=self.G[o:o + N * K].view(N, K), gb=self.G[ob:ob + N])
 
-    def qkv_bias_grad(self, pre):
-        o = self.off[pre + '.attention.self.query.bias']
-        return self.G[o:o + 2304]
+        def norm(key):
+            return _Rec(g=self.vec(key + '.weight'), b=self.vec(key + '.bias'), gg=self.g(key + '.weight').view(-1), gb=self.g(key + '.bias').view(-1))
 
-    def qkv_w_grad(self, pre):
-        o = self.off[pre + '.attention.self.query.weight']
-        return self.G[o:o + 2304 * 768].view(2304, 768)
+        def vit(pre):
+            return _Rec(n1=norm(pre + '.norm1'), qkv=lin(pre + '.qkv', pre + '.attn.qkv'), proj=lin(pre + '.proj', pre + '.attn.proj'),
+                        n2=norm(pre + '.norm2'), fc1=lin(pre + '.fc1', pre + '.mlp.fc1'), fc2=lin(pre + '.fc2', pre + '.mlp.fc2'))
+
+        def bert(pre):
+            return _Rec(qkv=lin(pre + '.qkv', pre + '.attention.self.query', rows=2304), ao=lin(pre + '.ao', pre + '.attention.output.dense'),
+                        ao_n=norm(pre + '.attention.output.LayerNorm'), i=lin(pre + '.i', pre + '.intermediate.dense'),
+                        o=lin(pre + '.o', pre + '.output.dense'), o_n=norm(pre + '.output.LayerNorm'))
+
+        def head(pre, tname, dname, dkey):
+            """LM head: t = transform dense, n = its LayerNorm, dec = decoder (bias: the 30522 checkpoint values, unpadded)."""
+            dec = _Rec(w=self.wb(dname), wt=self.wt(dname), b=self.vec(pre + '.bias'), gw=self.g(dkey), gb=self.g(pre + '.bias'))
+            return _Rec(t=lin(tname, pre + '.transform.dense'), n=norm(pre + '.transform.LayerNorm'), dec=dec)
+
+        self.blocks = [vit('module.bert.encoder.blocks.%d' % i) for i in range(12)]
+        self.tag_blocks = [vit('module.bert.encoder.tag_blocks.%d' % i) for i in range(4)]
+        self.dec = [bert('module.bert.decoder.layer.%d' % i) for i in range(4)]
+        ie, e = 'image_encoder.module.', 'module.bert.embeddings'
+        self.patch = lin('patch', ie + 'patch_embed.proj')
+        self.pos_embed = _Rec(p=self.p(ie + 'pos_embed').view(NV, 768), g=self.g(ie + 'pos_embed').view(NV, 768))
+        self.cls_token = _Rec(p=self.vec(ie + 'cls_token'), g=self.g(ie + 'cls_token').view(-1))
+        self.emb = _Rec(word=self.wb('word'), pos=self.wb('pos'), type=self.wb('type'), n=norm(e + '.LayerNorm'),
+                        gword=self.g(e + '.word_embeddings.weight'), gpos=self.g(e + '.position_embeddings.weight'),
+                        gtype=self.g(e + '.token_type_embeddings.weight'))
+        self.pooler = lin('pooler', 'module.bert.pooler.dense')
+        self.tag_head = head('module.bert.tag_logit.predictions', 'tag.t', 'tag.dec', 'module.bert.tag_logit.predictions.decoder.weight')
+        # the (tied) embedding gradient: the LM head's decoder is its first writer
+        self.cls_head = head('module.cls.predictions', 'cls.t', 'cls.dec', W.TIED_SRC if self.model.tie_weights else W.TIED_DST)
 
     # ------------------------------------------------------------------ helpers
     def _wgrad_tn(self, dy, x, gview, bias_grad):
@@ -534,43 +544,21 @@ class TrainEngine(object):
         S = max(1, min(stages, 256 // tiles))
         if S == 1:
             ops.gemm_tn(dy, x, 1, slabs=gview.view(1, N, Kin))
-        elif _TN_SUM and gview.is_contiguous():
-            ops.gemm_tn_sum(dy, x, S, gview)                     # the splits add themselves up inside the launch (round 5)
         else:
             ops.reduce_slabs(ops.gemm_tn(dy, x, S), gview)
         if bias_grad is not None:
             ops.colsum_bf16(dy, bias_grad)
 
-    def _wgrad(self, dyT, xT, gview, accumulate=False):
-        """gview[N][K] (+)= dyT[N][Mp] @ xT[K][Mp]^T with split-K sized to fill the chip."""
-        N, Kin = dyT.shape[0], xT.shape[0]
-        tiles = ((N + 127) // 128) * ((Kin + 127) // 128)
-        nk = dyT.shape[1] // 64
-        S = max(1, min(32, nk, (640 + tiles - 1) // tiles))
-        if S == 1:
-            if accumulate:
-                tmp = ops.gemm_ex(dyT, xT, out_dtype=torch.float32)
-                ops.reduce_slabs(tmp.view(1, N, Kin), gview, accumulate=True)
-            else:
-                ops.gemm_ex(dyT, xT, out=gview)
-            return
-        slabs = ops.gemm_ex(dyT, xT, split_k=S)
-        ops.reduce_slabs(slabs, gview, accumulate=accumulate)
-
-    def _dgrad_gelu(self, dy, wt, z, bias_grad):
-        """dz = (dy @ W) * gelu'(z) (bf16) with the bias gradient of the layer dz is the output gradient of: added by the GEMM's
-        own epilogue where the 256x256 kernel runs (M >= 2048), by a separate pass over dz otherwise.  Returns (dz, pending) --
+    def _dgrad_gelu(self, dy, wt, z, bias_grad, fused):
+        """dz = (dy @ W) * gelu'(z) (bf16) with the bias gradient of the layer dz is the output gradient of: with `fused`, added by the
+        GEMM's own epilogue where the 256x256 kernel runs (M >= 2048); by a separate pass over dz otherwise.  Returns (dz, pending) --
         pending is the bias gradient still to be added by _wgrad_tn, or None."""
-        if _FUSE_BIAS and dy.shape[0] >= 2048:
+        if fused and dy.shape[0] >= 2048:
             return ops.gemm_ex(dy, wt, aux=z, colsum=bias_grad), None
         return ops.gemm_ex(dy, wt, aux=z), bias_grad
 
-    def _ln_bwd(self, x, dy, gkey, bkey, eps, dres=None, dxb_colsum=None):
-        dxf, dxb = ops.layernorm_bwd(x, dy, self.vec(gkey), eps, self.g(gkey).view(-1), self.g(bkey).view(-1), dres=dres,
-                                     dxb_colsum=dxb_colsum if _FUSE_BIAS else None)
-        if dxb_colsum is not None and not _FUSE_BIAS:
-            ops.colsum_bf16(dxb, dxb_colsum)
-        return dxf, dxb
+    def _ln_bwd(self, x, dy, nrm, eps, dres=None, dxb_colsum=None):
+        return ops.layernorm_bwd(x, dy, nrm.g, eps, nrm.gg, nrm.gb, dres=dres, dxb_colsum=dxb_colsum)
 
     # ------------------------------------------------------------------ forward + backward
     def forward_backward(self, batch):
@@ -600,413 +588,371 @@ class TrainEngine(object):
         generated positions, i.e. ScstRewardCriterion with sample_weight = (reward - baseline) / B.  The 19 per-step
         forwards the reference differentiates through (one full re-encode per generated token) collapse into ONE pass:
         the decoder runs on [578 visual | 20 token rows | 19 [MASK] probe rows], probe j sees tokens 0..j."""
-        dev = self.dev
-        if capture:       # the device-side comparison only (read by flush_text_check every 50 steps, outside the graph)
-            ok = train_text_inputs_ok(batch)
-            if ok is not None:
-                if getattr(self, '_text_bad', None) is None:
-                    self._text_bad = torch.zeros((), dtype=torch.int32, device=ok.device)
-                self._text_bad += (~ok).to(torch.int32)
-        else:
-            self.check_text_inputs(batch)
-        seed_step = 0 if capture else self.step_no
-        img = batch['image']
-        Be = img.shape[0]                       # images the encoder runs on
-        KS = int(batch.get('seq_per_image', 1))   # decoder sequences per image (self-critical step: the samples of an image
-        B = Be * KS                             # share its encoder pass; their visual-row gradients are summed before its backward)
-        scst = 'sample_ids' in batch
-        TP = (T - 1) if scst else 0          # probe rows per sequence
-        TT = T + TP                          # text rows per sequence
-        LR = SV + TT                         # decoder rows per image (shadows the module constant on purpose)
-        M, Md = Be * NV, B * LR
+        self.check_text_inputs(batch, host_read=not capture)
+        st = _Step(self, batch, capture)
         self.G.zero_()
         self.loss_buf.zero_()
-        ie = 'image_encoder.module.'
-        # ================= forward: patch embed
-        patches = ops.patch_gather(img)
-        x = torch.empty(M, 768, device=dev)
-        pos = self.p(ie + 'pos_embed').view(NV, 768)
-        ops.gemm_bias_act(patches, self.wb('patch'), self.vec(ie + 'patch_embed.proj.bias'), residual=pos[1:], out=x,
+        self._patch_fwd(st)
+        self._encoder_fwd(st)
+        self._tag_head_fwd(st)
+        self._decoder_fwd(st)
+        if st.scst:
+            self._loss_rows_scst(st)
+        else:
+            self._loss_rows_masked(st)
+        self._lm_head(st)
+        yield 'cls'
+        yield from self._decoder_bwd(st)
+        self._embedding_bwd(st)
+        yield 'emb'
+        yield from self._encoder_bwd(st)
+        self._patch_bwd(st)
+        yield 'patch'
+        return self.loss_buf[0], self.loss_buf[1]
+
+    # ---- ViT block.  cls_only: only row 0 (CLS) of the block's output is ever read -- the last tag block: tag_hidden feeds the pooler
+    # and the joint sequence through tag_hidden[:, 0] alone (modeling_bert.py:1424, 1493).  LN1 and the qkv projection run on every
+    # row (the CLS query attends all keys, and K/V carry gradient to every row); attention, proj, LN2 and the MLP run for the Be CLS
+    # rows, and the block returns / takes (Be,768).
+    def _vit_fwd(self, st, blk, xin, cls_only=False):
+        h1, _ = ops.layernorm(xin, blk.n1.g, blk.n1.b, 1e-6)
+        qkv = ops.gemm_bias_act(h1, blk.qkv.w, blk.qkv.b)
+        ao, lse = ops.attn_dense_train(qkv, st.Be, NV, q_range=(0, 1) if cls_only else None)
+        if cls_only:
+            ao_r = ao.view(st.Be, NV, 768)[:, 0].contiguous()
+            xin_r = xin.view(st.Be, NV, 768)[:, 0].contiguous()
+        else:
+            ao_r, xin_r = ao, xin
+        R = ao_r.shape[0]
+        xmid = torch.empty(R, 768, device=self.dev)
+        ops.gemm_bias_act(ao_r, blk.proj.w, blk.proj.b, residual=xin_r, out=xmid)
+        h2, _ = ops.layernorm(xmid, blk.n2.g, blk.n2.b, 1e-6)
+        z = torch.empty(R, 3072, device=self.dev, dtype=torch.bfloat16)
+        g = ops.gemm_ex(h2, blk.fc1.w, bias=blk.fc1.b, act=L.ACT_GELU_ERF, zout=z)
+        xout = torch.empty(R, 768, device=self.dev)
+        ops.gemm_bias_act(g, blk.fc2.w, blk.fc2.b, residual=xmid, out=xout)
+        st.saved[blk] = (xin, h1, qkv, ao, lse, xmid, h2, z, g, ao_r)
+        return xout
+
+    def _vit_bwd(self, st, blk, dxo, cls_only=False):
+        """dxo = gradient of the block's output (cls_only: of its CLS rows); returns the gradient of the block's input on all rows (the
+        CLS query's attention spreads it over every row through K and V).
+        The bias gradients of fc2 / fc1 / proj are column sums of a backward operand.  On all rows each is added by the kernel that
+        WRITES that operand (cast, GEMM epilogue at M >= 2048, LayerNorm backward); on the CLS rows by _wgrad_tn's own pass."""
+        Be, M = st.Be, st.M
+        xin, h1, qkv, ao, lse, xmid, h2, z, g, ao_r = st.saved.pop(blk)
+        fused = not cls_only
+
+        def pending(gb):        # the bias gradient _wgrad_tn still has to add
+            return None if fused else gb
+        dxb = ops.cast_bf16_colsum(dxo, blk.fc2.gb) if fused else ops.cast_bf16(dxo)
+        self._wgrad_tn(dxb, g, blk.fc2.gw, pending(blk.fc2.gb))
+        dz, pend = self._dgrad_gelu(dxb, blk.fc2.wt, z, blk.fc1.gb, fused)
+        self._wgrad_tn(dz, h2, blk.fc1.gw, pend)
+        dh2 = ops.gemm_ex(dz, blk.fc1.wt)
+        dmf, dmb = self._ln_bwd(xmid, dh2, blk.n2, 1e-6, dres=dxo, dxb_colsum=blk.proj.gb if fused else None)
+        self._wgrad_tn(dmb, ao_r, blk.proj.gw, pending(blk.proj.gb))
+        dao = ops.gemm_ex(dmb, blk.proj.wt)
+        if cls_only:
+            dao_all = torch.zeros(Be, NV, 768, device=self.dev, dtype=torch.bfloat16)
+            dao_all[:, 0] = dao
+            dao = dao_all.view(M, 768)
+        dqkv = ops.attn_dense_bwd(qkv, ao, dao, lse, Be, NV, q_range=(0, 1) if cls_only else None)
+        self._wgrad_tn(dqkv, h1, blk.qkv.gw, blk.qkv.gb)
+        dh1 = ops.gemm_ex(dqkv, blk.qkv.wt)
+        if cls_only:
+            res = torch.zeros(Be, NV, 768, device=self.dev)
+            res[:, 0] = dmf
+            dmf = res.view(M, 768)
+        dif, _ = self._ln_bwd(xin, dh1, blk.n1, 1e-6, dres=dmf)
+        return dif
+
+    # ---- decoder layer.  text_only: only the text rows' outputs are read -- the last layer (LM head on the masked / probe rows); the
+    # visual rows' K/V are still needed (and carry gradient), their attention / output / MLP are not: the attention runs for the query
+    # blocks from QLO on, everything behind it on the (B*TT) text rows, and the layer returns / takes the gradient of those rows.
+    def _text_rows(self, st, x):
+        return x.view(st.B, st.LR, 768)[:, SV:].reshape(st.B * st.TT, 768).contiguous()
+
+    def _all_rows(self, st, x_text, dtype=torch.float32):
+        """Text rows back at their place among all decoder rows, zeros on the visual rows."""
+        x = torch.zeros(st.B, st.LR, 768, device=self.dev, dtype=dtype)
+        x[:, SV:] = x_text.view(st.B, st.TT, 768)
+        return x.view(st.Md, 768)
+
+    def _dense_residual(self, st, a, lin, res, rows, seed):
+        """BertSelfOutput / BertOutput up to their LayerNorm: dropout(dense(a)) + res.  rows = (rows per sequence, first row): where
+        the rows of `a` sit in a sequence, for the dropout's counter."""
+        out = torch.empty(a.shape[0], 768, device=self.dev)
+        if st.ph > 0:
+            ops.gemm_bias_act(a, lin.w, lin.b, out=out)
+            ops.hidden_dropout(out, res, rows[0], rows[1], seed, st.ph, out=out)
+        else:
+            ops.gemm_bias_act(a, lin.w, lin.b, residual=res, out=out)
+        return out
+
+    def _dense_residual_bwd(self, st, x, dy, nrm, gb, rows, seed, fused):
+        """Backward of LayerNorm(dropout(dense) + res) down to the dense output: (fp32 gradient of the LayerNorm input = what the
+        residual branch sees, bf16 gradient of the dense output = the masked one under dropout, bias gradient still to be added by
+        _wgrad_tn).  fused: the kernel that writes the bf16 operand adds its column sums to gb (the LayerNorm backward, or the cast
+        of the masked gradient); otherwise _wgrad_tn does."""
+        if st.ph > 0:
+            dxf, _ = self._ln_bwd(x, dy, nrm, 1e-12)
+            masked = ops.hidden_dropout(dxf, None, rows[0], rows[1], seed, st.ph)
+            dxb = ops.cast_bf16_colsum(masked, gb) if fused else ops.cast_bf16(masked)
+        else:
+            dxf, dxb = self._ln_bwd(x, dy, nrm, 1e-12, dxb_colsum=gb if fused else None)
+        return dxf, dxb, (None if fused else gb)
+
+    def _dec_attn_args(self, st, l, text_only):
+        return dict(p_drop=st.pd, drop_seed=st.dseed[l], causal_from=SV, mask_from=SV + T if st.scst else 0,
+                    q_range=(QLO, st.LR) if text_only else None)
+
+    def _dec_fwd(self, st, l, xd, text_only=False):
+        lay = self.dec[l]
+        xb = ops.cast_bf16(xd)
+        qkv = ops.gemm_bias_act(xb, lay.qkv.w, lay.qkv.b)
+        # visual rows attend visual rows; caption row q attends all visual rows and caption rows <= q (one kernel)
+        ctx, lse = ops.attn_dense_train(qkv, st.B, st.LR, **self._dec_attn_args(st, l, text_only))
+        if text_only:
+            ctx_r, xd_r, rows = self._text_rows(st, ctx), self._text_rows(st, xd), (st.TT, SV)
+        else:
+            ctx_r, xd_r, rows = ctx, xd, (st.LR, 0)
+        t1 = self._dense_residual(st, ctx_r, lay.ao, xd_r, rows, st.hseed(l, 1))
+        ab, af = ops.layernorm(t1, lay.ao_n.g, lay.ao_n.b, 1e-12, want_f32=True)
+        z = torch.empty(t1.shape[0], 3072, device=self.dev, dtype=torch.bfloat16)
+        it = ops.gemm_ex(ab, lay.i.w, bias=lay.i.b, act=L.ACT_GELU_ERF, zout=z)
+        t2 = self._dense_residual(st, it, lay.o, af, rows, st.hseed(l, 2))
+        _, yf = ops.layernorm(t2, lay.o_n.g, lay.o_n.b, 1e-12, want_bf16=False, want_f32=True)
+        st.dsaved.append((xb, qkv, ctx, lse, t1, ab, af, z, it, t2, ctx_r))
+        return yf
+
+    def _dec_bwd(self, st, l, dy, text_only=False):
+        """dy = gradient of the layer's output (text_only: of its text rows); returns the gradient of its input on all rows.  Bias
+        gradients as in _vit_bwd: added by the producing kernel on all rows, by _wgrad_tn on the text rows."""
+        lay = self.dec[l]
+        xb, qkv, ctx, lse, t1, ab, af, z, it, t2, ctx_r = st.dsaved[l]
+        fused = not text_only
+        rows = (st.TT, SV) if text_only else (st.LR, 0)
+        dt2f, dt2b, pend = self._dense_residual_bwd(st, t2, dy, lay.o_n, lay.o.gb, rows, st.hseed(l, 2), fused)
+        self._wgrad_tn(dt2b, it, lay.o.gw, pend)
+        dz, pend = self._dgrad_gelu(dt2b, lay.o.wt, z, lay.i.gb, fused)       # [rows,3072] bf16
+        self._wgrad_tn(dz, ab, lay.i.gw, pend)
+        da = ops.gemm_ex(dz, lay.i.wt, residual=dt2f, out_dtype=torch.float32)
+        dt1f, dt1b, pend = self._dense_residual_bwd(st, t1, da, lay.ao_n, lay.ao.gb, rows, st.hseed(l, 1), fused)
+        self._wgrad_tn(dt1b, ctx_r, lay.ao.gw, pend)
+        dctx = ops.gemm_ex(dt1b, lay.ao.wt)
+        if text_only:
+            dctx = self._all_rows(st, dctx, torch.bfloat16)
+        dqkv = ops.attn_dense_bwd(qkv, ctx, dctx, lse, st.B, st.LR, **self._dec_attn_args(st, l, text_only))
+        self._wgrad_tn(dqkv, xb, lay.qkv.gw, lay.qkv.gb)
+        res = self._all_rows(st, dt1f) if text_only else dt1f     # the residual path reaches the layer input on the rows that ran
+        return ops.gemm_ex(dqkv, lay.qkv.wt, residual=res, out_dtype=torch.float32)
+
+    # ---- phases of the step, in order
+    def _patch_fwd(self, st):
+        st.patches = ops.patch_gather(st.batch['image'])
+        st.x = torch.empty(st.M, 768, device=self.dev)
+        pos = self.pos_embed.p
+        ops.gemm_bias_act(st.patches, self.patch.w, self.patch.b, residual=pos[1:], out=st.x,
                           row_group=576, out_group_rows=NV, out_row_off=1, res_periodic=1)
-        check(lib.vitcap_cls_rows(_p(self.vec(ie + 'cls_token')), _p(pos), _p(x), Be, NV, _s()), 'cls_rows')
-        # ================= forward: 12 blocks + 4 tag blocks, activations kept
-        saved = {}
+        check(lib.vitcap_cls_rows(_p(self.cls_token.p), _p(pos), _p(st.x), st.Be, NV, _s()), 'cls_rows')
 
-        def block_fwd(pre, xin):
-            h1, _ = ops.layernorm(xin, self.vec(pre + '.norm1.weight'), self.vec(pre + '.norm1.bias'), 1e-6)
-            qkv = ops.gemm_bias_act(h1, self.wb(pre + '.qkv'), self.vec(pre + '.attn.qkv.bias'))
-            ao, lse = ops.attn_dense_train(qkv, Be, NV)
-            xmid = torch.empty(M, 768, device=dev)
-            ops.gemm_bias_act(ao, self.wb(pre + '.proj'), self.vec(pre + '.attn.proj.bias'), residual=xin, out=xmid)
-            h2, _ = ops.layernorm(xmid, self.vec(pre + '.norm2.weight'), self.vec(pre + '.norm2.bias'), 1e-6)
-            z = torch.empty(M, 3072, device=dev, dtype=torch.bfloat16)
-            g = ops.gemm_ex(h2, self.wb(pre + '.fc1'), bias=self.vec(pre + '.mlp.fc1.bias'), act=L.ACT_GELU_ERF, zout=z)
-            xout = torch.empty(M, 768, device=dev)
-            ops.gemm_bias_act(g, self.wb(pre + '.fc2'), self.vec(pre + '.mlp.fc2.bias'), residual=xmid, out=xout)
-            saved[pre] = (xin, h1, qkv, ao, lse, xmid, h2, z, g)
-            return xout
-
-        def block_fwd_cls(pre, xin):
-            """The same block when only row 0 (CLS) of its output is ever read -- the last tag block: tag_hidden feeds the pooler
-            and the joint sequence through tag_hidden[:, 0] alone (modeling_bert.py:1424, 1493).  LN1 and the qkv projection
-            run on every row (the CLS query attends all keys, and K/V carry gradient to every row); attention, proj, LN2 and
-            the MLP run for the B CLS rows.  Returns (B,768)."""
-            h1, _ = ops.layernorm(xin, self.vec(pre + '.norm1.weight'), self.vec(pre + '.norm1.bias'), 1e-6)
-            qkv = ops.gemm_bias_act(h1, self.wb(pre + '.qkv'), self.vec(pre + '.attn.qkv.bias'))
-            ao, lse = ops.attn_dense_train(qkv, Be, NV, q_range=(0, 1))
-            ao_c = ao.view(Be, NV, 768)[:, 0].contiguous()
-            xin_c = xin.view(Be, NV, 768)[:, 0].contiguous()
-            xmid_c = torch.empty(Be, 768, device=dev)
-            ops.gemm_bias_act(ao_c, self.wb(pre + '.proj'), self.vec(pre + '.attn.proj.bias'), residual=xin_c, out=xmid_c)
-            h2_c, _ = ops.layernorm(xmid_c, self.vec(pre + '.norm2.weight'), self.vec(pre + '.norm2.bias'), 1e-6)
-            z_c = torch.empty(Be, 3072, device=dev, dtype=torch.bfloat16)
-            g_c = ops.gemm_ex(h2_c, self.wb(pre + '.fc1'), bias=self.vec(pre + '.mlp.fc1.bias'), act=L.ACT_GELU_ERF, zout=z_c)
-            xout_c = torch.empty(Be, 768, device=dev)
-            ops.gemm_bias_act(g_c, self.wb(pre + '.fc2'), self.vec(pre + '.mlp.fc2.bias'), residual=xmid_c, out=xout_c)
-            saved[pre] = (xin, h1, qkv, ao, lse, xmid_c, h2_c, z_c, g_c, ao_c)
-            return xout_c
-
-        prune = self.prune_dead_rows
-        xt = None
+    def _encoder_fwd(self, st):
+        """12 blocks + 4 tag blocks (forking behind block 7), activations kept.  st.x: hidden states; st.xt_cls: CLS rows of the tag branch."""
+        x, xt = st.x, None
         for i in range(12):
             if i == 8:
                 xt = x
-            x = block_fwd('module.bert.encoder.blocks.%d' % i, x)
+            x = self._vit_fwd(st, self.blocks[i], x)
         for i in range(3):
-            xt = block_fwd('module.bert.encoder.tag_blocks.%d' % i, xt)
-        if prune:
-            xt_cls = block_fwd_cls('module.bert.encoder.tag_blocks.3', xt)
+            xt = self._vit_fwd(st, self.tag_blocks[i], xt)
+        if st.prune:
+            st.xt_cls = self._vit_fwd(st, self.tag_blocks[3], xt, cls_only=True)
         else:
-            xt_cls = block_fwd('module.bert.encoder.tag_blocks.3', xt).view(Be, NV, 768)[:, 0].contiguous()
-        # ================= forward: tag head (value of tag_loss only)
-        tg = 'module.bert.tag_logit.predictions'
-        pin = ops.cast_bf16(xt_cls)
-        pooled = ops.gemm_bias_act(pin, self.wb('pooler'), self.vec('module.bert.pooler.dense.bias'), act=L.ACT_TANH)
-        tgf = ops.gemm_bias_act(pooled, self.wb('tag.t'), self.vec(tg + '.transform.dense.bias'), act=L.ACT_GELU_ERF,
-                                out_dtype=torch.float32)
-        tgb, _ = ops.layernorm(tgf, self.vec(tg + '.transform.LayerNorm.weight'), self.vec(tg + '.transform.LayerNorm.bias'), 1e-12)
+            st.xt_cls = self._vit_fwd(st, self.tag_blocks[3], xt).view(st.Be, NV, 768)[:, 0].contiguous()
+        st.x = x
+
+    def _tag_head_fwd(self, st):
+        """Value of tag_loss only (reported, never back-propagated; the self-critical step has no labels)."""
+        dev, hd, batch = self.dev, self.tag_head, st.batch
+        pin = ops.cast_bf16(st.xt_cls)
+        pooled = ops.gemm_bias_act(pin, self.pooler.w, self.pooler.b, act=L.ACT_TANH)
+        tgf = ops.gemm_bias_act(pooled, hd.t.w, hd.t.b, act=L.ACT_GELU_ERF, out_dtype=torch.float32)
+        tgb, _ = ops.layernorm(tgf, hd.n.g, hd.n.b, 1e-12)
         tbias = torch.zeros(L.VOCAB_PAD, device=dev)
-        tbias[:L.VOCAB] = self.vec(tg + '.bias')
-        tag_logits = ops.gemm_bias_act(tgb, self.wb('tag.dec'), tbias, out_dtype=torch.float32)
-        if 'label' in batch:                 # reported only (never back-propagated); the self-critical step has no labels
+        tbias[:L.VOCAB] = hd.dec.b
+        tag_logits = ops.gemm_bias_act(tgb, hd.dec.w, tbias, out_dtype=torch.float32)
+        if 'label' in batch:
             label = batch['label'].to(dev).contiguous()
             if self.tag_loss == 'focal':       # FocalLossWithLogitsNegLoss(alpha .5, gamma 1).sum(), modeling_bert.py:713-715, 789-791
-                check(lib.vitcap_focal_loss_sum(_p(tag_logits), L.VOCAB_PAD, L.VOCAB, _p(label), 0.5, _p(self.loss_buf[1:]), Be, _s()),
+                check(lib.vitcap_focal_loss_sum(_p(tag_logits), L.VOCAB_PAD, L.VOCAB, _p(label), 0.5, _p(self.loss_buf[1:]), st.Be, _s()),
                       'focal')
             else:                              # torch.nn.BCEWithLogitsLoss(), modeling_bert.py:716-717
-                check(lib.vitcap_bce_logits_mean(_p(tag_logits), L.VOCAB_PAD, L.VOCAB, _p(label), _p(self.loss_buf[1:]), Be, _s()), 'bce')
-        # ================= forward: decoder on [578 visual | 20 caption] rows per image
-        e = 'module.bert.embeddings'
-        if scst:
-            sid = batch['sample_ids'].to(dev).view(B, T)
-            ids20 = torch.cat([sid, torch.full((B, TP), 103, dtype=torch.int64, device=dev)], 1).contiguous()   # tokens | [MASK] x19
-        else:
-            ids20 = batch['input_ids'][:, :T].to(dev).contiguous()
-        pre_emb = torch.empty(B * TT, 768, device=dev)
-        xtext = torch.empty(B * TT, 768, device=dev)
-        check(lib.vitcap_embed_rows(_p(ids20), TT, _p(self.wb('word')), _p(self.wb('pos')), _p(self.wb('type')),
-                                    _p(self.vec(e + '.LayerNorm.weight')), _p(self.vec(e + '.LayerNorm.bias')), 1e-12,
-                                    _p(pre_emb), _p(xtext), None, B * TT, T if scst else 0, _s()), 'embed_rows')
-        ph = self.hidden_dropout
+                check(lib.vitcap_bce_logits_mean(_p(tag_logits), L.VOCAB_PAD, L.VOCAB, _p(label), _p(self.loss_buf[1:]), st.Be, _s()), 'bce')
 
-        def hseed(l, site):            # per step, per layer (4 = embeddings), per site (1 attention.output, 2 output, 3 embeddings)
-            return mix32(mix32(mix32(self.dropout_seed, seed_step), 16 + l), site)
-        if ph > 0:                     # BertEmbeddings: dropout(LayerNorm(...)) on the text rows (device rows SV .. SV + TT - 1 of a sequence)
-            ops.hidden_dropout(xtext, None, TT, SV, hseed(4, 3), ph, out=xtext)
-        dx = torch.empty(B, LR, 768, device=dev)
-        dx[:, 0] = xt_cls if KS == 1 else xt_cls.repeat_interleave(KS, 0)
-        dx[:, 1:SV] = x.view(Be, NV, 768) if KS == 1 else x.view(Be, NV, 768).repeat_interleave(KS, 0)
-        dx[:, SV:] = xtext.view(B, TT, 768)
-        xd = dx.view(Md, 768)
-        dsaved = []
-        pd = self.attn_dropout
-        dseed = [mix32(mix32(self.dropout_seed, seed_step), l) for l in range(4)]      # per step, per layer
-        QLO = (SV // 128) * 128                       # first 128-row query block that holds text rows
-        for l in range(4):
-            pre = 'module.bert.decoder.layer.%d' % l
-            xb = ops.cast_bf16(xd)
-            qkv = ops.gemm_bias_act(xb, self.wb(pre + '.qkv'), self.qkv_bias(pre))
-            if l == 3 and prune:
-                # Last layer: only the text rows' outputs are read (LM head on the masked / probe rows); the visual rows' K/V
-                # are still needed (and carry gradient), their attention / output / MLP are not.  Text rows only from here.
-                ctx, lse = ops.attn_dense_train(qkv, B, LR, p_drop=pd, drop_seed=dseed[l], causal_from=SV,
-                                                mask_from=SV + T if scst else 0, q_range=(QLO, LR))
-                ctx_t = ctx.view(B, LR, 768)[:, SV:].reshape(B * TT, 768).contiguous()
-                xd_t = xd.view(B, LR, 768)[:, SV:].reshape(B * TT, 768).contiguous()
-                t1 = torch.empty(B * TT, 768, device=dev)
-                if ph > 0:      # BertSelfOutput: LayerNorm(dropout(dense(ctx)) + x)
-                    ops.gemm_bias_act(ctx_t, self.wb(pre + '.ao'), self.vec(pre + '.attention.output.dense.bias'), out=t1)
-                    ops.hidden_dropout(t1, xd_t, TT, SV, hseed(l, 1), ph, out=t1)
-                else:
-                    ops.gemm_bias_act(ctx_t, self.wb(pre + '.ao'), self.vec(pre + '.attention.output.dense.bias'), residual=xd_t, out=t1)
-                ab, af = ops.layernorm(t1, self.vec(pre + '.attention.output.LayerNorm.weight'),
-                                       self.vec(pre + '.attention.output.LayerNorm.bias'), 1e-12, want_f32=True)
-                z = torch.empty(B * TT, 3072, device=dev, dtype=torch.bfloat16)
-                it = ops.gemm_ex(ab, self.wb(pre + '.i'), bias=self.vec(pre + '.intermediate.dense.bias'), act=L.ACT_GELU_ERF, zout=z)
-                t2 = torch.empty(B * TT, 768, device=dev)
-                if ph > 0:      # BertOutput: LayerNorm(dropout(dense(intermediate)) + attention_output)
-                    ops.gemm_bias_act(it, self.wb(pre + '.o'), self.vec(pre + '.output.dense.bias'), out=t2)
-                    ops.hidden_dropout(t2, af, TT, SV, hseed(l, 2), ph, out=t2)
-                else:
-                    ops.gemm_bias_act(it, self.wb(pre + '.o'), self.vec(pre + '.output.dense.bias'), residual=af, out=t2)
-                _, text_out = ops.layernorm(t2, self.vec(pre + '.output.LayerNorm.weight'), self.vec(pre + '.output.LayerNorm.bias'),
-                                            1e-12, want_bf16=False, want_f32=True)
-                dsaved.append((xb, qkv, ctx, lse, t1, ab, af, z, it, t2, ctx_t))
-                break
-            # visual rows attend visual rows; caption row q attends all visual rows and caption rows <= q (one kernel)
-            ctx, lse = ops.attn_dense_train(qkv, B, LR, p_drop=pd, drop_seed=dseed[l], causal_from=SV,
-                                            mask_from=SV + T if scst else 0)
-            t1 = torch.empty(Md, 768, device=dev)
-            if ph > 0:
-                ops.gemm_bias_act(ctx, self.wb(pre + '.ao'), self.vec(pre + '.attention.output.dense.bias'), out=t1)
-                ops.hidden_dropout(t1, xd, LR, 0, hseed(l, 1), ph, out=t1)
-            else:
-                ops.gemm_bias_act(ctx, self.wb(pre + '.ao'), self.vec(pre + '.attention.output.dense.bias'), residual=xd, out=t1)
-            ab, af = ops.layernorm(t1, self.vec(pre + '.attention.output.LayerNorm.weight'),
-                                   self.vec(pre + '.attention.output.LayerNorm.bias'), 1e-12, want_f32=True)
-            z = torch.empty(Md, 3072, device=dev, dtype=torch.bfloat16)
-            it = ops.gemm_ex(ab, self.wb(pre + '.i'), bias=self.vec(pre + '.intermediate.dense.bias'), act=L.ACT_GELU_ERF, zout=z)
-            t2 = torch.empty(Md, 768, device=dev)
-            if ph > 0:
-                ops.gemm_bias_act(it, self.wb(pre + '.o'), self.vec(pre + '.output.dense.bias'), out=t2)
-                ops.hidden_dropout(t2, af, LR, 0, hseed(l, 2), ph, out=t2)
-            else:
-                ops.gemm_bias_act(it, self.wb(pre + '.o'), self.vec(pre + '.output.dense.bias'), residual=af, out=t2)
-            _, yf = ops.layernorm(t2, self.vec(pre + '.output.LayerNorm.weight'), self.vec(pre + '.output.LayerNorm.bias'), 1e-12,
-                                  want_bf16=False, want_f32=True)
-            dsaved.append((xb, qkv, ctx, lse, t1, ab, af, z, it, t2))
-            xd = yf
-        if not prune:
-            text_out = xd.view(B, LR, 768)[:, SV:].reshape(B * TT, 768)
-        # ================= loss on the masked caption positions
-        row_w = None
-        if scst:
-            # probe j (grid column T + j) predicts position j+1; a position counts while the sequence is unfinished, i.e. up
-            # to and including its first [SEP] (modeling_utils.py:853-877); coefficient = weight_b / (#counted positions)
-            tok = sid[:, 1:]
-            ended = ((sid[:, :-1] == 102).cumsum(1) > 0)                     # a [SEP] strictly before this position
-            unf = ~ended
-            mp = torch.zeros(B, TT, dtype=torch.bool, device=dev)
-            mp[:, T:] = unf
-            cnt = unf.sum(1).clamp(min=1).to(torch.float32)
-            wrow = (batch['sample_weight'].to(dev).to(torch.float32) / cnt)[:, None].expand(B, TP)
-            row_w = wrow[unf].contiguous()
-            tgt = tok[unf].contiguous()
-            sel = mp.view(-1).nonzero().view(-1)                              # rows of the (B*TT) text grid
-            n = int(sel.numel())
-            assert int(tgt.numel()) == n, 'sample_ids / unfinished mask disagree'
-            sel_bwd = sel
+    def _decoder_fwd(self, st):
+        """Text embeddings, then the 4 layers on [578 visual | TT text] rows per sequence.  st.text_out: the last layer's text rows."""
+        dev, emb, batch = self.dev, self.emb, st.batch
+        B, TT, TP, KS, Be = st.B, st.TT, st.TP, st.KS, st.Be
+        if st.scst:
+            st.sid = batch['sample_ids'].to(dev).view(B, T)
+            st.ids20 = torch.cat([st.sid, torch.full((B, TP), 103, dtype=torch.int64, device=dev)], 1).contiguous()   # tokens | [MASK] x19
         else:
-            # Static form (no host synchronisation, same shapes every step: graph-capturable).  Slot (b, j) = the j-th masked position of
-            # sample b; masked_ids[b, j] == 0 marks an unused slot (a caption with fewer than 3 masked tokens).  The used slots are moved
-            # to the front in their original order (stable sort), so with every slot used -- the synthetic batches -- rows, targets and
-            # weights are exactly what `nonzero()` / boolean indexing produced; an unused slot becomes a row with weight 0 (zero loss,
-            # zero gradient rows: exact zeros in every sum) whose gradient lands in a dummy row behind the text grid.
-            mpos = batch['masked_pos'][:, :T].to(dev) != 0                       # (B, T)
-            mids = batch['masked_ids'].to(dev)                                   # (B, J)
-            J = mids.shape[1]
-            cum = mpos.to(torch.int32).cumsum(1)                                 # 1-based rank of every masked position
-            want = torch.arange(1, J + 1, device=dev, dtype=torch.int32).view(1, J, 1)
-            tpos = ((cum.unsqueeze(1) == want) & mpos.unsqueeze(1)).to(torch.int32).argmax(2)      # (B, J): position of the j-th masked token
-            rows_all = (torch.arange(B, device=dev).view(B, 1) * TT + tpos).view(-1)
-            used = (mids != 0).view(-1)
-            # a batch whose masked_pos and masked_ids disagree is reported like a bad mask (device counter, TrainEngine.flush_text_check)
-            # (counts equal AND the used slots are the leading ones: dataset.py:321-324 pads masked_ids behind the real ids; a zero in
-            # front of a real id would pair targets with the wrong rows -- ADVICE r5)
-            nm = mpos.sum(1, keepdim=True)
-            bad = (nm.view(-1) != (mids != 0).sum(1)).any() | ((mids != 0) != (torch.arange(J, device=dev).view(1, J) < nm)).any()
-            if getattr(self, '_text_bad', None) is None:
-                self._text_bad = torch.zeros((), dtype=torch.int32, device=dev)
-            self._text_bad += bad.to(torch.int32)
-            order = torch.argsort((~used).to(torch.int8), stable=True)
-            used_s = used[order]
-            sel = rows_all[order].contiguous()                                   # forward: any valid row index (weight 0 where unused)
-            sel_bwd = torch.where(used_s, sel, torch.full_like(sel, B * TT))     # backward: unused slots -> the dummy row
-            tgt = mids.view(-1)[order].contiguous()
-            n = B * J
-            row_w = (used_s.to(torch.float32) / used.sum().clamp(min=1).to(torch.float32)).contiguous()     # 1 / #masked tokens: the mean
-        hrows = ops.cast_bf16(text_out.index_select(0, sel).contiguous())
-        c = 'module.cls.predictions'
+            st.ids20 = batch['input_ids'][:, :T].to(dev).contiguous()
+        st.pre_emb = torch.empty(B * TT, 768, device=dev)
+        xtext = torch.empty(B * TT, 768, device=dev)
+        check(lib.vitcap_embed_rows(_p(st.ids20), TT, _p(emb.word), _p(emb.pos), _p(emb.type), _p(emb.n.g), _p(emb.n.b), 1e-12,
+                                    _p(st.pre_emb), _p(xtext), None, B * TT, T if st.scst else 0, _s()), 'embed_rows')
+        if st.ph > 0:                  # BertEmbeddings: dropout(LayerNorm(...)) on the text rows (device rows SV .. SV + TT - 1 of a sequence)
+            ops.hidden_dropout(xtext, None, TT, SV, st.hseed(4, 3), st.ph, out=xtext)
+        dx = torch.empty(B, st.LR, 768, device=dev)
+        dx[:, 0] = st.xt_cls if KS == 1 else st.xt_cls.repeat_interleave(KS, 0)
+        dx[:, 1:SV] = st.x.view(Be, NV, 768) if KS == 1 else st.x.view(Be, NV, 768).repeat_interleave(KS, 0)
+        dx[:, SV:] = xtext.view(B, TT, 768)
+        xd = dx.view(st.Md, 768)
+        for l in range(3):
+            xd = self._dec_fwd(st, l, xd)
+        if st.prune:
+            st.text_out = self._dec_fwd(st, 3, xd, text_only=True)
+        else:
+            st.text_out = self._dec_fwd(st, 3, xd).view(B, st.LR, 768)[:, SV:].reshape(B * TT, 768)
+
+    def _loss_rows_scst(self, st):
+        """Rows of the text grid the loss reads (st.sel), their targets and weights: probe j (grid column T + j) predicts position j+1;
+        a position counts while the sequence is unfinished, i.e. up to and including its first [SEP] (modeling_utils.py:853-877);
+        coefficient = weight_b / (#counted positions)."""
+        dev, B, TT, TP, sid = self.dev, st.B, st.TT, st.TP, st.sid
+        tok = sid[:, 1:]
+        ended = ((sid[:, :-1] == 102).cumsum(1) > 0)                     # a [SEP] strictly before this position
+        unf = ~ended
+        mp = torch.zeros(B, TT, dtype=torch.bool, device=dev)
+        mp[:, T:] = unf
+        cnt = unf.sum(1).clamp(min=1).to(torch.float32)
+        wrow = (st.batch['sample_weight'].to(dev).to(torch.float32) / cnt)[:, None].expand(B, TP)
+        st.row_w = wrow[unf].contiguous()
+        st.tgt = tok[unf].contiguous()
+        st.sel = mp.view(-1).nonzero().view(-1)                              # rows of the (B*TT) text grid
+        st.n = int(st.sel.numel())
+        assert int(st.tgt.numel()) == st.n, 'sample_ids / unfinished mask disagree'
+        st.sel_bwd = st.sel
+
+    def _loss_rows_masked(self, st):
+        """The same for the masked-token loss, in a static form (no host synchronisation, same shapes every step: graph-capturable).
+        Slot (b, j) = the j-th masked position of sample b; masked_ids[b, j] == 0 marks an unused slot (a caption with fewer than 3
+        masked tokens).  The used slots are moved to the front in their original order (stable sort), so with every slot used -- the
+        synthetic batches -- rows, targets and weights are exactly what `nonzero()` / boolean indexing produced; an unused slot becomes
+        a row with weight 0 (zero loss, zero gradient rows: exact zeros in every sum) whose gradient lands in a dummy row behind the
+        text grid."""
+        dev, B, TT, batch = self.dev, st.B, st.TT, st.batch
+        mpos = batch['masked_pos'][:, :T].to(dev) != 0                       # (B, T)
+        mids = batch['masked_ids'].to(dev)                                   # (B, J)
+        J = mids.shape[1]
+        cum = mpos.to(torch.int32).cumsum(1)                                 # 1-based rank of every masked position
+        want = torch.arange(1, J + 1, device=dev, dtype=torch.int32).view(1, J, 1)
+        tpos = ((cum.unsqueeze(1) == want) & mpos.unsqueeze(1)).to(torch.int32).argmax(2)      # (B, J): position of the j-th masked token
+        rows_all = (torch.arange(B, device=dev).view(B, 1) * TT + tpos).view(-1)
+        used = (mids != 0).view(-1)
+        # a batch whose masked_pos and masked_ids disagree is reported like a bad mask (device counter, TrainEngine.flush_text_check)
+        # (counts equal AND the used slots are the leading ones: dataset.py:321-324 pads masked_ids behind the real ids; a zero in
+        # front of a real id would pair targets with the wrong rows -- ADVICE r5)
+        nm = mpos.sum(1, keepdim=True)
+        bad = (nm.view(-1) != (mids != 0).sum(1)).any() | ((mids != 0) != (torch.arange(J, device=dev).view(1, J) < nm)).any()
+        self._text_counter(dev).add_(bad.to(torch.int32))
+        order = torch.argsort((~used).to(torch.int8), stable=True)
+        used_s = used[order]
+        st.sel = rows_all[order].contiguous()                                # forward: any valid row index (weight 0 where unused)
+        st.sel_bwd = torch.where(used_s, st.sel, torch.full_like(st.sel, B * TT))     # backward: unused slots -> the dummy row
+        st.tgt = mids.view(-1)[order].contiguous()
+        st.n = B * J
+        st.row_w = (used_s.to(torch.float32) / used.sum().clamp(min=1).to(torch.float32)).contiguous()     # 1 / #masked tokens: the mean
+
+    def _lm_head(self, st):
+        """LM head on the loss rows: forward, loss (+ d loss / d logits), backward down to the text rows' gradient st.dh."""
+        dev, hd, n = self.dev, self.cls_head, st.n
+        hrows = ops.cast_bf16(st.text_out.index_select(0, st.sel).contiguous())
         zt = torch.empty(n, 768, device=dev, dtype=torch.bfloat16)
-        gt = ops.gemm_ex(hrows, self.wb('cls.t'), bias=self.vec(c + '.transform.dense.bias'), act=L.ACT_GELU_ERF, zout=zt,
-                         out_dtype=torch.float32)
-        h2b, _ = ops.layernorm(gt, self.vec(c + '.transform.LayerNorm.weight'), self.vec(c + '.transform.LayerNorm.bias'), 1e-12)
+        gt = ops.gemm_ex(hrows, hd.t.w, bias=hd.t.b, act=L.ACT_GELU_ERF, zout=zt, out_dtype=torch.float32)
+        h2b, _ = ops.layernorm(gt, hd.n.g, hd.n.b, 1e-12)
         cbias = torch.zeros(L.VOCAB_PAD, device=dev)
-        cbias[:L.VOCAB] = self.vec(c + '.bias')
-        logits = ops.gemm_bias_act(h2b, self.wb('cls.dec'), cbias, out_dtype=torch.float32)
+        cbias[:L.VOCAB] = hd.dec.b
+        logits = ops.gemm_bias_act(h2b, hd.dec.w, cbias, out_dtype=torch.float32)
         dlog = torch.empty(n, L.VOCAB_PAD, device=dev, dtype=torch.bfloat16)
-        check(lib.vitcap_ls_kl_loss(_p(logits), L.VOCAB_PAD, L.VOCAB, _p(tgt), 0.0 if scst else self.eps_ls, n, _p(row_w),
+        check(lib.vitcap_ls_kl_loss(_p(logits), L.VOCAB_PAD, L.VOCAB, _p(st.tgt), 0.0 if st.scst else self.eps_ls, n, _p(st.row_w),
                                     _p(self.loss_buf), _p(dlog), L.VOCAB_PAD, _s()), 'ls_kl')
-        # ================= backward: LM head
-        wkey = W.TIED_SRC if self.model.tie_weights else c + '.decoder.weight'
         bsum = torch.zeros(L.VOCAB_PAD, device=dev)
         dlT = ops.transpose_colsum(dlog, bsum)                                 # [VOCAB_PAD][n_pad]
-        self.g(c + '.bias').copy_(bsum[:L.VOCAB])
+        hd.dec.gb.copy_(bsum[:L.VOCAB])
         h2T = ops.transpose_colsum(h2b)
         gdec = torch.empty(L.VOCAB_PAD, 768, device=dev)
         ops.gemm_ex(dlT, h2T, out=gdec)
-        self.g(wkey).copy_(gdec[:L.VOCAB])                                     # first writer of the (tied) embedding gradient
-        dh2 = ops.gemm_ex(dlog, self.wt('cls.dec'))                            # [n,768] bf16
-        dgt, _ = self._ln_bwd(gt, dh2, c + '.transform.LayerNorm.weight', c + '.transform.LayerNorm.bias', 1e-12)
+        hd.dec.gw.copy_(gdec[:L.VOCAB])                                        # first writer of the (tied) embedding gradient
+        dh2 = ops.gemm_ex(dlog, hd.dec.wt)                                     # [n,768] bf16
+        dgt, _ = self._ln_bwd(gt, dh2, hd.n, 1e-12)
         dzt = torch.empty(n, 768, device=dev, dtype=torch.bfloat16)
         check(lib.vitcap_gelu_bwd(_p(dgt), _p(zt), _p(dzt), n * 768, _s()), 'gelu_bwd')
-        self._wgrad_tn(dzt, hrows, self.g(c + '.transform.dense.weight'), self.g(c + '.transform.dense.bias').view(-1))
-        dh = ops.gemm_ex(dzt, self.wt('cls.t'), out_dtype=torch.float32)      # [n,768] fp32
-        yield 'cls'
-        dtext = torch.zeros(B * TT + 1, 768, device=dev)            # + the dummy row unused loss slots write to
-        dtext.index_copy_(0, sel_bwd, dh)
+        self._wgrad_tn(dzt, hrows, hd.t.gw, hd.t.gb)
+        st.dh = ops.gemm_ex(dzt, hd.t.wt, out_dtype=torch.float32)            # [n,768] fp32
+
+    def _decoder_bwd(self, st):
+        """Yields dec1, dec0; leaves the gradient of the decoder's input rows in st.dyv (B, LR, 768)."""
+        B, TT = st.B, st.TT
+        dtext = torch.zeros(B * TT + 1, 768, device=self.dev)            # + the dummy row unused loss slots write to
+        dtext.index_copy_(0, st.sel_bwd, st.dh)
         dtext = dtext[:B * TT]
-        if prune:
-            dy = dtext                               # the last layer's backward runs on the text rows (see the forward)
-        else:
-            dy = torch.zeros(B, LR, 768, device=dev)
-            dy[:, SV:] = dtext.view(B, TT, 768)
-            dy = dy.view(Md, 768)
-        # ================= backward: decoder layers
+        dy = dtext if st.prune else self._all_rows(st, dtext)           # pruned: the last layer's backward runs on the text rows
         for l in (3, 2, 1, 0):
-            pre = 'module.bert.decoder.layer.%d' % l
-            if l == 3 and prune:
-                xb, qkv, ctx, lse, t1, ab, af, z, it, t2, ctx_t = dsaved[l]
-                dt2f, dt2b = self._ln_bwd(t2, dy, pre + '.output.LayerNorm.weight', pre + '.output.LayerNorm.bias', 1e-12)
-                if ph > 0:      # the dense branch sees the masked gradient, the residual branch (dt2f) the whole one
-                    dt2b = ops.cast_bf16(ops.hidden_dropout(dt2f, None, TT, SV, hseed(l, 2), ph))
-                self._wgrad_tn(dt2b, it, self.g(pre + '.output.dense.weight'), self.g(pre + '.output.dense.bias').view(-1))
-                dz = ops.gemm_ex(dt2b, self.wt(pre + '.o'), aux=z)
-                self._wgrad_tn(dz, ab, self.g(pre + '.intermediate.dense.weight'), self.g(pre + '.intermediate.dense.bias').view(-1))
-                da = ops.gemm_ex(dz, self.wt(pre + '.i'), residual=dt2f, out_dtype=torch.float32)
-                dt1f, dt1b = self._ln_bwd(t1, da, pre + '.attention.output.LayerNorm.weight',
-                                          pre + '.attention.output.LayerNorm.bias', 1e-12)
-                if ph > 0:
-                    dt1b = ops.cast_bf16(ops.hidden_dropout(dt1f, None, TT, SV, hseed(l, 1), ph))
-                self._wgrad_tn(dt1b, ctx_t, self.g(pre + '.attention.output.dense.weight'),
-                               self.g(pre + '.attention.output.dense.bias').view(-1))
-                dctx_t = ops.gemm_ex(dt1b, self.wt(pre + '.ao'))
-                dctx = torch.zeros(B, LR, 768, device=dev, dtype=torch.bfloat16)
-                dctx[:, SV:] = dctx_t.view(B, TT, 768)
-                dqkv = ops.attn_dense_bwd(qkv, ctx, dctx.view(Md, 768), lse, B, LR, p_drop=pd, drop_seed=dseed[l], causal_from=SV,
-                                          mask_from=SV + T if scst else 0, q_range=(QLO, LR))
-                self._wgrad_tn(dqkv, xb, self.qkv_w_grad(pre), self.qkv_bias_grad(pre))
-                res = torch.zeros(B, LR, 768, device=dev)
-                res[:, SV:] = dt1f.view(B, TT, 768)               # the residual path reaches the layer input on the text rows only
-                dy = ops.gemm_ex(dqkv, self.wt(pre + '.qkv'), residual=res.view(Md, 768), out_dtype=torch.float32)
-                continue
-            xb, qkv, ctx, lse, t1, ab, af, z, it, t2 = dsaved[l]
-            # bias gradients = column sums of dt2b / dz / dt1b, added by the kernels that write those operands
-            if ph > 0:      # masked gradient for the dense branch: its bf16 copy + bias column sums from the masked values
-                dt2f, _ = self._ln_bwd(t2, dy, pre + '.output.LayerNorm.weight', pre + '.output.LayerNorm.bias', 1e-12)
-                dt2b = ops.cast_bf16_colsum(ops.hidden_dropout(dt2f, None, LR, 0, hseed(l, 2), ph), self.g(pre + '.output.dense.bias').view(-1))
-            else:
-                dt2f, dt2b = self._ln_bwd(t2, dy, pre + '.output.LayerNorm.weight', pre + '.output.LayerNorm.bias', 1e-12,
-                                          dxb_colsum=self.g(pre + '.output.dense.bias').view(-1))
-            self._wgrad_tn(dt2b, it, self.g(pre + '.output.dense.weight'), None)
-            dz, pend = self._dgrad_gelu(dt2b, self.wt(pre + '.o'), z, self.g(pre + '.intermediate.dense.bias').view(-1))   # [Md,3072] bf16
-            self._wgrad_tn(dz, ab, self.g(pre + '.intermediate.dense.weight'), pend)
-            da = ops.gemm_ex(dz, self.wt(pre + '.i'), residual=dt2f, out_dtype=torch.float32)
-            if ph > 0:
-                dt1f, _ = self._ln_bwd(t1, da, pre + '.attention.output.LayerNorm.weight', pre + '.attention.output.LayerNorm.bias', 1e-12)
-                dt1b = ops.cast_bf16_colsum(ops.hidden_dropout(dt1f, None, LR, 0, hseed(l, 1), ph),
-                                            self.g(pre + '.attention.output.dense.bias').view(-1))
-            else:
-                dt1f, dt1b = self._ln_bwd(t1, da, pre + '.attention.output.LayerNorm.weight', pre + '.attention.output.LayerNorm.bias',
-                                          1e-12, dxb_colsum=self.g(pre + '.attention.output.dense.bias').view(-1))
-            self._wgrad_tn(dt1b, ctx, self.g(pre + '.attention.output.dense.weight'), None)
-            dctx = ops.gemm_ex(dt1b, self.wt(pre + '.ao'))
-            dqkv = ops.attn_dense_bwd(qkv, ctx, dctx, lse, B, LR, p_drop=pd, drop_seed=dseed[l], causal_from=SV,
-                                      mask_from=SV + T if scst else 0)
-            self._wgrad_tn(dqkv, xb, self.qkv_w_grad(pre), self.qkv_bias_grad(pre))
-            dy = ops.gemm_ex(dqkv, self.wt(pre + '.qkv'), residual=dt1f, out_dtype=torch.float32)
+            dy = self._dec_bwd(st, l, dy, text_only=(l == 3 and st.prune))
             if l % 2 == 0:
                 yield 'dec%d' % (l // 2)
-        dyv = dy.view(B, LR, 768)
-        # ================= backward: text embeddings
-        dtext_in = dyv[:, SV:].reshape(B * TT, 768).contiguous()
-        if ph > 0:
-            ops.hidden_dropout(dtext_in, None, TT, SV, hseed(4, 3), ph, out=dtext_in)
-        demb, _ = self._ln_bwd(pre_emb, dtext_in, e + '.LayerNorm.weight', e + '.LayerNorm.bias', 1e-12, dres=None)
-        check(lib.vitcap_embed_bwd(_p(demb), _p(ids20.view(-1)), TT, _p(self.g(e + '.word_embeddings.weight')),
-                                   _p(self.g(e + '.position_embeddings.weight')), _p(self.g(e + '.token_type_embeddings.weight')),
-                                   B * TT, T if scst else 0, _s()), 'embed_bwd')
-        yield 'emb'
-        # ================= backward: encoder
+        st.dyv = dy.view(B, st.LR, 768)
+
+    def _embedding_bwd(self, st):
+        emb, B, TT = self.emb, st.B, st.TT
+        dtext_in = st.dyv[:, SV:].reshape(B * TT, 768).contiguous()
+        if st.ph > 0:
+            ops.hidden_dropout(dtext_in, None, TT, SV, st.hseed(4, 3), st.ph, out=dtext_in)
+        demb, _ = self._ln_bwd(st.pre_emb, dtext_in, emb.n, 1e-12, dres=None)
+        check(lib.vitcap_embed_bwd(_p(demb), _p(st.ids20.view(-1)), TT, _p(emb.gword), _p(emb.gpos), _p(emb.gtype),
+                                   B * TT, T if st.scst else 0, _s()), 'embed_bwd')
+
+    def _encoder_bwd(self, st):
+        """Yields tag1, tag0, blk5 .. blk0; leaves the gradient of the patch embedding's output in st.dxe."""
+        Be, KS, M = st.Be, st.KS, st.M
         if KS > 1:      # the KS sequences of an image saw the same visual rows: their gradients add up
-            dyv_vis = dyv[:, :SV].reshape(Be, KS, SV, 768).sum(1)
+            dyv_vis = st.dyv[:, :SV].reshape(Be, KS, SV, 768).sum(1)
         else:
-            dyv_vis = dyv[:, :SV]
+            dyv_vis = st.dyv[:, :SV]
         dhid = dyv_vis[:, 1:SV].reshape(M, 768).contiguous()
-        if not prune:
-            dtag = torch.zeros(Be, NV, 768, device=dev)
+        if not st.prune:
+            dtag = torch.zeros(Be, NV, 768, device=self.dev)
             dtag[:, 0] = dyv_vis[:, 0]
             dtag = dtag.view(M, 768)
-
-        def block_bwd_cls(pre, dxo_c):
-            """Backward of block_fwd_cls: dxo_c (B,768) = gradient of the block's CLS output; returns the gradient of the block's
-            input on all rows (the CLS query's attention spreads it over every row through K and V)."""
-            xin, h1, qkv, ao, lse, xmid_c, h2_c, z_c, g_c, ao_c = saved.pop(pre)
-            dxb = ops.cast_bf16(dxo_c)
-            self._wgrad_tn(dxb, g_c, self.g(pre + '.mlp.fc2.weight'), self.g(pre + '.mlp.fc2.bias').view(-1))
-            dz = ops.gemm_ex(dxb, self.wt(pre + '.fc2'), aux=z_c)
-            self._wgrad_tn(dz, h2_c, self.g(pre + '.mlp.fc1.weight'), self.g(pre + '.mlp.fc1.bias').view(-1))
-            dh2 = ops.gemm_ex(dz, self.wt(pre + '.fc1'))
-            dmf, dmb = self._ln_bwd(xmid_c, dh2, pre + '.norm2.weight', pre + '.norm2.bias', 1e-6, dres=dxo_c)
-            self._wgrad_tn(dmb, ao_c, self.g(pre + '.attn.proj.weight'), self.g(pre + '.attn.proj.bias').view(-1))
-            dao_c = ops.gemm_ex(dmb, self.wt(pre + '.proj'))
-            dao = torch.zeros(Be, NV, 768, device=dev, dtype=torch.bfloat16)
-            dao[:, 0] = dao_c
-            dqkv = ops.attn_dense_bwd(qkv, ao, dao.view(M, 768), lse, Be, NV, q_range=(0, 1))
-            self._wgrad_tn(dqkv, h1, self.g(pre + '.attn.qkv.weight'), self.g(pre + '.attn.qkv.bias').view(-1))
-            dh1 = ops.gemm_ex(dqkv, self.wt(pre + '.qkv'))
-            res = torch.zeros(Be, NV, 768, device=dev)
-            res[:, 0] = dmf
-            dif, _ = self._ln_bwd(xin, dh1, pre + '.norm1.weight', pre + '.norm1.bias', 1e-6, dres=res.view(M, 768))
-            return dif
-
-        def block_bwd(pre, dxo):
-            xin, h1, qkv, ao, lse, xmid, h2, z, g = saved.pop(pre)
-            # the three bias gradients below are column sums of a backward operand; each is added by the kernel that WRITES that
-            # operand (cast, GEMM epilogue, LayerNorm backward) instead of a separate pass over it
-            if _FUSE_BIAS:
-                dxb = ops.cast_bf16_colsum(dxo, self.g(pre + '.mlp.fc2.bias').view(-1))
-            else:
-                dxb = ops.cast_bf16(dxo)
-                ops.colsum_bf16(dxb, self.g(pre + '.mlp.fc2.bias').view(-1))
-            self._wgrad_tn(dxb, g, self.g(pre + '.mlp.fc2.weight'), None)
-            dz, pend = self._dgrad_gelu(dxb, self.wt(pre + '.fc2'), z, self.g(pre + '.mlp.fc1.bias').view(-1))
-            self._wgrad_tn(dz, h2, self.g(pre + '.mlp.fc1.weight'), pend)
-            dh2 = ops.gemm_ex(dz, self.wt(pre + '.fc1'))
-            dmf, dmb = self._ln_bwd(xmid, dh2, pre + '.norm2.weight', pre + '.norm2.bias', 1e-6, dres=dxo,
-                                    dxb_colsum=self.g(pre + '.attn.proj.bias').view(-1))
-            self._wgrad_tn(dmb, ao, self.g(pre + '.attn.proj.weight'), None)
-            dao = ops.gemm_ex(dmb, self.wt(pre + '.proj'))
-            dqkv = ops.attn_dense_bwd(qkv, ao, dao, lse, Be, NV)
-            self._wgrad_tn(dqkv, h1, self.g(pre + '.attn.qkv.weight'), self.g(pre + '.attn.qkv.bias').view(-1))
-            dh1 = ops.gemm_ex(dqkv, self.wt(pre + '.qkv'))
-            dif, _ = self._ln_bwd(xin, dh1, pre + '.norm1.weight', pre + '.norm1.bias', 1e-6, dres=dmf)
-            return dif
-
         for i in (3, 2, 1, 0):
-            if i == 3 and prune:
-                dtag = block_bwd_cls('module.bert.encoder.tag_blocks.3', dyv_vis[:, 0].contiguous())
+            if i == 3 and st.prune:
+                dtag = self._vit_bwd(st, self.tag_blocks[3], dyv_vis[:, 0].contiguous(), cls_only=True)
             else:
-                dtag = block_bwd('module.bert.encoder.tag_blocks.%d' % i, dtag)
+                dtag = self._vit_bwd(st, self.tag_blocks[i], dtag)
             if i % 2 == 0:
                 yield 'tag%d' % (i // 2)
         for i in (11, 10, 9, 8):
-            dhid = block_bwd('module.bert.encoder.blocks.%d' % i, dhid)
+            dhid = self._vit_bwd(st, self.blocks[i], dhid)
             if i % 2 == 0:
                 yield 'blk%d' % (i // 2)
         dxe = dhid
         ops.reduce_slabs(dtag.view(1, M * 768), dxe.view(-1), accumulate=True)      # fork point: the two branches' gradients meet
         for i in range(7, -1, -1):
-            dxe = block_bwd('module.bert.encoder.blocks.%d' % i, dxe)
+            dxe = self._vit_bwd(st, self.blocks[i], dxe)
             if i % 2 == 0:
                 yield 'blk%d' % (i // 2)
-        # ================= backward: patch embed, cls token, position embedding
-        check(lib.vitcap_sum_over_batch(_p(dxe), NV * 768, Be, _p(self.g(ie + 'pos_embed')), NV * 768, _s()), 'sum_over_batch')
-        self.g(ie + 'cls_token').view(-1).copy_(self.g(ie + 'pos_embed').view(NV, 768)[0])
+        st.dxe = dxe
+
+    def _patch_bwd(self, st):
+        """Patch embed, cls token, position embedding."""
+        Be, dxe = st.Be, st.dxe
+        check(lib.vitcap_sum_over_batch(_p(dxe), NV * 768, Be, _p(self.pos_embed.g), NV * 768, _s()), 'sum_over_batch')
+        self.cls_token.g.copy_(self.pos_embed.g[0])
         dpatch = ops.cast_bf16(dxe.view(Be, NV, 768)[:, 1:].reshape(Be * 576, 768).contiguous())
-        self._wgrad_tn(dpatch, patches, self.g(ie + 'patch_embed.proj.weight').view(768, 768), self.g(ie + 'patch_embed.proj.bias').view(-1))
-        yield 'patch'
-        return self.loss_buf[0], self.loss_buf[1]
+        self._wgrad_tn(dpatch, st.patches, self.patch.gw, self.patch.gb)
 
     # ------------------------------------------------------------------ optimizer
     def all_reduce_grads(self):
