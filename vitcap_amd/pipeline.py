@@ -10,7 +10,7 @@ get_raw_model 566-618, predict_output_to_tsv_row 620-630) for what the hot path 
   reference's suffix-matching loader, captions the test split, writes ``<model>.…predict.tsv`` rows
   ``key \\t json([{"caption": str, "conf": exp(logprob)}])`` per rank and merges them on rank 0;
 * the input side: ``test_data`` names a TSV of (key, base64 JPEG) rows read through ``.lineidx``
-  (tsv.py), decoded by worker processes on the host (jpegdec.py) and resized / cropped / normalised on the GPU bit-identical to
+  (tsv.py), decoded by worker processes on the host (loader.py, jpegdec.py) and resized / cropped / normalised on the GPU bit-identical to
   Pillow (csrc/preproc.hip); ``data: synthetic`` (seeded uniform(-1,1) images) and an iterable passed as ``test_batches`` remain;
 * ``ensure_train`` runs the HIP training engine (vitcap_amd/train.py) on synthetic or caller-provided batches and
   writes reference-format snapshots; ``ensure_evaluate`` needs the external
@@ -27,127 +27,11 @@ import torch
 
 from . import dist_util as D
 
-
-
-def _release_slab(shm):
-    """close() raises BufferError while a numpy view of the segment is still exported; the name must be unlinked all the same, or the
-    segment outlives the process until the resource tracker reaps it."""
-    try:
-        shm.close()
-    except Exception:
-        pass
-    try:
-        shm.unlink()
-    except Exception:
-        pass
-
-
-def _pin_slabs(slabs):
-    """hipHostRegister on every shared-memory slab -> list of registered base addresses (empty when the runtime refuses: the copies
-    then take the pageable path, slower but correct).  VITCAP_LOADER_PIN=0 disables."""
-    import ctypes
-    if os.environ.get('VITCAP_LOADER_PIN', '1') == '0':
-        return []
-    done = []
-    try:
-        rt = torch.cuda.cudart()
-        for shm in slabs:
-            addr = ctypes.addressof(ctypes.c_char.from_buffer(shm.buf))
-            err = rt.cudaHostRegister(addr, shm.size, 0)
-            if int(getattr(err, 'value', err)) != 0:
-                logging.warning('hipHostRegister refused a loader slab (error %s): host -> device copies stay pageable', err)
-                break
-            done.append(addr)
-    except Exception as e:          # noqa
-        logging.warning('loader slabs not page-locked (%s)', e)
-    return done
-
-
-def _unpin_slabs(addrs):
-    try:
-        rt = torch.cuda.cudart()
-        for a in addrs:
-            rt.cudaHostUnregister(a)
-    except Exception:
-        pass
-
-
-def _prefetched(gen, device, depth=2):
-    """Runs the batch generator in a background thread, `depth` batches ahead: reading the TSV rows, handing them to the decode workers,
-    the host -> device copies and the launch of the transform kernel no longer sit between two caption launches of the consumer
-    (measured: the consumer thread was the limit at 26 ms per batch of 64, the GPU needs 17).  A batch is handed over after the producer's
-    stream has been synchronised, so the consumer may use it on any stream."""
-    import queue
-    import threading
-    q = queue.Queue(maxsize=max(1, depth))
-    END = object()
-    stop = threading.Event()            # set when the consumer goes away (exception, generator closed): the producer must not block in put
-
-    def put(item):
-        while not stop.is_set():
-            try:
-                q.put(item, timeout=0.2)
-                return True
-            except queue.Full:
-                continue
-        return False
-
-    def work():
-        try:
-            if device.type == 'cuda':
-                torch.cuda.set_device(device)
-            ev = torch.cuda.Event(blocking=True) if device.type == 'cuda' else None     # sleep, do not spin (see generate_async)
-            # the producer's copies and transform kernels go to a stream of their own: on the (per-process) default stream they shared a
-            # queue with the consumer's blocking device -> host copies of the finished captions, and each side waited behind the other's
-            # work -- with 24 batches of prefetch a `.cpu()` of 5 KB could sit behind a whole batch of host -> device copies
-            # (docs/LAB_r05.md 5: the 22 ms-per-batch mode of the round script's input-side runs)
-            from .model import role_stream
-            side = role_stream(device, 'loader', lambda: torch.cuda.Stream(device)) if device.type == 'cuda' else None
-            if side is not None:
-                torch.cuda.set_stream(side)          # thread-local: this thread only
-            for b in gen:
-                t0 = time.perf_counter()
-                if ev is not None:
-                    ev.record(torch.cuda.current_stream(device))
-                    ev.synchronize()
-                t1 = time.perf_counter()
-                ok = put(b)
-                LOADER_TIMES['copy_sync'] = LOADER_TIMES.get('copy_sync', 0.0) + t1 - t0
-                LOADER_TIMES['queue_full'] = LOADER_TIMES.get('queue_full', 0.0) + time.perf_counter() - t1
-                if not ok:
-                    break
-            else:
-                put(END)
-        except BaseException as e:          # surfaces in the consumer
-            put(e)
-        finally:
-            close = getattr(gen, 'close', None)     # runs the generator's own `finally` (worker pool, shared-memory slabs) in this thread
-            if close is not None:
-                try:
-                    close()
-                except Exception:
-                    pass
-    t = threading.Thread(target=work, daemon=True)
-    t.start()
-    try:
-        while True:
-            t0 = time.perf_counter()
-            b = q.get()
-            LOADER_TIMES['queue_empty'] = LOADER_TIMES.get('queue_empty', 0.0) + time.perf_counter() - t0
-            if b is END:
-                break
-            if isinstance(b, BaseException):
-                raise b
-            yield b
-    finally:
-        stop.set()
-        t.join(timeout=30)
-
-
-LOADER_TIMES = {}           # seconds, summed over the batches of the last predict: where the producer thread and the consumer waited
-LAST_PREDICT_STATS = {}     # filled by CaptionUniPipeline.predict: rows, steady-state images/sec of this rank (tools/input_side_bench.py)
 from .checkpoint import Checkpointer
 from .config import Config
+from .loader import LOADER_TIMES, prefetched, timed      # LOADER_TIMES: the loader's own dict (tools/input_side_bench.py reads it here)
+
+LAST_PREDICT_STATS = {}     # filled by CaptionUniPipeline.predict: rows, steady-state images/sec of this rank (tools/input_side_bench.py)
 
 _UNI_DEFAULT = {   # the subset of UniPipeline._default (uni_pipeline.py:93-148) the hot path reads
     'dist_backend': 'nccl', 'effective_batch_size': 256, 'test_batch_size': 48, 'max_iter': 10, 'log_step': 100,
@@ -244,6 +128,108 @@ class _EngineState(object):
             return self.eng.load_scheduler_state_dict(sd)
         self.eng.load_model_state_dict(sd)
         return torch.nn.modules.module._IncompatibleKeys([], [])
+
+
+class _PredictRun(object):
+    """State of one CaptionUniPipeline.predict: the generation options per number of visible tag slots, the count the last
+    device-resident mask showed, the batches in flight and the row counter of the steady-state figure."""
+
+    def __init__(self, pipe, model):
+        self.pipe, self.model = pipe, model
+        self.overlap = not model.test_extra_input.get('do_sample', False)
+        # the same option validation ImageCaptioning.forward applies (max_length, repetition_penalty, num_keep_best, use_cbs,
+        # token ids ...): an option this build does not implement raises here instead of being decoded with defaults
+        self.base = model.gen_options(gemm_mode=1) if self.overlap else None
+        self.opts = {}                  # vitcap_gen_opts per number of visible tag slots: the caller's mask decides
+        self.seen_n = None              # visible tag slots of the last batch whose text tensors live on the device
+        self.pending = []               # greedy / beam: batch i decodes while batch i+1 is encoded (generate_async)
+        self.rows, self.t_first, self.rows_first = 0, None, 0
+
+    def opts_for(self, n_tag):
+        base = self.base
+        if n_tag not in self.opts:
+            if base.tag_visible and n_tag != base.tag_visible:
+                raise ValueError('test_extra_input tag_visible=%d but the attention_mask shows %d tag slots' % (base.tag_visible, n_tag))
+            self.opts[n_tag] = base if n_tag == base.tag_visible else self.model.gen_options(gemm_mode=1, tag_visible=n_tag)
+        return self.opts[n_tag]
+
+    def submit(self, batch):
+        """Starts one batch and queues (batch, output or its future, device-side mask verdict, count it was compared with)."""
+        model, flag, expect_n = self.model, None, None
+        if not self.overlap:
+            self.pending.append((batch, model(batch), flag, expect_n))
+            return
+        # host tensors (what the loader yields) are checked on the host; tensors already on the device cost ONE host
+        # synchronisation (the first batch, to read the number of visible tag slots), afterwards they are compared on
+        # their stream and the verdict is read when the batch's captions are collected -- nothing stalls the
+        # 2-slot pipeline
+        am = batch.get('attention_mask')
+        if am is not None and am.is_cuda and self.seen_n is not None:
+            expect_n = self.seen_n
+            n_tag, flag = model.check_text_inputs(batch, self.base.max_length, expect_n_tag=expect_n)
+        else:
+            n_tag = model.check_text_inputs(batch, self.base.max_length)
+            if am is not None and am.is_cuda:
+                self.seen_n = n_tag
+        with timed('consumer_submit'):
+            out = model.generate_async(batch['image'], opts=self.opts_for(n_tag))
+        self.pending.append((batch, out, flag, expect_n))
+
+    def collect(self, entry):
+        """Waits for one queued batch -> its predict-TSV rows."""
+        b, out, flag, expect_n = entry
+        with timed('consumer_wait_gpu'):
+            out = out.result() if self.overlap else out          # synchronises with the batch's decode stream
+        if flag is not None and not bool(flag):
+            # the device-side comparison against the count of the earlier batches failed: either this batch's (valid) mask shows
+            # another number of visible tag slots -- then it is decoded again with the options of ITS count, as a host-resident
+            # batch would have been from the start -- or the mask is not one the engine implements (ADVICE r3)
+            n_tag = self.model.check_text_inputs(b, self.base.max_length)         # raises NotImplementedError for an unsupported mask
+            # compared with the count THIS batch was submitted against (one batch is always in flight: by now `seen_n` may already
+            # hold the count an earlier re-decode found -- ADVICE r4)
+            if n_tag == expect_n:
+                raise NotImplementedError('a batch\'s attention_mask / token_type_ids on the device do not describe the mask structure '
+                                          'the HIP engine implements (ImageCaptioning.check_text_inputs)')
+            logging.info('visible tag slots changed from %s to %d: batch decoded again with its own options', expect_n, n_tag)
+            self.seen_n = n_tag
+            out = self.model.generate_async(b['image'], opts=self.opts_for(n_tag)).result()
+        with timed('consumer_rows'):
+            return list(self.pipe.predict_output_to_tsv_row(b, (out[0].cpu(), out[1].cpu())))
+
+    def caption_rows(self, batches, dev):
+        """(key, json) rows of all batches, in order."""
+        with torch.no_grad():
+            for batch in batches:
+                batch = dict(batch)
+                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
+                self.submit(batch)
+                # TWO batches stay in flight behind the one just submitted: batch k-2 is collected (its decode finished before
+                # batch k-1's started) while k-1 decodes and k encodes, so the detokeniser / JSON / TSV work of this thread (~5 ms
+                # per 64 captions) never sits between two submissions -- with one batch in flight the GPU ran batch k's decode
+                # alone while this thread was still writing batch k-1's rows (round 5: 21 vs 16 ms per batch from disk).  The
+                # outputs of a batch are its own tensors; its workspace slot is re-used by batch k+1 behind a stream-side wait.
+                while len(self.pending) > (2 if self.overlap else 0):
+                    yield from self.collect(self.pending.pop(0))
+            for entry in self.pending:
+                yield from self.collect(entry)
+
+    def counted(self, rows):
+        """images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
+        workers running) to the last row -- the figure the reference's trainer logs as images/sec (trainer.py:155-170)."""
+        for row in rows:
+            self.rows += 1
+            if self.t_first is None and self.rows >= 2 * int(self.pipe.cfg.test_batch_size):
+                self.t_first, self.rows_first = time.perf_counter(), self.rows
+            yield row
+
+    def report(self):
+        if self.t_first is None or self.rows <= self.rows_first:
+            return
+        dt = time.perf_counter() - self.t_first
+        LAST_PREDICT_STATS.update(rows=self.rows, steady_rows=self.rows - self.rows_first, steady_seconds=dt, t_end=time.perf_counter(),
+                                  loader_seconds={k: round(v, 3) for k, v in LOADER_TIMES.items()},
+                                  images_per_sec=(self.rows - self.rows_first) / dt)
+        logging.info('predict: %d rows, steady state %.1f images/sec on rank %d', self.rows, LAST_PREDICT_STATS['images_per_sec'], self.pipe.rank)
 
 
 class CaptionUniPipeline(object):
@@ -517,7 +503,8 @@ class CaptionUniPipeline(object):
         return self.get_checkpoint_file(iteration=max_iter)
 
     def iter_test_batches(self):
-        """Per-rank shard of the test set.  `data: synthetic` -> seeded images, keys '<rank>_<i>'."""
+        """Per-rank shard of the test set: caller-provided batches, the rows of a TSV of (key, base64 JPEG) through
+        vitcap_amd/loader.py, or `data: synthetic` -> seeded images, keys '<rank>_<i>'."""
         if self.cfg.test_batches is not None:
             for i, b in enumerate(self.cfg.test_batches):
                 if i % self.world == self.rank:
@@ -525,148 +512,7 @@ class CaptionUniPipeline(object):
             return
         tsv = self.test_image_tsv()
         if tsv is not None:
-            # (key, base64 JPEG) rows; rank r takes rows r, r+world, ... like DistributedSampler(shuffle=False)
-            # (uni_pipeline.py:782-850); decode on the host, transform on the GPU (csrc/preproc.hip)
-            from .imageio import ImagePreprocessor
-            from .tsv import TSVFile
-            tsv = op.abspath(tsv)
-            rows = TSVFile(tsv)
-            pre = ImagePreprocessor(torch.device('cuda', self.local_rank), int(self.cfg.test_crop_size),
-                                    float(self.cfg.crop_pct or 1.0))
-            bs = int(self.cfg.test_batch_size)
-            mine = list(range(self.rank, len(rows), self.world))
-            # JPEG decoding is host work: `num_workers` worker PROCESSES (the reference's DataLoader(num_workers),
-            # uni_pipeline.py:333-339) decode the images of the next batches while the GPU captions the current one.  Measured on the
-            # GPU box (tools/input_side_bench.py, profiles/r04_input_side.json): one core decodes 600 images/s, threads of one process
-            # top out near 2 000 (GIL), a GPU captions 3 700.  The workers are SPAWNED (never forked: this process owns a GPU
-            # context) and import vitcap_amd.jpegdec only.  `loader_threads: true` keeps the decode in threads of this process.
-            # Rows are read by the WORKERS (round 5: a task names the file and its row numbers), batches come back in order.
-            from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
-            from .jpegdec import coef_item, decode_rows, decode_rows_into, jpeg_lib
-            from .imageio import CoefImage
-            # device JPEG back half (round 6): the workers only entropy-decode baseline JPEGs (libvitcap_jpeg.so); dequantisation, inverse
-            # DCT, upsampling and the colour conversion run on the GPU in front of the resize, bit-identical to Pillow.  `device_jpeg:
-            # false` (or a missing library) keeps the whole decode in the workers.
-            device_jpeg = (self.cfg.device_jpeg is None or bool(self.cfg.device_jpeg)) and jpeg_lib() is not None and not self.cfg.loader_threads
-            import numpy as np
-            workers = max(1, int(self.cfg.num_workers or 1))
-            chunk = int(os.environ.get('VITCAP_LOADER_CHUNK', 8))      # images per worker task
-            per_batch = (bs + chunk - 1) // chunk
-            # batches being decoded ahead of the one handed out: ten tasks per worker.  Decode times jitter (image sizes, a host shared
-            # with other tenants) and the consumer can never run faster than the GPU to make up for a gap, so every gap is lost for good:
-            # with 3 batches ahead + 4 queued 0.93-0.94 of the resident rate, with 10 + 24 0.96-0.975 (profiles/r05_input_side.json)
-            ahead = min(12, max(3, (10 * workers + per_batch - 1) // per_batch))     # <= 15 batches of slabs (2.9 GB nominal) however many workers
-            ahead = int(os.environ.get('VITCAP_LOADER_AHEAD', ahead))
-            starts = list(range(0, len(mine), bs))
-            slabs, free = [], []
-            if self.cfg.loader_threads:
-                pool = ThreadPoolExecutor(max_workers=workers)
-            else:
-                import multiprocessing as mp
-                from multiprocessing import shared_memory
-                ctx = mp.get_context('spawn')
-                # VITCAP_LOADER_CPUS=<first>[:<stride>] (experiment): worker i is pinned to CPU first + i * stride (default stride 1) -- under a
-                # CFS quota on a many-core host the scheduler otherwise migrates the decoders across the whole machine
-                pin = os.environ.get('VITCAP_LOADER_CPUS')
-                if pin:
-                    from .jpegdec import pin_worker
-                    first, _, stride = pin.partition(':')
-                    pool = ProcessPoolExecutor(max_workers=workers, mp_context=ctx, initializer=pin_worker,
-                                               initargs=(ctx.Value('i', 0), int(first), int(stride or 1)))
-                else:
-                    pool = ProcessPoolExecutor(max_workers=workers, mp_context=ctx)
-                # decoded pixels come back through shared memory (vitcap_amd/jpegdec.py); a slab holds one task's images and is reused
-                # two batches after the batch that read it went to the GPU
-                slab_bytes = int(self.cfg.loader_slab_mb or 24) << 20
-                # the slabs are page-locked shared memory (x ranks on one host): the decode-ahead depth is capped in BYTES, not batches
-                # (at test_batch_size 512 the batch-count rule asked for 9-23 GB per rank).  `loader_shm_gb` (default 4); the
-                # floor is one batch ahead + the three in retirement.
-                budget = int(float(self.cfg.loader_shm_gb or os.environ.get('VITCAP_LOADER_SHM_GB', 4)) * 2**30)
-                ahead = max(1, min(ahead, budget // (per_batch * slab_bytes) - 3))
-                n_slabs = (ahead + 3) * per_batch
-                logging.info('loader: %d slabs x %d MB = %.1f GB of page-locked shared memory (%d batches ahead)', n_slabs, slab_bytes >> 20,
-                             n_slabs * slab_bytes / 2**30, ahead)
-                # a /dev/shm too small for the slabs (container default: 64 MB) would kill the workers with SIGBUS on first touch:
-                # check the free space first and fall back to returning the pixels through the pool's pipe (decode_many)
-                try:
-                    st = os.statvfs('/dev/shm')
-                    room = st.f_bavail * st.f_frsize
-                except OSError:
-                    room = 0
-                if room >= (n_slabs * slab_bytes * 5) // 4:
-                    try:
-                        for _ in range(n_slabs):
-                            slabs.append(shared_memory.SharedMemory(create=True, size=slab_bytes))
-                    except OSError as e:
-                        logging.warning('shared-memory slabs unavailable (%s): decoded images return through the worker pipe', e)
-                        for shm in slabs:
-                            _release_slab(shm)
-                        slabs = []
-                else:
-                    logging.warning('/dev/shm has %.0f MB free, the loader wants %.0f MB of slabs: decoded images return through the worker '
-                                    'pipe (lower num_workers / loader_slab_mb, or enlarge /dev/shm)', room / 2**20, n_slabs * slab_bytes / 2**20)
-                free = list(range(len(slabs)))
-                # page-lock the slabs: a pageable source makes every host -> device copy go through the runtime's staging buffer (a
-                # single-threaded memcpy of ~1 MB per image in THIS process, then the DMA); registered, the DMA reads the slab itself
-                pinned = _pin_slabs(slabs)
-            retired = []                                               # slab ids of the last batches handed to the GPU
-            try:
-                with pool:
-                    inflight = []
-
-                    def submit(k):
-                        # a task names the file and the row numbers: the WORKER reads and base64-decodes its rows (jpegdec.py)
-                        ids = mine[starts[k]:starts[k] + bs]
-                        tasks = []
-                        for c in range(0, len(ids), chunk):
-                            if slabs:
-                                sid = free.pop()
-                                tasks.append((sid, pool.submit(decode_rows_into, slabs[sid].name, tsv, ids[c:c + chunk], device_jpeg)))
-                            else:
-                                tasks.append((None, pool.submit(decode_rows, tsv, ids[c:c + chunk])))
-                        inflight.append(tasks)
-                    nxt = 0
-                    while nxt < len(starts) and len(inflight) < ahead:
-                        submit(nxt)
-                        nxt += 1
-                    while inflight:
-                        tasks = inflight.pop(0)
-                        keys, imgs, used = [], [], []
-                        t_wait = time.perf_counter()
-                        for sid, f in tasks:
-                            ks, items = f.result()
-                            keys.extend(ks)
-                            for item in items:
-                                if sid is not None and isinstance(item, tuple) and item[0] == 'coef':
-                                    imgs.append(CoefImage(*coef_item(item, slabs[sid].buf)))     # the GPU finishes the decode (csrc/jpeg.hip)
-                                elif sid is not None and isinstance(item, tuple):
-                                    off, h, w = item
-                                    imgs.append(np.ndarray((h, w, 3), dtype=np.uint8, buffer=slabs[sid].buf, offset=off))
-                                else:
-                                    imgs.append(item)
-                            if sid is not None:
-                                used.append(sid)
-                        t_pre = time.perf_counter()
-                        batch = {'image': pre(imgs), 'key': keys}       # host -> device copies of pageable memory return once staged
-                        del imgs
-                        LOADER_TIMES['decode_wait'] = LOADER_TIMES.get('decode_wait', 0.0) + t_pre - t_wait
-                        LOADER_TIMES['transform_enqueue'] = LOADER_TIMES.get('transform_enqueue', 0.0) + time.perf_counter() - t_pre
-                        retired.append(used)
-                        if len(retired) > 2:
-                            free.extend(retired.pop(0))
-                        if nxt < len(starts):
-                            submit(nxt)
-                            nxt += 1
-                        yield batch
-            finally:
-                if slabs:
-                    try:
-                        torch.cuda.current_stream(torch.device('cuda', self.local_rank)).synchronize()     # no copy still reads a slab
-                    except Exception:
-                        pass
-                    _unpin_slabs(pinned)
-                for shm in slabs:
-                    _release_slab(shm)
+            yield from self.test_tsv_loader(op.abspath(tsv))      # closing this generator closes the loader (PEP 380)
             return
         from . import weights as W
         n = int(self.cfg.synthetic_num_images or 8)
@@ -679,6 +525,30 @@ class CaptionUniPipeline(object):
             img = torch.from_numpy(W.gen_image_batch(done + b, seed)[done:])
             yield {'image': img, 'key': ['%d_%d' % (self.rank, done + i) for i in range(b)]}
             done += b
+
+    def test_tsv_loader(self, tsv):
+        """loader.PredictBatchLoader over this rank's rows of `tsv` (rank r takes rows r, r+world, ...), set up from the configuration
+        (num_workers, loader_threads, loader_slab_mb, loader_shm_gb, device_jpeg) and the VITCAP_LOADER_* switches."""
+        from . import loader as L
+        from .imageio import ImagePreprocessor
+        from .jpegdec import jpeg_lib
+        from .tsv import TSVFile
+        c, env = self.cfg, os.environ
+        dev = torch.device('cuda', self.local_rank)
+        threads = bool(c.loader_threads)
+        # device JPEG back half (round 6): the workers only entropy-decode baseline JPEGs (libvitcap_jpeg.so); dequantisation, inverse
+        # DCT, upsampling and the colour conversion run on the GPU in front of the resize, bit-identical to Pillow.  `device_jpeg:
+        # false` (or a missing library) keeps the whole decode in the workers.
+        device_jpeg = (c.device_jpeg is None or bool(c.device_jpeg)) and jpeg_lib() is not None and not threads
+        bs, workers = int(c.test_batch_size), max(1, int(c.num_workers or 1))
+        chunk = int(env.get('VITCAP_LOADER_CHUNK', 8))      # images per worker task
+        slab_bytes = int(c.loader_slab_mb or 24) << 20
+        budget = int(float(c.loader_shm_gb or env.get('VITCAP_LOADER_SHM_GB', 4)) * 2**30)      # `loader_shm_gb` (default 4)
+        plan = L.decode_ahead_plan(bs, workers, chunk, slab_bytes, budget, not threads, env.get('VITCAP_LOADER_AHEAD'))
+        pre = ImagePreprocessor(dev, int(c.test_crop_size), float(c.crop_pct or 1.0))
+        mine = list(range(self.rank, len(TSVFile(tsv)), self.world))
+        executor = L.decode_executor(workers, threads, env.get('VITCAP_LOADER_CPUS'))
+        return L.PredictBatchLoader(tsv, mine, bs, chunk, plan, executor, L.SlabPool(plan, slab_bytes, dev), device_jpeg, pre)
 
     def test_image_tsv(self):
         """Image rows of the test set: `test_image_tsv: <file>` or the reference layout data/<test_data>/<split>.tsv
@@ -705,120 +575,34 @@ class CaptionUniPipeline(object):
         dev = torch.device('cuda', self.local_rank)
         model.pack(dev)
         sub = predict_result_file if self.world == 1 else '{}_{}_{}.tsv'.format(predict_result_file, self.rank, self.world)
-        from .tsv import TSVFile, tsv_writer
-
-        te = model.test_extra_input
-        overlap = not te.get('do_sample', False)
-        # the same option validation ImageCaptioning.forward applies (max_length, repetition_penalty, num_keep_best, use_cbs,
-        # token ids ...): an option this build does not implement raises here instead of being decoded with defaults
-        base = model.gen_options(gemm_mode=1) if overlap else None
-        popts = {}                                # vitcap_gen_opts per number of visible tag slots: the caller's mask decides
-
-        def opts_for(n_tag):
-            if n_tag not in popts:
-                if base.tag_visible and n_tag != base.tag_visible:
-                    raise ValueError('test_extra_input tag_visible=%d but the attention_mask shows %d tag slots' % (base.tag_visible, n_tag))
-                popts[n_tag] = base if n_tag == base.tag_visible else model.gen_options(gemm_mode=1, tag_visible=n_tag)
-            return popts[n_tag]
-
-        seen = {'n': None}                        # visible tag slots of the last batch whose text tensors live on the device
-
-        def collect(entry):
-            b, out, flag, expect_n = entry
-            t_c0 = time.perf_counter()
-            out = out.result() if overlap else out          # synchronises with the batch's decode stream
-            LOADER_TIMES['consumer_wait_gpu'] = LOADER_TIMES.get('consumer_wait_gpu', 0.0) + time.perf_counter() - t_c0
-            if flag is not None and not bool(flag):
-                # the device-side comparison against the count of the earlier batches failed: either this batch's (valid) mask shows
-                # another number of visible tag slots -- then it is decoded again with the options of ITS count, as a host-resident
-                # batch would have been from the start -- or the mask is not one the engine implements
-                n_tag = model.check_text_inputs(b, base.max_length)         # raises NotImplementedError for an unsupported mask
-                # compared with the count THIS batch was submitted against (one batch is always in flight: by now `seen` may already
-                # hold the count an earlier re-decode found -- ADVICE r4)
-                if n_tag == expect_n:
-                    raise NotImplementedError('a batch\'s attention_mask / token_type_ids on the device do not describe the mask structure '
-                                              'the HIP engine implements (ImageCaptioning.check_text_inputs)')
-                logging.info('visible tag slots changed from %s to %d: batch decoded again with its own options', expect_n, n_tag)
-                seen['n'] = n_tag
-                out = model.generate_async(b['image'], opts=opts_for(n_tag)).result()
-            t_c1 = time.perf_counter()
-            rows = list(self.predict_output_to_tsv_row(b, (out[0].cpu(), out[1].cpu())))
-            LOADER_TIMES['consumer_rows'] = LOADER_TIMES.get('consumer_rows', 0.0) + time.perf_counter() - t_c1
-            return rows
-
-        def gen_rows():
-            pending = []                          # greedy / beam: batch i decodes while batch i+1 is encoded (generate_async)
-            with torch.no_grad():
-                # batches queued on the device: capped in IMAGES (24 batches of 64 = 1 536 images = 1.4 GB of bf16 crops; the same count of
-                # 512-image batches would be 11 GB)
-                depth = int(self.cfg.loader_prefetch or os.environ.get('VITCAP_LOADER_PREFETCH', 0)) or max(2, min(24, 1536 // max(1, int(self.cfg.test_batch_size))))
-                for batch in _prefetched(self.iter_test_batches(), dev, depth=depth):
-                    batch = dict(batch)
-                    batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
-                    flag = None
-                    expect_n = None
-                    if overlap:
-                        # host tensors (what the loader yields) are checked on the host; tensors already on the device cost ONE host
-                        # synchronisation (the first batch, to read the number of visible tag slots), afterwards they are compared on
-                        # their stream and the verdict is read when the batch's captions are collected -- nothing stalls the
-                        # 2-slot pipeline
-                        am = batch.get('attention_mask')
-                        if am is not None and am.is_cuda and seen['n'] is not None:
-                            expect_n = seen['n']
-                            n_tag, flag = model.check_text_inputs(batch, base.max_length, expect_n_tag=expect_n)
-                        else:
-                            n_tag = model.check_text_inputs(batch, base.max_length)
-                            if am is not None and am.is_cuda:
-                                seen['n'] = n_tag
-                        t_s0 = time.perf_counter()
-                        out = model.generate_async(batch['image'], opts=opts_for(n_tag))
-                        LOADER_TIMES['consumer_submit'] = LOADER_TIMES.get('consumer_submit', 0.0) + time.perf_counter() - t_s0
-                    else:
-                        out = model(batch)
-                    pending.append((batch, out, flag, expect_n))
-                    # TWO batches stay in flight behind the one just submitted: batch k-2 is collected (its decode finished before
-                    # batch k-1's started) while k-1 decodes and k encodes, so the detokeniser / JSON / TSV work of this thread (~5 ms
-                    # per 64 captions) never sits between two submissions -- with one batch in flight the GPU ran batch k's decode
-                    # alone while this thread was still writing batch k-1's rows (round 5: 21 vs 16 ms per batch from disk).  The
-                    # outputs of a batch are its own tensors; its workspace slot is re-used by batch k+1 behind a stream-side wait.
-                    while len(pending) > (2 if overlap else 0):
-                        for key, js in collect(pending.pop(0)):
-                            yield key, js
-                for entry in pending:
-                    for key, js in collect(entry):
-                        yield key, js
+        from .tsv import tsv_writer
+        run = _PredictRun(self, model)
+        # batches queued on the device: capped in IMAGES (24 batches of 64 = 1 536 images = 1.4 GB of bf16 crops; the same count of
+        # 512-image batches would be 11 GB)
+        depth = int(self.cfg.loader_prefetch or os.environ.get('VITCAP_LOADER_PREFETCH', 0)) or max(2, min(24, 1536 // max(1, int(self.cfg.test_batch_size))))
         LOADER_TIMES.clear()
-        stats = {'rows': 0, 't_first': None, 'rows_first': 0}
-
-        def timed_rows():
-            # images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
-            # workers running) to the last row -- the figure the reference's trainer logs as images/sec (trainer.py:155-170)
-            for row in gen_rows():
-                stats['rows'] += 1
-                if stats['t_first'] is None and stats['rows'] >= 2 * int(self.cfg.test_batch_size):
-                    stats['t_first'], stats['rows_first'] = time.perf_counter(), stats['rows']
-                yield row
-        tsv_writer(timed_rows(), sub)               # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
-        if stats['t_first'] is not None and stats['rows'] > stats['rows_first']:
-            dt = time.perf_counter() - stats['t_first']
-            LAST_PREDICT_STATS.update(rows=stats['rows'], steady_rows=stats['rows'] - stats['rows_first'], steady_seconds=dt, t_end=time.perf_counter(),
-                                      loader_seconds={k: round(v, 3) for k, v in LOADER_TIMES.items()},
-                                      images_per_sec=(stats['rows'] - stats['rows_first']) / dt)
-            logging.info('predict: %d rows, steady state %.1f images/sec on rank %d', stats['rows'], LAST_PREDICT_STATS['images_per_sec'], self.rank)
+        batches = prefetched(self.iter_test_batches(), dev, depth=depth)
+        tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)               # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
+        run.report()
         if self.world > 1:
-            import torch.distributed as dist
-            dist.barrier()
-            if self.rank == 0:      # concatenate and de-duplicate by key (uni_pipeline.py:816-831)
-                def merged():
-                    seen = set()
-                    for r in range(self.world):
-                        for row in TSVFile('{}_{}_{}.tsv'.format(predict_result_file, r, self.world)):
-                            if row[0] not in seen:
-                                seen.add(row[0])
-                                yield row
-                tsv_writer(merged(), predict_result_file)
-            dist.barrier()
+            self.merge_rank_files(predict_result_file)
         return predict_result_file
+
+    def merge_rank_files(self, predict_result_file):
+        """Rank 0 concatenates the ranks' files and de-duplicates by key (uni_pipeline.py:816-831); every rank waits for it."""
+        import torch.distributed as dist
+        from .tsv import TSVFile, tsv_writer
+        dist.barrier()
+        if self.rank == 0:
+            def merged():
+                seen = set()
+                for r in range(self.world):
+                    for row in TSVFile('{}_{}_{}.tsv'.format(predict_result_file, r, self.world)):
+                        if row[0] not in seen:
+                            seen.add(row[0])
+                            yield row
+            tsv_writer(merged(), predict_result_file)
+        dist.barrier()
 
     def ensure_predict(self, model_file=None):
         check_model_config(self.cfg, training=False)
