@@ -1,27 +1,9 @@
 // Greedy bookkeeping and tag top-k: row-wise scans over the 30522-wide vocabulary (HBM/L2-bound).
 #include "common.h"
 #include "rng.h"
+#include "select.h"
 
 namespace {
-
-struct ArgMax {
-  float v;
-  int i;
-};
-__device__ __forceinline__ ArgMax am_better(ArgMax a, ArgMax b) {
-  // larger value wins; on ties the LOWER index wins (torch.argmax / topk behaviour on CPU)
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-__device__ __forceinline__ ArgMax wave_argmax(ArgMax a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ArgMax b;
-    b.v = __shfl_xor(a.v, o, 64);
-    b.i = __shfl_xor(a.i, o, 64);
-    a = am_better(a, b);
-  }
-  return a;
-}
 
 __global__ void greedy_init_kernel(int64_t* ids, int32_t* unf, float* sum_lp, float* cnt, int B, int max_len, int bos,
                                    int pad, int32_t* live) {
@@ -36,363 +18,165 @@ __global__ void greedy_init_kernel(int64_t* ids, int32_t* unf, float* sum_lp, fl
 }
 
 // one 1024-thread workgroup per sequence
-__global__ __launch_bounds__(1024) void greedy_step_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                           int64_t* __restrict__ ids, int32_t* __restrict__ unf,
-                                                           float* __restrict__ sum_lp, float* __restrict__ cnt,
-                                                           float* __restrict__ logprob_out,
-                                                           float* __restrict__ margin_out, int64_t* __restrict__ raw_last,
-                                                           int t, int max_len, int eos, int pad, int32_t* __restrict__ live,
-                                                           VcEosExtra eos_x) {
-  __shared__ ArgMax s_am[16];
-  __shared__ float s_second[16];
-  __shared__ float s_sum[16];
-  __shared__ ArgMax s_best;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (unf[b] == 0) {
-    // finished sequence: tokens_to_add = pad, the score is frozen (modeling_utils.py:855-858, 873-877); the logits are not
-    // read -- once every sequence has finished the step's other kernels have not even produced them
-    if (tid == 0) {
-      ids[(size_t)b * max_len + t] = pad;
-      if (t == max_len - 1) {
-        if (raw_last) raw_last[b] = pad;
-        logprob_out[b] = sum_lp[b] / cnt[b];
-      }
-    }
-    return;
-  }
+__global__ __launch_bounds__(1024) void greedy_step_kernel(const float* __restrict__ logits, int ldl, int V, StepState st, int t) {
+  __shared__ float s_v[16], s_second[16], s_sum[16];
+  __shared__ int s_i[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  // a finished sequence's logits are not read -- once every sequence has finished the step's other kernels have not even produced them
+  if (st.skip_finished(b, t)) return;
   const float* row = logits + (size_t)b * ldl;
-  ArgMax best{-INFINITY, 0x7fffffff};
-  float second = -INFINITY;   // runner-up value (for the top-2 margin tap)
-  for (int i = tid; i < V; i += 1024) {
-    const float v = row[i];
-    if (v > best.v || (v == best.v && i < best.i)) {
-      second = fmaxf(second, best.v);
-      best.v = v;
-      best.i = i;
-    } else {
-      second = fmaxf(second, v);
-    }
-  }
-  // wave reduce keeping the runner-up
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ArgMax ob;
-    ob.v = __shfl_xor(best.v, o, 64);
-    ob.i = __shfl_xor(best.i, o, 64);
-    const float os = __shfl_xor(second, o, 64);
-    const ArgMax nb = am_better(best, ob);
-    second = fmaxf(fmaxf(second, os), (nb.i == best.i) ? ob.v : best.v);
-    best = nb;
-  }
-  if (lane == 0) { s_am[w] = best; s_second[w] = second; }
-  __syncthreads();
-  if (tid == 0) {
-    ArgMax bb = s_am[0];
-    float ss = s_second[0];
-    for (int k = 1; k < 16; ++k) {
-      const ArgMax nb = am_better(bb, s_am[k]);
-      ss = fmaxf(fmaxf(ss, s_second[k]), (nb.i == bb.i) ? s_am[k].v : bb.v);
-      bb = nb;
-    }
-    s_best = bb;
-    if (margin_out) margin_out[(size_t)b * max_len + t] = bb.v - ss;
-  }
-  __syncthreads();
-  const ArgMax bb = s_best;
+  Pick<true, false> best;                  // with the runner-up, for the top-2 margin tap
+  for (int i = tid; i < V; i += 1024) best.offer(row[i], i);
+  best = block_pick<16>(best, {s_v, s_i, s_second, nullptr});
   float se = 0.f;
-  for (int i = tid; i < V; i += 1024) se += expf(row[i] - bb.v);
-  se = wave_sum(se);
-  if (lane == 0) s_sum[w] = se;
-  __syncthreads();
-  if (tid == 0) {
-    float tot = 0.f;
-    for (int k = 0; k < 16; ++k) tot += s_sum[k];
-    const float lp = -logf(tot);                    // logit[tok] - max - log(sum exp(x - max)), tok is the max
-    const int u = unf[b];
-    const int add = u ? bb.i : pad;
-    float s = sum_lp[b] + lp * (float)u;
-    float c = cnt[b] + (float)u;
-    int nu = u * (vc_is_eos(add, eos, eos_x) ? 0 : 1);
-    int64_t outtok = add;
-    if (t == max_len - 1) {
-      if (raw_last) raw_last[b] = add;               // the token actually chosen, before the forced [SEP]
-      if (nu) outtok = eos;                          // modeling_utils.py:870-871
-      logprob_out[b] = s / c;                        // modeling_utils.py:873-877
-    }
-    ids[(size_t)b * max_len + t] = outtok;
-    sum_lp[b] = s;
-    cnt[b] = c;
-    unf[b] = nu;
-    if (live && u && !nu) atomicSub(live, 1);
-  }
+  for (int i = tid; i < V; i += 1024) se += expf(row[i] - best.v);
+  const float tot = block_sum<16>(se, s_sum);
+  // log-prob = logit[tok] - max - log(sum exp(x - max)), tok is the max
+  if (tid == 0) st.commit(b, t, best.i, -logf(tot), best.v - best.second);
 }
 
 
 // ---- sampling step (do_sample): temperature, top-k / top-p filtering, one draw per sequence ----------------------
 // One 1024-thread workgroup per sequence; the whole 30522-wide row lives in registers (30 values per thread).
 constexpr int SM_NPT = 30;
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // unsigned order == float order
-}
+struct SampleArgs {
+  const float* logits;
+  int ldl, V;
+  float temperature;
+  int top_k;
+  float top_p;
+  uint32_t seed;
+  int seq_off;      // row b draws from the stream of sequence b + seq_off of the call
+};
+struct SampleLds {
+  RadixLds radix;
+  float f[16];
+};
 
-// MSB-first radix selection over the order keys: returns the largest key `thr` such that the total weight of the
-// elements with key > thr is <= T while adding the elements equal to thr would exceed T -- i.e. "keep key >= thr".
-// With unit weights and T = k-1 this is the k-th largest value (top-k keeps ties, like `logits < kth` removes);
-// with weights = probability mass and T = top_p it is the nucleus boundary (an element is kept iff the mass ranked
-// strictly above it is <= top_p, modeling_utils.py:1119-1131).  Integer weights make the sums order-independent.
-#define SM_RADIX_SELECT(THR, WEIGHT_EXPR, T)                                                   \
-  {                                                                                            \
-    uint32_t prefix_ = 0, pmask_ = 0;                                                          \
-    unsigned long long acc_ = 0;                                                               \
-    for (int pass_ = 0; pass_ < 4; ++pass_) {                                                  \
-      const int shift_ = 24 - 8 * pass_;                                                       \
-      if (tid < 256) s_hist[tid] = 0;                                                          \
-      __syncthreads();                                                                         \
-      _Pragma("unroll") for (int j = 0; j < SM_NPT; ++j) {                                     \
-        if ((key[j] & pmask_) == prefix_ && key[j] != 0) {                                     \
-          const unsigned long long w_ = (WEIGHT_EXPR);                                         \
-          if (w_) atomicAdd(&s_hist[(key[j] >> shift_) & 255u], w_);                           \
-        }                                                                                      \
-      }                                                                                        \
-      __syncthreads();                                                                         \
-      if (tid == 0) {                                                                          \
-        unsigned long long a_ = acc_;                                                          \
-        int d_ = 255;                                                                          \
-        for (; d_ > 0; --d_) {                                                                 \
-          if (a_ + s_hist[d_] > (T)) break;                                                    \
-          a_ += s_hist[d_];                                                                    \
-        }                                                                                      \
-        s_sel = (uint32_t)d_;                                                                  \
-        s_acc = a_;                                                                            \
-      }                                                                                        \
-      __syncthreads();                                                                         \
-      prefix_ |= s_sel << shift_;                                                              \
-      pmask_ |= 255u << shift_;                                                                \
-      acc_ = s_acc;                                                                            \
-      __syncthreads();                                                                         \
-    }                                                                                          \
-    THR = prefix_;                                                                             \
-  }
-
-// BEAM = true: the do_sample branch of beam search (modeling_utils.py:966-985).  Same temperature / filter, with
-// min_tokens_to_keep = `min_keep` (k = max(top_k, min_keep); ranks 0..min_keep always survive top-p, 1125-1130), then TWO draws
-// without replacement (the two largest of x + Gumbel noise == torch.multinomial(p, 2)); written per row: the two words, their
-// temperature-scaled logits and the log-sum-exp of the surviving set (so log_softmax(filtered)[word] = value - lse).
-template <bool BEAM>
-__global__ __launch_bounds__(1024) void sample_step_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                           int64_t* __restrict__ ids, int32_t* __restrict__ unf,
-                                                           float* __restrict__ sum_lp, float* __restrict__ cnt,
-                                                           float* __restrict__ logprob_out,
-                                                           float* __restrict__ margin_out, int64_t* __restrict__ raw_last,
-                                                           int t, int max_len, int eos, int pad, float temperature, int top_k,
-                                                           float top_p, uint32_t seed, int seq_off, int32_t* __restrict__ live,
-                                                           int min_keep, float* __restrict__ cand_val,
-                                                           int32_t* __restrict__ cand_idx, float* __restrict__ cand_lse,
-                                                           VcEosExtra eos_x) {
-  __shared__ unsigned long long s_hist[256];
-  __shared__ unsigned long long s_acc;
-  __shared__ uint32_t s_sel;
-  __shared__ float s_f[16];
-  __shared__ float s_bcast;
-  __shared__ ArgMax s_am[16];
-  __shared__ float s_second[16];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (BEAM) {
-    if (live && *live == 0) return;     // every image's search has closed
-  } else if (unf[b] == 0) {             // finished sequence: pad, frozen score (see greedy_step_kernel)
-    if (tid == 0) {
-      ids[(size_t)b * max_len + t] = pad;
-      if (t == max_len - 1) {
-        if (raw_last) raw_last[b] = pad;
-        logprob_out[b] = sum_lp[b] / cnt[b];
-      }
-    }
-    return;
-  }
-  const float* row = logits + (size_t)b * ldl;
-  float x[SM_NPT];
-  uint32_t key[SM_NPT];      // 0 = absent (column >= V)
+// The front end both sampling kernels share: row b scaled by 1 / temperature into x (element j = column tid + 1024 j; key = its
+// order key, 0 beyond V), top-k with k = max(top_k, min_keep), top-p keeping ranks 0..min_keep whatever their mass
+// (min_tokens_to_keep, modeling_utils.py:1125-1130).  Survivors are the elements with key >= the returned threshold;
+// m = their maximum, z = sum exp(x - m) over them.
+__device__ __forceinline__ uint32_t sample_filter(const SampleArgs& a, int b, int min_keep, float (&x)[SM_NPT],
+                                                   uint32_t (&key)[SM_NPT], float& m, float& z, SampleLds& lds) {
+  const int tid = threadIdx.x;
+  const float* row = a.logits + (size_t)b * a.ldl;
 #pragma unroll
   for (int j = 0; j < SM_NPT; ++j) {
     const int i = tid + j * 1024;
-    float v = i < V ? row[i] : -INFINITY;
-    if (temperature != 1.0f) v = v / temperature;
+    float v = i < a.V ? row[i] : -INFINITY;
+    if (a.temperature != 1.0f) v = v / a.temperature;
     x[j] = v;
-    key[j] = i < V ? order_key(v) : 0u;
+    key[j] = i < a.V ? order_key(v) : 0u;
   }
-  // ---- top-k -------------------------------------------------------------------------------------------------
   uint32_t thr = 1u;                                       // keep every present element
-  if (top_k > 0) {
-    if (top_k < min_keep) top_k = min_keep;
-    const unsigned long long kk = (unsigned long long)(top_k < V ? top_k : V) - 1ull;
-    uint32_t tk;
-    SM_RADIX_SELECT(tk, 1ull, kk);
+  if (a.top_k > 0) {
+    const int top_k = a.top_k < min_keep ? min_keep : a.top_k;
+    const uint32_t tk = radix_select(key, [](int) { return 1ull; }, (unsigned long long)(top_k < a.V ? top_k : a.V) - 1ull, lds.radix);
     thr = tk > thr ? tk : thr;
   }
-  // ---- softmax statistics of the surviving set ------------------------------------------------------------------
-  float m = -INFINITY;
+  // softmax statistics of the surviving set
+  auto mass = [&](uint32_t from) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < SM_NPT; ++j) if (key[j] >= from) s += expf(x[j] - m);
+    return block_sum<16>(s, lds.f);
+  };
+  m = -INFINITY;
 #pragma unroll
   for (int j = 0; j < SM_NPT; ++j) if (key[j] >= thr) m = fmaxf(m, x[j]);
-  m = wave_max(m);
-  if (lane == 0) s_f[w] = m;
-  __syncthreads();
-  if (tid == 0) { float mm = s_f[0]; for (int k = 1; k < 16; ++k) mm = fmaxf(mm, s_f[k]); s_bcast = mm; }
-  __syncthreads();
-  m = s_bcast;
-  __syncthreads();
-  float z = 0.f;
-#pragma unroll
-  for (int j = 0; j < SM_NPT; ++j) if (key[j] >= thr) z += expf(x[j] - m);
-  z = wave_sum(z);
-  if (lane == 0) s_f[w] = z;
-  __syncthreads();
-  if (tid == 0) { float zz = 0.f; for (int k = 0; k < 16; ++k) zz += s_f[k]; s_bcast = zz; }
-  __syncthreads();
-  z = s_bcast;
-  __syncthreads();
-  // ---- top-p (nucleus) ---------------------------------------------------------------------------------------
-  if (top_p < 1.0f) {
+  m = block_max<16>(m, lds.f);
+  z = mass(thr);
+  if (a.top_p < 1.0f) {                                    // nucleus
     const float scale = 1099511627776.0f / z;              // 2^40 / Z: probabilities as 40-bit fixed point
-    const unsigned long long P = (unsigned long long)((double)top_p * 1099511627776.0);
-    uint32_t tp;
+    const unsigned long long P = (unsigned long long)((double)a.top_p * 1099511627776.0);
     const uint32_t thr_k = thr;
-    SM_RADIX_SELECT(tp, (key[j] >= thr_k ? (unsigned long long)(expf(x[j] - m) * scale) : 0ull), P);
+    uint32_t tp = radix_select(key, [&](int j) { return key[j] >= thr_k ? (unsigned long long)(expf(x[j] - m) * scale) : 0ull; }, P,
+                               lds.radix);
     if (min_keep > 1) {                                    // ranks 0..min_keep stay whatever their mass
-      uint32_t tm;
-      SM_RADIX_SELECT(tm, (key[j] >= thr_k ? 1ull : 0ull), (unsigned long long)min_keep);
+      const uint32_t tm = radix_select(key, [&](int j) { return key[j] >= thr_k ? 1ull : 0ull; }, (unsigned long long)min_keep,
+                                       lds.radix);
       tp = tm < tp ? tm : tp;
     }
     if (tp > thr) {
       thr = tp;
-      z = 0.f;                                             // renormalise over the nucleus
-#pragma unroll
-      for (int j = 0; j < SM_NPT; ++j) if (key[j] >= thr) z += expf(x[j] - m);
-      z = wave_sum(z);
-      if (lane == 0) s_f[w] = z;
-      __syncthreads();
-      if (tid == 0) { float zz = 0.f; for (int k = 0; k < 16; ++k) zz += s_f[k]; s_bcast = zz; }
-      __syncthreads();
-      z = s_bcast;
+      z = mass(thr);                                       // renormalise over the nucleus
     }
   }
-  const uint32_t hrow = vc_mix(vc_mix(seed, (uint32_t)(b + seq_off)), (uint32_t)t);   // stream of sequence b + seq_off of the call
-  if (BEAM) {
-    // ---- two draws without replacement: the largest, then the largest of the rest, of x + Gumbel noise ----------------
-    float sc[SM_NPT];
-#pragma unroll
-    for (int j = 0; j < SM_NPT; ++j) {
-      const int i = tid + j * 1024;
-      sc[j] = key[j] >= thr ? x[j] - logf(-logf(vc_uniform(vc_mix(hrow, (uint32_t)i)))) : -INFINITY;
-    }
-    int excl = -1;
-    for (int d = 0; d < 2; ++d) {
-      ArgMax best{-INFINITY, 0x7fffffff};
-      float bx = 0.f;
-#pragma unroll
-      for (int j = 0; j < SM_NPT; ++j) {
-        const int i = tid + j * 1024;
-        if (key[j] >= thr && i != excl && (sc[j] > best.v || (sc[j] == best.v && i < best.i))) { best.v = sc[j]; best.i = i; bx = x[j]; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        ArgMax ob;
-        ob.v = __shfl_xor(best.v, o, 64);
-        ob.i = __shfl_xor(best.i, o, 64);
-        const float obx = __shfl_xor(bx, o, 64);
-        const ArgMax nb = am_better(best, ob);
-        bx = (nb.i == best.i) ? bx : obx;
-        best = nb;
-      }
-      __syncthreads();
-      if (lane == 0) { s_am[w] = best; s_f[w] = bx; }
-      __syncthreads();
-      ArgMax bb = s_am[0];
-      float xx = s_f[0];
-      for (int k = 1; k < 16; ++k) {
-        const ArgMax nb = am_better(bb, s_am[k]);
-        xx = (nb.i == bb.i) ? xx : s_f[k];
-        bb = nb;
-      }
-      excl = bb.i;
-      if (tid == 0) {
-        cand_val[(size_t)b * 2 + d] = xx;
-        cand_idx[(size_t)b * 2 + d] = bb.i;
-      }
-    }
-    if (tid == 0) cand_lse[b] = m + logf(z);
-    return;
-  }
-  // ---- one draw: argmax(x + Gumbel noise) over the surviving set == multinomial(softmax(filtered)) ----------
-  ArgMax best{-INFINITY, 0x7fffffff};
-  float bx = 0.f, second = -INFINITY;
+  return thr;
+}
+// noise stream of row b at step t, and the score of its column i: x + Gumbel noise, so that argmax == multinomial(softmax(x))
+__device__ __forceinline__ uint32_t sample_stream(const SampleArgs& a, int b, int t) {
+  return vc_mix(vc_mix(a.seed, (uint32_t)(b + a.seq_off)), (uint32_t)t);
+}
+__device__ __forceinline__ float gumbel_score(float x, uint32_t hrow, int i) {
+  return x - logf(-logf(vc_uniform(vc_mix(hrow, (uint32_t)i))));
+}
+
+// one draw: argmax(x + Gumbel noise) over the surviving set == multinomial(softmax(filtered)), then the step's bookkeeping
+__global__ __launch_bounds__(1024) void sample_step_kernel(SampleArgs a, StepState st, int t) {
+  __shared__ SampleLds lds;
+  __shared__ float s_v[16], s_second[16];
+  __shared__ int s_i[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (st.skip_finished(b, t)) return;
+  float x[SM_NPT], m, z;
+  uint32_t key[SM_NPT];
+  const uint32_t thr = sample_filter(a, b, 1, x, key, m, z, lds);
+  const uint32_t hrow = sample_stream(a, b, t);
+  Pick<true, true> best;                   // runner-up for the margin; payload = the winner's unperturbed logit
 #pragma unroll
   for (int j = 0; j < SM_NPT; ++j) {
     const int i = tid + j * 1024;
-    if (key[j] >= thr) {
-      const float u = vc_uniform(vc_mix(hrow, (uint32_t)i));
-      const float sc = x[j] - logf(-logf(u));
-      if (sc > best.v || (sc == best.v && i < best.i)) {
-        second = fmaxf(second, best.v);
-        best.v = sc; best.i = i; bx = x[j];
-      } else {
-        second = fmaxf(second, sc);
-      }
-    }
+    if (key[j] >= thr) best.offer(gumbel_score(x[j], hrow, i), i, x[j]);
   }
+  best = block_pick<16>(best, {s_v, s_i, s_second, lds.f});
+  // log_softmax of the FILTERED, temperature-scaled logits
+  if (tid == 0) st.commit(b, t, best.i, best.x - m - logf(z), best.v - best.second);
+}
+
+// The do_sample branch of beam search (modeling_utils.py:966-985): the same filter with min_tokens_to_keep = 2, then TWO draws
+// without replacement (the two largest of x + Gumbel noise == torch.multinomial(p, 2)); written per row: the two words, their
+// temperature-scaled logits and the log-sum-exp of the surviving set (so log_softmax(filtered)[word] = value - lse).
+__global__ __launch_bounds__(1024) void beam_sample_kernel(SampleArgs a, int t, const int32_t* __restrict__ live,
+                                                           float* __restrict__ cand_val, int32_t* __restrict__ cand_idx,
+                                                           float* __restrict__ cand_lse) {
+  VC_LIVE_EXIT(live);                      // every image's search has closed
+  __shared__ SampleLds lds;
+  __shared__ float s_v[16];
+  __shared__ int s_i[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float x[SM_NPT], m, z;
+  uint32_t key[SM_NPT];
+  const uint32_t thr = sample_filter(a, b, 2, x, key, m, z, lds);
+  const uint32_t hrow = sample_stream(a, b, t);
+  float sc[SM_NPT];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ArgMax ob;
-    ob.v = __shfl_xor(best.v, o, 64);
-    ob.i = __shfl_xor(best.i, o, 64);
-    const float obx = __shfl_xor(bx, o, 64);
-    const float os = __shfl_xor(second, o, 64);
-    const ArgMax nb = am_better(best, ob);
-    second = fmaxf(fmaxf(second, os), (nb.i == best.i) ? ob.v : best.v);
-    bx = (nb.i == best.i) ? bx : obx;
-    best = nb;
-  }
-  if (lane == 0) { s_am[w] = best; s_second[w] = second; s_f[w] = bx; }
-  __syncthreads();
-  if (tid == 0) {
-    ArgMax bb = s_am[0];
-    float ss = s_second[0], xx = s_f[0];
-    for (int k = 1; k < 16; ++k) {
-      const ArgMax nb = am_better(bb, s_am[k]);
-      ss = fmaxf(fmaxf(ss, s_second[k]), (nb.i == bb.i) ? s_am[k].v : bb.v);
-      xx = (nb.i == bb.i) ? xx : s_f[k];
-      bb = nb;
+  for (int j = 0; j < SM_NPT; ++j) sc[j] = key[j] >= thr ? gumbel_score(x[j], hrow, tid + j * 1024) : -INFINITY;
+  int excl = -1;
+  for (int d = 0; d < 2; ++d) {            // the largest, then the largest of the rest
+    Pick<false, true> best;
+#pragma unroll
+    for (int j = 0; j < SM_NPT; ++j) {
+      const int i = tid + j * 1024;
+      if (key[j] >= thr && i != excl) best.offer(sc[j], i, x[j]);
     }
-    if (margin_out) margin_out[(size_t)b * max_len + t] = bb.v - ss;
-    const float lp = xx - m - logf(z);                   // log_softmax of the FILTERED, temperature-scaled logits
-    const int u = unf[b];
-    const int add = u ? bb.i : pad;
-    float s = sum_lp[b] + lp * (float)u;
-    float c = cnt[b] + (float)u;
-    int nu = u * (vc_is_eos(add, eos, eos_x) ? 0 : 1);
-    int64_t outtok = add;
-    if (t == max_len - 1) {
-      if (raw_last) raw_last[b] = add;               // the token actually chosen, before the forced [SEP]
-      if (nu) outtok = eos;
-      logprob_out[b] = s / c;
+    __syncthreads();
+    best = block_pick<16>(best, {s_v, s_i, nullptr, lds.f});
+    excl = best.i;
+    if (tid == 0) {
+      cand_val[(size_t)b * 2 + d] = best.x;
+      cand_idx[(size_t)b * 2 + d] = best.i;
     }
-    ids[(size_t)b * max_len + t] = outtok;
-    sum_lp[b] = s;
-    cnt[b] = c;
-    unf[b] = nu;
-    if (live && u && !nu) atomicSub(live, 1);
   }
+  if (tid == 0) cand_lse[b] = m + logf(z);
 }
 
 // sigmoid + top-k (k <= 64), one 1024-thread workgroup per row; each thread keeps up to 32 candidates as sortable 64-bit keys
-// (tk_key below: larger value first, lower index on ties -- torch.topk's CPU order) and its own running maximum, so a round is
+// (tk_key, select.h: larger value first, lower index on ties -- torch.topk's CPU order) and its own running maximum, so a round is
 // one workgroup-wide max over 1024 cached values behind ONE barrier and a 32-element rescan by the one thread whose candidate was
 // taken (k rescans of every thread's 32 values behind two barriers were 122 us per batch of 64 rows).
 constexpr int TK_PER_THREAD = 32;
-__device__ __forceinline__ unsigned long long tk_key(float f, int i);
-__device__ __forceinline__ float tk_val(unsigned long long k);
-__device__ __forceinline__ int tk_idx(unsigned long long k);
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long a);
 __global__ __launch_bounds__(1024) void sigmoid_topk_kernel(const float* __restrict__ logits, int ldl, int V, int k,
                                                             float thresh, int64_t* __restrict__ out_ids,
                                                             float* __restrict__ out_prob,
@@ -447,30 +231,6 @@ __global__ __launch_bounds__(1024) void sigmoid_topk_kernel(const float* __restr
 //                         replays the reference's python candidate loop + BeamHypotheses (n_hyp = 1) on the device;
 //   beam_reorder_kernel : gathers the text K/V cache rows of the chosen parent beams.
 // ------------------------------------------------------------------------------------------------
-// (value, index) as ONE sortable 64-bit key: high word = the float mapped monotonically onto unsigned, low word = ~index, so
-// "larger value first, lower index on ties" (torch.topk on CPU) is a plain unsigned max -- one compare per element instead of
-// the two-field comparison (the k rescans of 32 register values per thread are what this kernel spends its time on).
-__device__ __forceinline__ unsigned long long tk_key(float f, int i) {
-  unsigned u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned)(~i);
-}
-__device__ __forceinline__ float tk_val(unsigned long long k) {
-  unsigned u = (unsigned)(k >> 32);
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ int tk_idx(unsigned long long k) { return (int)(~(unsigned)k); }
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)a, o, 64), hi = __shfl_xor((unsigned)(a >> 32), o, 64);
-    const unsigned long long b = ((unsigned long long)hi << 32) | lo;
-    a = b > a ? b : a;
-  }
-  return a;
-}
-
 __global__ __launch_bounds__(1024) void row_topk_lse_kernel(const float* __restrict__ logits, int ldl, int V, int k,
                                                             float* __restrict__ out_val, int* __restrict__ out_idx,
                                                             float* __restrict__ out_lse, const int32_t* __restrict__ live) {
@@ -498,14 +258,8 @@ __global__ __launch_bounds__(1024) void row_topk_lse_kernel(const float* __restr
     tmax = key[j] > tmax ? key[j] : tmax;
   }
   if (tid == 0) s_n = 0;
-  {
-    unsigned long long mine = tmax;                    // k best thread maxima of this wave
-    for (int r = 0; r < k; ++r) {
-      const unsigned long long best = wave_max_u64(mine);
-      if (lane == 0) s_cand[w][r] = best;
-      if (mine == best) mine = 0ull;
-    }
-  }
+  unsigned long long mine[1] = {tmax};                // k best thread maxima of this wave
+  wave_take_k(mine, k, [&](int r, unsigned long long best) { if (lane == 0) s_cand[w][r] = best; });
   __syncthreads();
   if (w == 0) {
     unsigned long long c[4];
@@ -514,18 +268,10 @@ __global__ __launch_bounds__(1024) void row_topk_lse_kernel(const float* __restr
       const int idx = lane + u * 64;
       c[u] = idx < 16 * k ? s_cand[idx / k][idx % k] : 0ull;
     }
-    unsigned long long best = 0ull;
-    for (int r = 0; r < k; ++r) {
-      best = c[0] > c[1] ? c[0] : c[1];
-      best = c[2] > best ? c[2] : best;
-      best = c[3] > best ? c[3] : best;
-      best = wave_max_u64(best);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c[u] == best) c[u] = 0ull;
-      if (r == 0 && lane == 0) s_cand[0][0] = best;    // the row maximum (slot reused; everyone has read the candidates)
-    }
-    if (lane == 0) s_thr = best;                       // k-th largest thread maximum (0 when the row has fewer than k values)
+    wave_take_k(c, k, [&](int r, unsigned long long best) {
+      if (lane == 0 && r == 0) s_cand[0][0] = best;    // the row maximum (slot reused; everyone has read the candidates)
+      if (lane == 0 && r == k - 1) s_thr = best;       // k-th largest thread maximum (0 when the row has fewer than k values)
+    });
   }
   __syncthreads();
   const unsigned long long thr = s_thr;
@@ -539,9 +285,7 @@ __global__ __launch_bounds__(1024) void row_topk_lse_kernel(const float* __restr
       if (pos < CAP) s_list[pos] = key[j];
     }
   }
-  se = wave_sum(se);
-  if (lane == 0) s_sum[w] = se;
-  __syncthreads();
+  const float tot = block_sum<16>(se, s_sum);         // its barrier also publishes the list
   if (w == 0) {
     const int n = s_n < CAP ? s_n : CAP;
     unsigned long long c[CAP / 64];
@@ -550,24 +294,13 @@ __global__ __launch_bounds__(1024) void row_topk_lse_kernel(const float* __restr
       const int idx = lane + u * 64;
       c[u] = idx < n ? s_list[idx] : 0ull;
     }
-    for (int r = 0; r < k; ++r) {
-      unsigned long long best = 0ull;
-#pragma unroll
-      for (int u = 0; u < CAP / 64; ++u) best = c[u] > best ? c[u] : best;
-      best = wave_max_u64(best);
+    wave_take_k(c, k, [&](int r, unsigned long long best) {
       if (lane == 0) {
         out_val[(size_t)b * k + r] = tk_val(best);
         out_idx[(size_t)b * k + r] = tk_idx(best);
       }
-#pragma unroll
-      for (int u = 0; u < CAP / 64; ++u)
-        if (c[u] == best) c[u] = 0ull;
-    }
-    if (lane == 0) {
-      float tot = 0.f;
-      for (int q = 0; q < 16; ++q) tot += s_sum[q];
-      out_lse[b] = rowmax + logf(tot);
-    }
+    });
+    if (lane == 0) out_lse[b] = rowmax + logf(tot);
   }
 }
 
@@ -605,24 +338,12 @@ __global__ __launch_bounds__(256) void row_topk_pieces_kernel(const float* __res
     mine[j] = key[j];
   }
   if (tid == 0) s_n = 0;
-  for (int r = 0; r < k; ++r) {                        // the k best piece keys of this wave
-    unsigned long long best = mine[0];
-#pragma unroll
-    for (int j = 1; j < PPT; ++j) best = mine[j] > best ? mine[j] : best;
-    best = wave_max_u64(best);
-    if (lane == 0) s_cand[w][r] = best;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j)
-      if (mine[j] == best) mine[j] = 0ull;
-  }
+  // the k best piece keys of this wave
+  wave_take_k(mine, k, [&](int r, unsigned long long best) { if (lane == 0) s_cand[w][r] = best; });
   __syncthreads();
   if (w == 0) {
-    unsigned long long c = lane < 4 * k ? s_cand[lane / k][lane % k] : 0ull;
-    for (int r = 0; r < k; ++r) {
-      const unsigned long long best = wave_max_u64(c);
-      if (lane == 0) s_sel[r] = best;
-      if (c == best) c = 0ull;
-    }
+    unsigned long long c[1] = {lane < 4 * k ? s_cand[lane / k][lane % k] : 0ull};
+    wave_take_k(c, k, [&](int r, unsigned long long best) { if (lane == 0) s_sel[r] = best; });
   }
   __syncthreads();
   const unsigned long long thr = s_sel[k - 1];
@@ -652,19 +373,13 @@ __global__ __launch_bounds__(256) void row_topk_pieces_kernel(const float* __res
       const int idx = lane + u * 64;
       c[u] = idx < n ? s_list[idx] : 0ull;
     }
-    for (int r = 0; r < k; ++r) {
-      unsigned long long best = 0ull;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) best = c[u] > best ? c[u] : best;
-      best = wave_max_u64(best);
+    wave_take_k(c, k, [&](int r, unsigned long long best) {
       if (lane == 0) {
         out_val[(size_t)b * k + r] = tk_val(best);
         out_idx[(size_t)b * k + r] = tk_idx(best);
       }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (c[u] == best) c[u] = 0ull;
-    }
+    });
+    // this site adds its four wave partials pairwise, not serially (block_sum would change the last bit): kept as it is
     if (lane == 0) out_lse[b] = rowmax + logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
   }
 }
@@ -940,8 +655,8 @@ extern "C" int vitcap_greedy_step(const float* logits, int ldl, int V, int64_t* 
                                   int B, int t, int max_len, int eos, int pad, void* stream) {
   VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out, "greedy_step: null pointer");
   VC_REQUIRE(B > 0 && V > 0 && ldl >= V && t >= 1 && t < max_len, "greedy_step: bad sizes (t=%d)", t);
-  hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V, ids, unfinished,
-                     sum_lp, cnt, logprob_out, margin_out, raw_last, t, max_len, eos, pad, (int32_t*)vc_tls_live, vc_tls_eos_extra);
+  hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V,
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad), t);
   VC_LAUNCH_CHECK("greedy_step");
   return VITCAP_OK;
 }
@@ -997,16 +712,23 @@ extern "C" int vitcap_beam_init(const vitcap_beam_state* s, int B, int K, int ma
   return VITCAP_OK;
 }
 
+// `who` = the entry point's name in the error texts; sampled candidates need two beams
+static int launch_beam_step(const char* who, int sampled, const float* cand_val, const int32_t* cand_idx, const float* lse,
+                            const vitcap_beam_state* s, int B, int K, int V, int t, int max_len, int eos, int pad,
+                            float length_penalty, void* stream) {
+  VC_REQUIRE(cand_val && cand_idx && lse && s && B > 0 && K >= (sampled ? 2 : 1) && K <= MAXBEAM, "%s: bad arguments", who);
+  VC_REQUIRE(t >= 1 && t < max_len && max_len <= 40, "%s: t=%d out of range (max_len %d <= 40)", who, t, max_len);
+  VC_REQUIRE(s->n_keep >= 1 && s->n_keep <= MAXBEAM, "%s: n_keep must be 1..%d (got %d)", who, MAXBEAM, s->n_keep);
+  hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_val, cand_idx, lse,
+                     make_state(s), B, K, V, t, max_len, eos, pad, length_penalty, (int32_t*)vc_tls_live, sampled);
+  VC_LAUNCH_CHECK(who);
+  return VITCAP_OK;
+}
+
 extern "C" int vitcap_beam_step(const float* cand_val, const int32_t* cand_idx, const float* lse,
                                 const vitcap_beam_state* s, int B, int K, int V, int t, int max_len, int eos, int pad,
                                 float length_penalty, void* stream) {
-  VC_REQUIRE(cand_val && cand_idx && lse && s && B > 0 && K >= 1 && K <= MAXBEAM, "beam_step: bad arguments");
-  VC_REQUIRE(t >= 1 && t < max_len && max_len <= 40, "beam_step: t=%d out of range (max_len %d <= 40)", t, max_len);
-  VC_REQUIRE(s->n_keep >= 1 && s->n_keep <= MAXBEAM, "beam_step: n_keep must be 1..%d (got %d)", MAXBEAM, s->n_keep);
-  hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_val, cand_idx, lse,
-                     make_state(s), B, K, V, t, max_len, eos, pad, length_penalty, (int32_t*)vc_tls_live, 0);
-  VC_LAUNCH_CHECK("beam_step");
-  return VITCAP_OK;
+  return launch_beam_step("beam_step", 0, cand_val, cand_idx, lse, s, B, K, V, t, max_len, eos, pad, length_penalty, stream);
 }
 
 // The same step on SAMPLED candidates (vitcap_beam_sample_candidates: cand_val / cand_idx [B*K][2], lse [B*K]): consumed in
@@ -1014,13 +736,7 @@ extern "C" int vitcap_beam_step(const float* cand_val, const int32_t* cand_idx, 
 extern "C" int vitcap_beam_step_sampled(const float* cand_val, const int32_t* cand_idx, const float* lse,
                                         const vitcap_beam_state* s, int B, int K, int V, int t, int max_len, int eos, int pad,
                                         float length_penalty, void* stream) {
-  VC_REQUIRE(cand_val && cand_idx && lse && s && B > 0 && K >= 2 && K <= MAXBEAM, "beam_step_sampled: bad arguments");
-  VC_REQUIRE(t >= 1 && t < max_len && max_len <= 40, "beam_step_sampled: t=%d out of range (max_len %d <= 40)", t, max_len);
-  VC_REQUIRE(s->n_keep >= 1 && s->n_keep <= MAXBEAM, "beam_step_sampled: n_keep must be 1..%d (got %d)", MAXBEAM, s->n_keep);
-  hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_val, cand_idx, lse,
-                     make_state(s), B, K, V, t, max_len, eos, pad, length_penalty, (int32_t*)vc_tls_live, 1);
-  VC_LAUNCH_CHECK("beam_step_sampled");
-  return VITCAP_OK;
+  return launch_beam_step("beam_step_sampled", 1, cand_val, cand_idx, lse, s, B, K, V, t, max_len, eos, pad, length_penalty, stream);
 }
 
 extern "C" int vitcap_beam_reorder_cache(const void* src, void* dst, const int32_t* parent, int layers, int NS,
@@ -1042,6 +758,15 @@ extern "C" int vitcap_beam_finalize(const vitcap_beam_state* s, int64_t* out_ids
   return VITCAP_OK;
 }
 
+static int check_sample_params(const char* who, const vitcap_sample_params* sp) {
+  VC_REQUIRE(sp->temperature > 0.f && sp->top_k >= 0 && sp->top_p > 0.f, "%s: temperature %g / top_k %d / top_p %g out of range", who,
+             (double)sp->temperature, sp->top_k, (double)sp->top_p);
+  return VITCAP_OK;
+}
+static SampleArgs sample_args(const float* logits, int ldl, int V, const vitcap_sample_params* sp, int seq_offset) {
+  return SampleArgs{logits, ldl, V, sp->temperature, sp->top_k, sp->top_p, sp->seed, seq_offset};
+}
+
 extern "C" int vitcap_sample_step_offset(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
                                          float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last,
                                          int B, int t, int max_len, int eos, int pad, const vitcap_sample_params* sp, int seq_offset,
@@ -1049,13 +774,9 @@ extern "C" int vitcap_sample_step_offset(const float* logits, int ldl, int V, in
   VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out && sp, "sample_step: null pointer");
   VC_REQUIRE(B > 0 && V > 0 && V <= SM_NPT * 1024 && ldl >= V && t >= 1 && t < max_len && seq_offset >= 0,
              "sample_step: bad sizes (V=%d t=%d)", V, t);
-  VC_REQUIRE(sp->temperature > 0.f && sp->top_k >= 0 && sp->top_p > 0.f,
-             "sample_step: temperature %g / top_k %d / top_p %g out of range", (double)sp->temperature, sp->top_k,
-             (double)sp->top_p);
-  hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V, ids, unfinished,
-                     sum_lp, cnt, logprob_out, margin_out, raw_last, t, max_len, eos, pad, sp->temperature, sp->top_k,
-                     sp->top_p, sp->seed, seq_offset, (int32_t*)vc_tls_live, 1, (float*)nullptr, (int32_t*)nullptr,
-                     (float*)nullptr, vc_tls_eos_extra);
+  if (const int rc = check_sample_params("sample_step", sp)) return rc;
+  hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, sample_args(logits, ldl, V, sp, seq_offset),
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad), t);
   VC_LAUNCH_CHECK("sample_step");
   return VITCAP_OK;
 }
@@ -1076,13 +797,9 @@ extern "C" int vitcap_beam_sample_candidates(const float* logits, int ldl, int V
   VC_REQUIRE(logits && sp && out_val && out_idx && out_lse, "beam_sample_candidates: null pointer");
   VC_REQUIRE(rows > 0 && V > 2 && V <= SM_NPT * 1024 && ldl >= V && t >= 1 && row_offset >= 0,
              "beam_sample_candidates: bad sizes (V=%d t=%d)", V, t);
-  VC_REQUIRE(sp->temperature > 0.f && sp->top_k >= 0 && sp->top_p > 0.f,
-             "beam_sample_candidates: temperature %g / top_k %d / top_p %g out of range", (double)sp->temperature, sp->top_k,
-             (double)sp->top_p);
-  hipLaunchKernelGGL(sample_step_kernel<true>, dim3(rows), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V,
-                     (int64_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (int64_t*)nullptr, t, 0, 0, 0, sp->temperature, sp->top_k, sp->top_p, sp->seed, row_offset,
-                     (int32_t*)vc_tls_live, 2, out_val, out_idx, out_lse, VcEosExtra{{-1, -1, -1}});
+  if (const int rc = check_sample_params("beam_sample_candidates", sp)) return rc;
+  hipLaunchKernelGGL(beam_sample_kernel, dim3(rows), dim3(1024), 0, (hipStream_t)stream, sample_args(logits, ldl, V, sp, row_offset),
+                     t, vc_tls_live, out_val, out_idx, out_lse);
   VC_LAUNCH_CHECK("beam_sample_candidates");
   return VITCAP_OK;
 }

@@ -4,6 +4,7 @@
 // instruction reads a contiguous 1 KiB.  Statistics are two-pass in registers (mean, then centred sum
 // of squares) in fp32, like ATen's CPU LayerNorm, then y = (x-mean)*rstd*gamma+beta.
 #include "common.h"
+#include "select.h"
 
 namespace {
 
@@ -71,12 +72,28 @@ __device__ __forceinline__ f32x4 ld_bf4(const bf16_t* p) {
                __uint_as_float(u.y & 0xffff0000u)};
 }
 
+// BertEmbeddings.forward for one row held by one wave (modeling_bert.py:222-237): (word[tok] + pos[p]) + type[0] -- the association
+// of `words + position + token_type` (:234) -- to `pre` (fp32, may be null), then LayerNorm to xf / xb (ln_row: either may be null).
+struct EmbedTables {
+  const bf16_t* word;
+  const bf16_t* pos;
+  const bf16_t* type;
+};
+__device__ __forceinline__ void embed_ln_row(int64_t tok, int p, const EmbedTables& tb, const float* gamma, const float* beta,
+                                             float eps, int lane, bf16_t* xb, float* xf, float* pre) {
+  f32x4 v[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int c = i * 256 + lane * 4;
+    v[i] = (ld_bf4(tb.word + (size_t)tok * D768 + c) + ld_bf4(tb.pos + (size_t)p * D768 + c)) + ld_bf4(tb.type + c);
+    if (pre) *(f32x4*)(pre + c) = v[i];
+  }
+  ln_row(v, gamma, beta, eps, lane, xb, xf);
+}
+
 // rows (b,0): word[ids[b][t-1]] + pos[t-1] + type[0];  rows (b,1): word[mask] + pos[t] + type[0]; then LN.
 __global__ __launch_bounds__(256) void embed_step_kernel(const int64_t* __restrict__ ids, int max_len, int t,
-                                                         int mask_token, const bf16_t* __restrict__ word,
-                                                         const bf16_t* __restrict__ pos,
-                                                         const bf16_t* __restrict__ type,
-                                                         const float* __restrict__ gamma,
+                                                         int mask_token, EmbedTables tb, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float eps,
                                                          float* __restrict__ xf, bf16_t* __restrict__ xb, int rows,
                                                          const int32_t* __restrict__ live) {
@@ -86,108 +103,50 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const int64_t* __restri
   if (row >= rows) return;
   const int b = row >> 1, which = row & 1;
   const int64_t tok = which ? (int64_t)mask_token : ids[(size_t)b * max_len + (t - 1)];
-  const int p = which ? t : t - 1;
-  f32x4 v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int c = i * 256 + lane * 4;
-    const f32x4 a = ld_bf4(word + (size_t)tok * D768 + c);
-    const f32x4 q = ld_bf4(pos + (size_t)p * D768 + c);
-    const f32x4 ty = ld_bf4(type + c);
-    v[i] = (a + q) + ty;   // same association as `words + position + token_type` (modeling_bert.py:234)
-  }
-  ln_row(v, gamma, beta, eps, lane, xb + (size_t)row * D768, xf + (size_t)row * D768);
+  embed_ln_row(tok, which ? t : t - 1, tb, gamma, beta, eps, lane, xb + (size_t)row * D768, xf + (size_t)row * D768, nullptr);
 }
 
 // Greedy token choice + bookkeeping for step t from the vocabulary GEMM's row statistics, fused with the text embedding of
 // step t+1.  One 128-thread workgroup per sequence.
 //   rowstat [B][pieces][4] = {max, argmax column (int bits), sum exp(x - max), -} per 32-column piece of the logits row:
 //   tok = column of the overall maximum, lowest column on ties (torch.argmax);  lp = log_softmax(row)[tok] =
-//   -log(sum_pieces s_p * exp(m_p - M));  then exactly greedy_step_kernel's bookkeeping (modeling_utils.py:850-877);
+//   -log(sum_pieces s_p * exp(m_p - M));  then the step's bookkeeping (StepState, select.h);
 //   rows (b,0) = word[ids[b][t]] + pos[t] + type[0], (b,1) = word[MASK] + pos[t+1] + type[0], LayerNorm -> x of step t+1.
-__global__ __launch_bounds__(128) void greedy_select_embed_kernel(const float* __restrict__ rowstat, int pieces,
-                                                                  int64_t* __restrict__ ids, int32_t* __restrict__ unf,
-                                                                  float* __restrict__ sum_lp, float* __restrict__ cnt,
-                                                                  float* __restrict__ logprob_out, int64_t* __restrict__ raw_last,
-                                                                  int t, int max_len, int eos, int pad, int32_t* __restrict__ live,
-                                                                  int mask_token, const bf16_t* __restrict__ word,
-                                                                  const bf16_t* __restrict__ pos, const bf16_t* __restrict__ type,
-                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                  float eps, float* __restrict__ xf, bf16_t* __restrict__ xb,
-                                                                  VcEosExtra eos_x) {
-  const bool last = t == max_len - 1;
-  if (live != nullptr && *live == 0 && !last) return;       // every sequence finished: ids stay PAD, x is not needed any more
+__global__ __launch_bounds__(128) void greedy_select_embed_kernel(const float* __restrict__ rowstat, int pieces, StepState st, int t,
+                                                                  int mask_token, EmbedTables tb, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps,
+                                                                  float* __restrict__ xf, bf16_t* __restrict__ xb) {
+  const bool last = t == st.max_len - 1;
+  if (st.live != nullptr && *st.live == 0 && !last) return;       // every sequence finished: ids stay PAD, x is not needed any more
   __shared__ float s_m[2], s_s[2];
   __shared__ int s_i[2];
   __shared__ long long s_tok;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int u = unf[b];
-  float M = 0.f, lp = 0.f;
-  int I = pad;
-  if (u) {
+  if (st.skip_finished(b, t)) {
+    if (tid == 0) s_tok = st.pad;
+  } else {
     const f32x4* rs = (const f32x4*)rowstat + (size_t)b * pieces;
-    float bm = -INFINITY;
-    int bi = 0x7fffffff;
+    Pick<false, false> best;
     for (int i = tid; i < pieces; i += 128) {
       const f32x4 r = rs[i];
-      const int idx = __float_as_int(r[1]);
-      if (r[0] > bm || (r[0] == bm && idx < bi)) { bm = r[0]; bi = idx; }
+      best.offer(r[0], __float_as_int(r[1]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(bm, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (om > bm || (om == bm && oi < bi)) { bm = om; bi = oi; }
-    }
-    if (lane == 0) { s_m[w] = bm; s_i[w] = bi; }
-    __syncthreads();
-    M = s_m[0];
-    I = s_i[0];
-    if (s_m[1] > M || (s_m[1] == M && s_i[1] < I)) { M = s_m[1]; I = s_i[1]; }
+    best = block_pick<2>(best, {s_m, s_i, nullptr, nullptr});
     float se = 0.f;
     for (int i = tid; i < pieces; i += 128) {
       const f32x4 r = rs[i];
-      se += r[2] * expf(r[0] - M);
+      se += r[2] * expf(r[0] - best.v);
     }
-    se = wave_sum(se);
-    if (lane == 0) s_s[w] = se;
-    __syncthreads();
-    lp = -logf(s_s[0] + s_s[1]);                              // logit[tok] - M - log(sum exp(x - M)), tok is the maximum
-  }
-  if (tid == 0) {
-    const int add = u ? I : pad;
-    const float s = sum_lp[b] + lp * (float)u;
-    const float c = cnt[b] + (float)u;
-    const int nu = u * (vc_is_eos(add, eos, eos_x) ? 0 : 1);
-    long long outtok = add;
-    if (last) {
-      if (raw_last) raw_last[b] = add;               // the token actually chosen, before the forced [SEP]
-      if (nu) outtok = eos;                          // modeling_utils.py:870-871
-      logprob_out[b] = s / c;                        // modeling_utils.py:873-877
-    }
-    ids[(size_t)b * max_len + t] = outtok;
-    sum_lp[b] = s;
-    cnt[b] = c;
-    unf[b] = nu;
-    if (live && u && !nu) atomicSub(live, 1);
-    s_tok = outtok;
+    // 0 + s0 + s1 == s0 + s1: the two wave partials are added as before.  logit[tok] - M - log(sum exp(x - M)), tok is the maximum
+    const float lp = -logf(block_sum<2>(se, s_s));
+    if (tid == 0) s_tok = st.commit(b, t, best.i, lp, 0.f);
   }
   if (last) return;
   __syncthreads();
-  // embedding of step t+1 (BertEmbeddings.forward, modeling_bert.py:222-237): wave 0 -> row (b,0), wave 1 -> row (b,1)
-  const long long tok = w ? (long long)mask_token : s_tok;
-  const int p = w ? t + 1 : t;
+  // embedding of step t+1: wave 0 -> row (b,0), wave 1 -> row (b,1)
   const int row = b * 2 + w;
-  f32x4 v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int c = i * 256 + lane * 4;
-    const f32x4 a = ld_bf4(word + (size_t)tok * D768 + c);
-    const f32x4 q = ld_bf4(pos + (size_t)p * D768 + c);
-    const f32x4 ty = ld_bf4(type + c);
-    v[i] = (a + q) + ty;   // same association as `words + position + token_type` (modeling_bert.py:234)
-  }
-  ln_row(v, gamma, beta, eps, lane, xb + (size_t)row * D768, xf + (size_t)row * D768);
+  embed_ln_row(w ? (long long)mask_token : s_tok, w ? t + 1 : t, tb, gamma, beta, eps, lane, xb + (size_t)row * D768,
+               xf + (size_t)row * D768, nullptr);
 }
 
 // Embeddings of the predicted tag tokens that ViTSplitCLSEmbModel.forward writes over the last 50 text slots
@@ -211,35 +170,22 @@ __global__ __launch_bounds__(256) void tag_embed_kernel(const int64_t* __restric
   const int64_t tok = j == 49 ? (int64_t)102 : tag_ids[(size_t)b * 50 + j];
   const bool extra = !branch_a && !tagemb_cls;
   const bf16_t* tab = tagemb_cls ? cls_w : (extra ? xword : word);
-  const bf16_t* ptab = extra ? xpos : pos;
-  const bf16_t* ttab = extra ? xtype : type;
   const int pbase = extra ? pos0 : 20;     // encode_tag_to_embedding's literal caption_len = 20 (:1381, :1396); the caller's position_ids reach bert.extra_embeddings only (:1484-1485)
-  f32x4 v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int c = i * 256 + lane * 4;
-    const f32x4 a = ld_bf4(tab + (size_t)tok * D768 + c);
-    if (branch_a && tagemb_cls) {
-      v[i] = a;
-    } else {
-      const f32x4 q = ld_bf4(ptab + (size_t)(pbase + j) * D768 + c);
-      const f32x4 ty = ld_bf4(ttab + c);
-      v[i] = (a + q) + ty;
-    }
-  }
   if (branch_a && tagemb_cls) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int c = i * 256 + lane * 4;
-      *(f32x4*)(xf + (size_t)row * D768 + c) = v[i];
+      const f32x4 v = ld_bf4(tab + (size_t)tok * D768 + c);
+      *(f32x4*)(xf + (size_t)row * D768 + c) = v;
       uint2 o;
-      o.x = pack2bf(v[i][0], v[i][1]);
-      o.y = pack2bf(v[i][2], v[i][3]);
+      o.x = pack2bf(v[0], v[1]);
+      o.y = pack2bf(v[2], v[3]);
       *(uint2*)(xb + (size_t)row * D768 + c) = o;
     }
     return;
   }
-  ln_row(v, extra ? xgamma : gamma, extra ? xbeta : beta, eps, lane, xb + (size_t)row * D768, xf + (size_t)row * D768);
+  embed_ln_row(tok, pbase + j, EmbedTables{tab, extra ? xpos : pos, extra ? xtype : type}, extra ? xgamma : gamma,
+               extra ? xbeta : beta, eps, lane, xb + (size_t)row * D768, xf + (size_t)row * D768, nullptr);
 }
 
 // dst[(b * dst_img_rows + dst_row0 + r) * ld_dst + dst_col0 + c] = src[(b * src_img_rows + src_row0 + r) * ld_src + src_col0 + c]
@@ -257,25 +203,17 @@ __global__ __launch_bounds__(256) void copy_row_blocks_kernel(const bf16_t* __re
 }
 
 // teacher-forced text rows: row r = word[ids[r]] + pos[r % rows_per_seq] + type[0] -> (pre-LN sum fp32, LN fp32, LN bf16)
-__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* __restrict__ ids, int rows_per_seq,
-                                                         const bf16_t* __restrict__ word, const bf16_t* __restrict__ pos,
-                                                         const bf16_t* __restrict__ type, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, float eps, float* __restrict__ pre,
-                                                         float* __restrict__ xf, bf16_t* __restrict__ xb, int rows, int pos_wrap) {
+__global__ __launch_bounds__(256) void embed_rows_kernel(const int64_t* __restrict__ ids, int rows_per_seq, EmbedTables tb,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                         float* __restrict__ pre, float* __restrict__ xf, bf16_t* __restrict__ xb,
+                                                         int rows, int pos_wrap) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int64_t tok = ids[row];
   int p = row % rows_per_seq;
   if (pos_wrap > 0 && p >= pos_wrap) p = p - pos_wrap + 1;     // probe rows: [MASK] at positions 1, 2, ...
-  f32x4 v[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int c = i * 256 + lane * 4;
-    v[i] = (ld_bf4(word + (size_t)tok * D768 + c) + ld_bf4(pos + (size_t)p * D768 + c)) + ld_bf4(type + c);
-    if (pre) *(f32x4*)(pre + (size_t)row * D768 + c) = v[i];
-  }
-  ln_row(v, gamma, beta, eps, lane, xb ? xb + (size_t)row * D768 : nullptr, xf ? xf + (size_t)row * D768 : nullptr);
+  embed_ln_row(ids[row], p, tb, gamma, beta, eps, lane, xb ? xb + (size_t)row * D768 : nullptr,
+               xf ? xf + (size_t)row * D768 : nullptr, pre ? pre + (size_t)row * D768 : nullptr);
 }
 
 // image [B,3,384,384] -> patches [B*576, 768], k = c*256 + kh*16 + kw.  One thread = 8 kw (16 B out).
@@ -370,7 +308,7 @@ extern "C" int vitcap_embed_step(const int64_t* ids, int max_len, int t, int mas
   VC_REQUIRE(t >= 1 && t < max_len && B > 0, "embed_step: bad t=%d (max_len %d) or B=%d", t, max_len, B);
   const int rows = 2 * B;
   hipLaunchKernelGGL(embed_step_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, max_len, t,
-                     mask_token, (const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb, gamma,
+                     mask_token, EmbedTables{(const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb}, gamma,
                      beta, eps, x_f32, (bf16_t*)x_bf16, rows, vc_tls_live);
   VC_LAUNCH_CHECK("embed_step");
   return VITCAP_OK;
@@ -385,10 +323,10 @@ extern "C" int vitcap_greedy_select_embed(const float* rowstat, int pieces, int6
   VC_REQUIRE(B > 0 && pieces > 0 && t >= 1 && t < max_len, "greedy_select_embed: bad sizes (t=%d, pieces=%d)", t, pieces);
   VC_REQUIRE(t == max_len - 1 || (word_emb && pos_emb && type_emb && gamma && beta && x_f32 && x_bf16),
              "greedy_select_embed: the embedding of step t+1 needs the tables and outputs");
-  hipLaunchKernelGGL(greedy_select_embed_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, rowstat, pieces, ids, unfinished,
-                     sum_lp, cnt, logprob_out, raw_last, t, max_len, eos, pad, (int32_t*)vc_tls_live, mask_token,
-                     (const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb, gamma, beta, eps, x_f32,
-                     (bf16_t*)x_bf16, vc_tls_eos_extra);
+  hipLaunchKernelGGL(greedy_select_embed_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, rowstat, pieces,
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, nullptr, max_len, eos, pad), t, mask_token,
+                     EmbedTables{(const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb}, gamma, beta, eps, x_f32,
+                     (bf16_t*)x_bf16);
   VC_LAUNCH_CHECK("greedy_select_embed");
   return VITCAP_OK;
 }
@@ -433,7 +371,7 @@ extern "C" int vitcap_embed_rows(const int64_t* ids, int rows_per_seq, const voi
                                  float* x_f32, void* x_bf16, int rows, int pos_wrap, void* stream) {
   VC_REQUIRE(ids && word_emb && pos_emb && type_emb && gamma && beta && rows > 0 && rows_per_seq > 0, "embed_rows: bad arguments");
   hipLaunchKernelGGL(embed_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, rows_per_seq,
-                     (const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb, gamma, beta, eps, pre_f32,
+                     EmbedTables{(const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb}, gamma, beta, eps, pre_f32,
                      x_f32, (bf16_t*)x_bf16, rows, pos_wrap);
   VC_LAUNCH_CHECK("embed_rows");
   return VITCAP_OK;
