@@ -1,6 +1,6 @@
 """Exact-match rate of the device's captions against every reference-produced fixture (GPU box):
 greedy: reference_population.npz (32 images); beam: the 5 beam goldens of reference_vectors.npz (7 images), the image-dependent
-beam-5 pair and the 8 population images.  Used to A/B kernel variants that move near ties (tools/exact_rate_ab.sh)."""
+beam-5 pair and the 8 population images.  Used to A/B kernel variants that move near ties: run it once per build."""
 import os
 import sys
 

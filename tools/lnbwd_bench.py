@@ -1,4 +1,4 @@
-"""LayerNorm backward at the encoder shape under VITCAP_LNBWD_WAVES (GPU box)."""
+"""LayerNorm backward at the encoder shape (GPU box)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,4 +18,4 @@ for name, dy in (('dy bf16', torch.randn(M, 768, device='cuda').to(torch.bfloat1
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 20 * 1e3
     byt = M * 768 * (4 + dy.element_size() + 4 + 4 + 2)
-    print('WAVES=%s %s: %.1f us, %.2f TB/s' % (os.environ.get('VITCAP_LNBWD_WAVES', '16'), name, us, byt / us / 1e6), flush=True)
+    print('%s: %.1f us, %.2f TB/s' % (name, us, byt / us / 1e6), flush=True)

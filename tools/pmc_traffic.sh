@@ -1,13 +1,13 @@
 #!/bin/bash
 # usage (on an MI355X): bash tools/pmc_traffic.sh <tag> [extra bench.py args, e.g. "--batch 512"]  -> HBM traffic per kernel (FETCH_SIZE / WRITE_SIZE in separate passes)
 TAG=$1
-EXTRA="$2"
+ARGS="$2"
 R=$(cd "$(dirname "$0")/.." && pwd)
 export OUT=${OUT:-$R/out}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/traffic_${TAG}_$c -o p -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --single-region --power 0 $EXTRA > $OUT/traffic_${TAG}_$c.log 2>&1
+rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/traffic_${TAG}_$c -o p -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --single-region --power 0 $ARGS > $OUT/traffic_${TAG}_$c.log 2>&1
 done
 cd $R
 python3 - $TAG <<'PY'

@@ -16,57 +16,23 @@
 //     makes the bf16 path reproducible by the CPU oracle's rounding emulation).
 // (2) attn_decode_step: 2 query rows per sequence against the cached visual K/V (read in place from
 //     the prefill's packed qkv buffer) plus the text K/V cache; HBM-bound, 8 lanes per key row.
-#include <stdlib.h>
-
-#include "common.h"
+#include "attn_common.h"
 #include "rng.h"
 
 namespace {
 
-constexpr int HD = 64;          // head dim
-constexpr int NH = 12;          // heads
-constexpr int QKV_LD = 2304;    // packed row: [q | k | v] x [head][64]
-constexpr int KT = 64;          // keys per tile
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
 typedef __attribute__((ext_vector_type(4))) int attn_i32x4;
 // one LDS-DMA piece through a buffer descriptor: 64 lanes x 16 B -> 1 KiB at the wave-uniform LDS byte address `lds`; global address =
-// descriptor base + per-lane voff + scalar soff.  Against glds16 (64-bit per-lane addresses) the per-tile address arithmetic moves from
+// descriptor base + per-lane voff + scalar soff.  Against glds16 (common.h: 64-bit per-lane addresses) the per-tile address arithmetic moves from
 // 8 v_lshl_add_u64 + 2 v_mad_i64_i32 per key tile to scalar adds (round 6: the loop is bound by vector-ALU issue and by the board's power).
 __device__ __forceinline__ void bufdma16(uint32_t lds, uint32_t voff, const attn_i32x4& rsrc, uint32_t soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-// 16-byte chunk c of LDS row r (128 B = one key's 64 head dims) is stored at chunk c ^ kv_swz(r): the 16-lane groups of the
-// K fragment reads (ds_read_b128: 16 different rows, one chunk) and the 32-lane groups of the V transpose reads
-// (ds_read_b64_tr_b16: 4 consecutive rows x 64 B) then touch every bank once (MI355X_MICROARCH.md, LDS).
-__device__ __forceinline__ int kv_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
-
-// build-time knobs of the dense kernel (tools/attn_variants.sh measures them; the defaults are the shipped form)
-#ifndef VC_ATTN_NSTG
-#define VC_ATTN_NSTG 3
-#endif
-#ifndef VC_ATTN_MINW
-#define VC_ATTN_MINW 3
-#endif
-#ifndef VC_ATTN_ROWSUM_MFMA
-#define VC_ATTN_ROWSUM_MFMA 1
-#endif
-#ifndef VC_ATTN_VEARLY
-#define VC_ATTN_VEARLY 1
-#endif
-#ifndef VC_ATTN_ABL           // timing ablations (tools/attn_variants.sh; results are WRONG when != 0): 1 no QK^T MFMAs, 2 no exp2 / convert
-#define VC_ATTN_ABL 0         // arithmetic, 4 no P.V / row-sum MFMAs, 8 no per-tile barrier, 16 no LDS-DMA after the first two tiles, 32 no V reads
-#endif
-constexpr int NSTG = VC_ATTN_NSTG;       // K/V tile ring: tile t+NSTG-1 is in flight while tile t is multiplied
-constexpr int TILE_B = KT * 128;         // one K (or V) tile: 64 keys x 128 B
+constexpr int NSTG = 3;                  // K/V tile ring: tile t+2 is in flight while tile t is multiplied
 constexpr int STG_B = 2 * TILE_B;        // [K | V]
+constexpr int DENSE_MINW = 3;            // waves per SIMD the dense kernel is compiled for
 
 // DROP: attention dropout of the decoder in training -- the probabilities that feed P.V are zeroed where
 // vc_drop_keep() says so and the output is scaled by 1/(1-p); the softmax statistics (and lse) are those of the
@@ -81,12 +47,20 @@ constexpr int STG_B = 2 * TILE_B;        // [K | V]
 // Row sums run through the matrix pipe as well: one more MFMA per 16-key block with an all-ones A operand accumulates
 // sum_k bf16(P) for the lane's query in every register of `lacc` (the loop is bound by vector-ALU issue; the matrix pipe
 // has room) -- so the normaliser is the sum of the ROUNDED probabilities the numerator uses.
+//
+// Variants that were build-time switches until the shipped form settled (measurements: docs/LAB_r01_r04.md 4.2 iii, "What did NOT matter" and
+// "Measured anatomy"; docs/LAB_refactor_kernel_switches.md names the last commit that builds them), all within +-2 % or slower:
+//   four waves per SIMD instead of three (128 VGPRs, which needs the ring of two K/V slots instead of three: timed as one variant);
+//   the row sum on the vector ALU (of the rounded or of the unrounded P) instead of the matrix pipe; the V transpose reads one 16-key
+//   block ahead of their MFMAs (16 fewer live registers) instead of all four blocks in front of the softmax.  The anatomy figures came from six timing ablations with wrong results by
+//   construction (no QK^T MFMAs, no exp2 / convert arithmetic, no P.V / row-sum MFMAs, no per-tile barrier, no LDS-DMA after the first
+//   two tiles, no V reads).
 template <bool DROP>
-__global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                         float* __restrict__ lse, int S, int B, int ld_rows, float c_log2,
-                                                         uint32_t drop_seed, uint32_t drop_thr, float drop_scale,
-                                                         int causal_from, int mask_from, int q_lo, int q_rows, int rev,
-                                                         const uint32_t* __restrict__ drop_salt) {
+__global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                                     float* __restrict__ lse, int S, int B, int ld_rows, float c_log2,
+                                                                     uint32_t drop_seed, uint32_t drop_thr, float drop_scale,
+                                                                     int causal_from, int mask_from, int q_lo, int q_rows, int rev,
+                                                                     const uint32_t* __restrict__ drop_salt) {
   __shared__ __attribute__((aligned(1024))) char smem[NSTG * STG_B];   // [stage][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -145,7 +119,9 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
       bufdma16(sl_ + 4096, s_off, kv_rsrc, so_ + 32 * QKV_LD * 2);                                              \
       bufdma16(sl_ + TILE_B, s_off, kv_rsrc, so_ + 768 * 2);                                                    \
       bufdma16(sl_ + TILE_B + 4096, s_off, kv_rsrc, so_ + 768 * 2 + 32 * QKV_LD * 2);                           \
-    } else { /* tail tile: rows past the sequence re-read its last row (their scores are masked) */            \
+    } else { /* tail tile: rows past the sequence re-read its last row (their scores are masked).  A deliberate  \
+                twin of attn_bwd.hip's dQ STAGE_TILE: one shared spelling moves the other file's instruction    \
+                order (docs/LAB_refactor_kernel_switches.md) */                                                 \
       const int r0_ = (t_) * KT + srow, r1_ = r0_ + 32;                                                         \
       const uint32_t c_ = (uint32_t)(768 * 2 + ((lane & 7) ^ kv_swz(srow)) * 16);                               \
       const char* a0_ = gbase + (size_t)(r0_ < S ? r0_ : S - 1) * (QKV_LD * 2) + c_;                            \
@@ -157,24 +133,9 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
     }                                                                                                           \
   } while (0)
 
-  // fragment read offsets inside a stage (per lane, fixed): K row qi (+32 kt), chunk (2 ds + half) ^ swz(qi);
-  // V transpose read rd of a 16-key block: lane supplies row 8 rd + 4 half + j (j = (lane & 15) >> 2), 8 bytes at dims
-  // 32 dt + 16 ((lane >> 4) & 1) + 4 (lane & 3)
-  int koff[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) koff[ds] = qi * 128 + (((2 * ds + half) ^ kv_swz(qi)) * 16);
-  int voff[2][2];
-  {
-    const int j = (lane & 15) >> 2;
-    const int c2 = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-#pragma unroll
-    for (int rd = 0; rd < 2; ++rd) {
-      const int r = 8 * rd + 4 * half + j;                       // row within the 16-key block (block base is a multiple of 16)
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-        voff[rd][dt] = TILE_B + r * 128 + (((c2 + 4 * dt) ^ kv_swz(r)) * 16) + (lane & 1) * 8;
-    }
-  }
+  // fragment read offsets inside a stage (attn_common.h): K rows qi (+32 kt); the V tile lies TILE_B behind the K tile
+  int koff[4], voff[2][2];
+  ATTN_READ_OFFSETS(koff, voff, TILE_B, lane, half);
 
   f32x16 ot[2], lacc;
 #pragma unroll
@@ -208,7 +169,7 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
       for (int g = 0; g < 4; ++g) lv[dt][g] = *(const bf16x4*)(vr + dt * 32 + g * 8);
   }
   if (ntiles > 0) STAGE_TILE(0, 0);
-  if (NSTG > 2 && ntiles > 1) STAGE_TILE(1, 1);
+  if (ntiles > 1) STAGE_TILE(1, 1);
   if (left) {
     for (int key = key0; key < S; ++key) {
       if (key > key0) {
@@ -253,7 +214,6 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
   do {                                                                                                          \
     const char* kl = smem + (stg_) * STG_B;                                                                     \
     f32x16 st[2];                                                                                               \
-    if (VC_ATTN_ABL & 1) { _Pragma("unroll") for (int r = 0; r < 16; ++r) { st[0][r] = (float)(r + qi) * 1e-3f; st[1][r] = (float)(r - qi) * 1e-3f; } } else { \
     /* all eight K fragments are requested before the first MFMA (left to itself hipcc reads them two at a time, each pair     \
        behind its own lgkmcnt(0): four exposed LDS round trips per tile; measured anatomy in docs/LAB_r01_r04.md 4.2 iii) */          \
     bf16x8 kfr[2][4];                                                                                           \
@@ -266,22 +226,17 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
       _Pragma("unroll") for (int ds = 1; ds < 4; ++ds)                                                          \
         st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kt][ds], qf[ds], st[kt], 0, 0, 0);                 \
     }                                                                                                           \
-    }                                                                                                           \
-    /* the transpose reads of this tile's V fragments go out now: their latency hides behind the softmax       \
-       (VC_ATTN_VEARLY; otherwise one 16-key block ahead of its MFMAs, 16 fewer live registers) */              \
-    s16x4 vt[VC_ATTN_VEARLY ? 4 : 2][2][2];                                                                     \
+    /* the transpose reads of this tile's four V fragments go out now: their latency hides behind the softmax */\
+    s16x4 vt[4][2][2];                                                                                          \
     const uint32_t vb_ = lds_addr(kl);                                                                          \
-    if (VC_ATTN_ABL & 32) { _Pragma("unroll") for (int i_ = 0; i_ < (VC_ATTN_VEARLY ? 4 : 2); ++i_) _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) vt[i_][dt][rd] = s16x4{(short)(0x3c00 + i_), (short)0x3c00, (short)(0x3c00 + dt), (short)(0x3c00 + rd)}; } else \
-    if (VC_ATTN_VEARLY) {                                                                                       \
-      _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                          \
-        _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                                      \
-          const uint32_t a_ = vb_ + (uint32_t)voff[rd][dt];                                                     \
-          vt[0][dt][rd] = lds_tr_read<0>(a_);                                                                   \
-          vt[1][dt][rd] = lds_tr_read<2048>(a_);                                                                \
-          vt[VC_ATTN_VEARLY ? 2 : 0][dt][rd] = lds_tr_read<4096>(a_);                                           \
-          vt[VC_ATTN_VEARLY ? 3 : 1][dt][rd] = lds_tr_read<6144>(a_);                                           \
-        }                                                                                                       \
-    }                                                                                                           \
+    _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                            \
+      _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                                        \
+        const uint32_t a_ = vb_ + (uint32_t)voff[rd][dt];                                                       \
+        vt[0][dt][rd] = lds_tr_read<0>(a_);                                                                     \
+        vt[1][dt][rd] = lds_tr_read<2048>(a_);                                                                  \
+        vt[2][dt][rd] = lds_tr_read<4096>(a_);                                                                  \
+        vt[3][dt][rd] = lds_tr_read<6144>(a_);                                                                  \
+      }                                                                                                         \
     if (MASKED_) {                                                                                              \
       const int kv0 = (t_) * KT;                                                                                \
       _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                                                          \
@@ -298,8 +253,8 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
       ma_[i_] = max3f(st[0][3 * i_], st[0][3 * i_ + 1], st[0][3 * i_ + 2]);                                     \
       mb_[i_] = max3f(st[1][3 * i_], st[1][3 * i_ + 1], st[1][3 * i_ + 2]);                                     \
     }                                                                                                           \
-    const float mc0_ = max3f(ma_[0], ma_[1], ma_[2]), mc1_ = max3f(ma_[3], ma_[4], st[0][15]);                   \
-    const float mc2_ = max3f(mb_[0], mb_[1], mb_[2]), mc3_ = max3f(mb_[3], mb_[4], st[1][15]);                   \
+    const float mc0_ = max3f(ma_[0], ma_[1], ma_[2]), mc1_ = max3f(ma_[3], ma_[4], st[0][15]);                  \
+    const float mc2_ = max3f(mb_[0], mb_[1], mb_[2]), mc3_ = max3f(mb_[3], mb_[4], st[1][15]);                  \
     float mx = fmaxf(max3f(mc0_, mc1_, mc2_), mc3_);                                                            \
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                                                                     \
     const float m_new = fmaxf(m_i, ceilf(mx * c_log2));                                                         \
@@ -316,41 +271,19 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
     /* P = exp2(s*c - m) with one fma per score */                                                              \
     const float nm = -m_i;                                                                                      \
     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                                                            \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) st[kt][r] = (VC_ATTN_ABL & 2) ? st[kt][r] + nm : fast_exp2(fmaf(st[kt][r], c_log2, nm)); \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) st[kt][r] = fast_exp2(fmaf(st[kt][r], c_log2, nm));        \
     /* O^T += V^T . P^T over the four 16-key blocks; row sums: ones . P^T */                                    \
-    if (VC_ATTN_VEARLY && !(VC_ATTN_ABL & 32)) {                                                                \
-      asm volatile("s_waitcnt lgkmcnt(0)"                                                                       \
-                   : "+v"(vt[0][0][0]), "+v"(vt[0][0][1]), "+v"(vt[0][1][0]), "+v"(vt[0][1][1]),                \
-                     "+v"(vt[1][0][0]), "+v"(vt[1][0][1]), "+v"(vt[1][1][0]), "+v"(vt[1][1][1]),                \
-                     "+v"(vt[VC_ATTN_VEARLY ? 2 : 0][0][0]), "+v"(vt[VC_ATTN_VEARLY ? 2 : 0][0][1]),            \
-                     "+v"(vt[VC_ATTN_VEARLY ? 2 : 0][1][0]), "+v"(vt[VC_ATTN_VEARLY ? 2 : 0][1][1]),            \
-                     "+v"(vt[VC_ATTN_VEARLY ? 3 : 1][0][0]), "+v"(vt[VC_ATTN_VEARLY ? 3 : 1][0][1]),            \
-                     "+v"(vt[VC_ATTN_VEARLY ? 3 : 1][1][0]), "+v"(vt[VC_ATTN_VEARLY ? 3 : 1][1][1]));           \
-    } else {                                                                                                    \
-      _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                          \
-        _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) vt[0][dt][rd] = lds_tr_read<0>(vb_ + (uint32_t)voff[rd][dt]); \
-    }                                                                                                           \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                         \
+                 : "+v"(vt[0][0][0]), "+v"(vt[0][0][1]), "+v"(vt[0][1][0]), "+v"(vt[0][1][1]),                  \
+                   "+v"(vt[1][0][0]), "+v"(vt[1][0][1]), "+v"(vt[1][1][0]), "+v"(vt[1][1][1]),                  \
+                   "+v"(vt[2][0][0]), "+v"(vt[2][0][1]), "+v"(vt[2][1][0]), "+v"(vt[2][1][1]),                  \
+                   "+v"(vt[3][0][0]), "+v"(vt[3][0][1]), "+v"(vt[3][1][0]), "+v"(vt[3][1][1]));                 \
     const uint32_t hx = hq ^ (uint32_t)((t_) * KT);                                                             \
-    float psum = 0.f;                                                                                           \
     _Pragma("unroll") for (int kb = 0; kb < 4; ++kb) {                                                          \
       const int kt = kb >> 1, ks = kb & 1;                                                                      \
-      const int vs = VC_ATTN_VEARLY ? kb : (kb & 1);                                                            \
-      if (!VC_ATTN_VEARLY) {                                                                                    \
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vt[vs][0][0]), "+v"(vt[vs][0][1]), "+v"(vt[vs][1][0]), "+v"(vt[vs][1][1])); \
-        if (kb < 3) {                                                                                           \
-          _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                      \
-            _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                                  \
-              const uint32_t a_ = vb_ + (uint32_t)voff[rd][dt];                                                 \
-              vt[vs ^ 1][dt][rd] = kb == 0 ? lds_tr_read<2048>(a_) : (kb == 1 ? lds_tr_read<4096>(a_) : lds_tr_read<6144>(a_)); \
-            }                                                                                                   \
-        }                                                                                                       \
-      }                                                                                                         \
       bf16x8 pf;                                                                                                \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) pf[j] = (__bf16)st[kt][ks * 8 + j];                         \
-      if (VC_ATTN_ABL & 4) { ot[0][kb] += (float)pf[0]; ot[1][kb] += (float)pf[5]; } else {                      \
-      if (VC_ATTN_ROWSUM_MFMA == 1) lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lacc, 0, 0, 0);    \
-      else if (VC_ATTN_ROWSUM_MFMA == 2) { _Pragma("unroll") for (int j = 0; j < 8; ++j) psum += st[kt][ks * 8 + j]; } /* unrounded P (timing) */ \
-      else { _Pragma("unroll") for (int j = 0; j < 8; ++j) psum += (float)pf[j]; }                              \
+      lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lacc, 0, 0, 0);                                  \
       if (DROP) {                                                                                               \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                         \
           const int r = ks * 8 + j;                                                                             \
@@ -359,29 +292,22 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
         }                                                                                                       \
       }                                                                                                         \
       _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) {                                                        \
-        const s16x8 v8 = __builtin_shufflevector(vt[vs][dt][0], vt[vs][dt][1], 0, 1, 2, 3, 4, 5, 6, 7);         \
+        const s16x8 v8 = __builtin_shufflevector(vt[kb][dt][0], vt[kb][dt][1], 0, 1, 2, 3, 4, 5, 6, 7);         \
         ot[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v8), pf, ot[dt], 0, 0, 0);  \
       }                                                                                                         \
-      }                                                                                                         \
     }                                                                                                           \
-    if (VC_ATTN_ROWSUM_MFMA != 1) l_i += psum;                                                                      \
   } while (0)
 
   int stg = 0;                       // ring slot of tile t (wave-uniform)
   for (int t = 0; t < nfull; ++t) {
-    // tile t landed (this wave's 4 pieces; with three slots tile t+1's 4 may stay in flight), then for every wave -- and every
-    // wave is done with tile t-1, whose slot the next request is about to overwrite
-    if (NSTG > 2 && t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    // tile t landed (this wave's 4 pieces; tile t+1's 4 may stay in flight), then for every wave -- and every wave is done with
+    // tile t-1, whose slot the next request is about to overwrite
+    if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(VC_ATTN_ABL & 8)) __syncthreads();
-    if (NSTG > 2) {
-      const int stg2 = stg == 0 ? 2 : stg - 1;                     // (stg + 2) % 3
-      if (t + 2 < ntiles && !(VC_ATTN_ABL & 16)) STAGE_TILE(t + 2, stg2);
-    } else {
-      if (t + 1 < ntiles) STAGE_TILE(t + 1, stg ^ 1);
-    }
+    __syncthreads();
+    if (t + 2 < ntiles) STAGE_TILE(t + 2, stg == 0 ? 2 : stg - 1);   // (stg + 2) % 3
     if (active) TILE_COMPUTE(stg, t, false);
-    stg = NSTG > 2 ? (stg == 2 ? 0 : stg + 1) : (stg ^ 1);
+    stg = stg == 2 ? 0 : stg + 1;
   }
   if (tail_tile) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -393,7 +319,7 @@ __global__ __launch_bounds__(256, VC_ATTN_MINW) void attn_dense_kernel(const bf1
 
   // ---- normalise and store: lane holds O[q][dt*32 + 8*g + 4*half + 0..3]; every register of lacc holds the MFMA part of
   // the row sum, l_i the left-over keys' part (one half-wave)
-  const float l_tot = (VC_ATTN_ROWSUM_MFMA == 1 ? lacc[0] : 0.f) + l_i + __shfl_xor(l_i, 32, 64);
+  const float l_tot = lacc[0] + l_i + __shfl_xor(l_i, 32, 64);
   const float inv = DROP ? drop_scale / l_tot : 1.0f / l_tot;
   const int q = q0 + qi;
   if (lse && q < S && half == 0) lse[((size_t)b * NH + h) * S + q] = m_i + log2f(l_tot);   // log2-domain logsumexp (training)
@@ -428,9 +354,6 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
                                                           const bf16_t* __restrict__ tag_a, const bf16_t* __restrict__ tag_b,
                                                           int n_tag, const int64_t* __restrict__ tag_len) {
   VC_LIVE_EXIT(live);
-#ifdef VC_ATTN_DECODE_FAT     // measurement build (tools/coresident_probe.py): 80 registers, cannot be resident next to two GEMM waves per SIMD
-  asm volatile("" ::: "v72");
-#endif
   __shared__ float sc[2][MAXKEYS];
   __shared__ float red[2][4];
   __shared__ float oacc[4][2][HD];
@@ -905,7 +828,7 @@ static int attn_decode_groups(const void* qkv_step, const void* vis_qkv, const v
 }
 
 
-#define VC_LAUNCH_DENSE(DROP_, grid_, stream_, ...) \
+#define VC_LAUNCH_DENSE(DROP_, grid_, stream_, ...)                                                             \
   hipLaunchKernelGGL(attn_dense_kernel<DROP_>, grid_, dim3(256), 0, (hipStream_t)(stream_), __VA_ARGS__, vc_tls_walk_rev ? 1 : 0, vc_tls_drop_salt)
 
 extern "C" int vitcap_attn_dense_fwd(const void* qkv, void* out, int B, int S, float scale, void* stream) {

@@ -19,65 +19,24 @@
 // counted vmcnt waits; the row-major operands (S, dP) are read with ds_read_b128, the transposed ones (K^T, Q^T, dO^T) straight from
 // the same tiles with ds_read_b64_tr_b16 -- the two runs of 4 consecutive rows a lane needs per 16-row MFMA step are exactly the C
 // layout of the score tile (see attn.hip).
-#include "common.h"
+#include "attn_common.h"
 #include "rng.h"
 
 namespace {
 
-constexpr int HD = 64;
-constexpr int NH = 12;
-constexpr int QKV_LD = 2304;
-constexpr int KT = 64;
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// build knobs measured on one box against the shipped form (profiles/r05_train_attn_bwd_ab.txt): all within the run-to-run spread
-#ifndef VC_BWD_PRIO          // 1: s_setprio(1) around the MFMA bursts (two waves of different workgroups share a SIMD)
-#define VC_BWD_PRIO 0
-#endif
-#define VC_BWD_PRIO_ON() do { if (VC_BWD_PRIO) __builtin_amdgcn_s_setprio(1); } while (0)
-#define VC_BWD_PRIO_OFF() do { if (VC_BWD_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-#ifndef VC_BWD_PREFETCH      // 1: the row-major fragments of a tile's second half are requested behind the first half's S / dP MFMAs
-#define VC_BWD_PREFETCH 0
-#endif
 // waves per SIMD the dQ kernel is compiled for.  3 = 168 registers: reached with the S^T and the dP^T MFMA chains one after the other (one set
 // of row-major fragments live at a time) and the tail mode as a template parameter (an instantiation holds either the left-over-key loop or
 // the masked tail tile); what the allocator still spills (13 registers in the encoder's instantiation) is stored once in front of the loop
 // and re-read once behind it -- checked in the ISA, no scratch access inside the loop.  Per launch -2.4 % (encoder) / -3.5 % (decoder)
 // against two waves, the training step within its spread (profiles/r05_train_attn_bwd_ab.txt).
-#ifndef VC_BWD_DQ_MINW
-#define VC_BWD_DQ_MINW 3
-#endif
-constexpr int DT_B = KT * 128;               // one row-major tile: 64 rows x 128 B
+constexpr int DQ_MINW = 3;
+// Measured against this form on one box and dropped, all within the run-to-run spread (same profile): s_setprio(1) around the MFMA bursts
+// (two waves of different workgroups share a SIMD); the row-major fragments of a tile's second half requested behind the first half's
+// S / dP MFMAs.
 constexpr int NSTG = 3;                      // ring: tile t+2 is in flight while tile t is multiplied
-constexpr int DQ_STG = 2 * DT_B;             // dq stage:  [K | V]
-constexpr int DKV_STG = 2 * DT_B + 1024;     // dkv stage: [Q | dO | L[64] | D[64] | 512 B the other two waves' copies land in]
+constexpr int DQ_STG = 2 * TILE_B;           // dq stage:  [K | V]
+constexpr int DKV_STG = 2 * TILE_B + 1024;   // dkv stage: [Q | dO | L[64] | D[64] | 512 B the other two waves' copies land in]
 
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
-}
-__device__ __forceinline__ int kv_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }   // attn.hip
-
-// per-lane read offsets inside a row-major tile: rows (lane & 31) (+32) as ds_read_b128 fragments, and the transpose reads of a
-// 16-row block (attn.hip: voff)
-#define VC_BWD_READ_OFFSETS()                                                                     \
-  int koff[4];                                                                                    \
-  _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) koff[ds] = (lane & 31) * 128 + (((2 * ds + half) ^ kv_swz(lane & 31)) * 16); \
-  int toff[2][2];                                                                                 \
-  {                                                                                               \
-    const int j_ = (lane & 15) >> 2;                                                              \
-    const int c2_ = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);                                    \
-    _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                            \
-      const int r_ = 8 * rd + 4 * half + j_;                                                      \
-      _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                            \
-        toff[rd][dt] = r_ * 128 + (((c2_ + 4 * dt) ^ kv_swz(r_)) * 16) + (lane & 1) * 8;          \
-    }                                                                                             \
-  }
 // joint_visible (common.h) without short-circuit control flow: in the peeled masked instances of the tile macros below the && / || form
 // became a divergent branch per score and pushed the kernels into scratch (57 spilled registers); same truth table
 __device__ __forceinline__ bool visible_nb(int q, int k, int S, int cf, int mf) {
@@ -89,12 +48,12 @@ __device__ __forceinline__ bool visible_nb(int q, int k, int S, int cf, int mf) 
 #define VC_ZERO16 f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}
 
 template <bool DROP, bool TAIL>
-__global__ __launch_bounds__(256, VC_BWD_DQ_MINW) void attn_bwd_dq_dma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
-                                                                 const bf16_t* __restrict__ dout, const float* __restrict__ lse,
-                                                                 float* __restrict__ dsum, bf16_t* __restrict__ dqkv, int S, int B,
-                                                                 int ld_rows, float c_log2, float scale, uint32_t drop_seed,
-                                                                 uint32_t drop_thr, float drop_scale, int causal_from, int mask_from,
-                                                                 int q_lo, int q_hi, const uint32_t* __restrict__ drop_salt) {
+__global__ __launch_bounds__(256, DQ_MINW) void attn_bwd_dq_dma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                                       const bf16_t* __restrict__ dout, const float* __restrict__ lse,
+                                                                       float* __restrict__ dsum, bf16_t* __restrict__ dqkv, int S, int B,
+                                                                       int ld_rows, float c_log2, float scale, uint32_t drop_seed,
+                                                                       uint32_t drop_thr, float drop_scale, int causal_from, int mask_from,
+                                                                       int q_lo, int q_hi, const uint32_t* __restrict__ drop_salt) {
   __shared__ __attribute__((aligned(1024))) char smem[NSTG * DQ_STG];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -137,7 +96,9 @@ __global__ __launch_bounds__(256, VC_BWD_DQ_MINW) void attn_bwd_dq_dma_kernel(co
   const bool tail_tile = rem > 8 || (causal_from > 0 && rem > 0);
   const int ntiles = nfull + (tail_tile ? 1 : 0);
 
-  // ---- staging (attn.hip STAGE_TILE): wave w moves rows [8w, 8w+8) and [32+8w, 32+8w+8) of the K and of the V tile
+  // ---- staging: wave w moves rows [8w, 8w+8) and [32+8w, 32+8w+8) of the K and of the V tile.  This is attn.hip's tail branch again
+  // and stays a local copy: one shared function is spelled like one of the two, and the other kernel's instruction order (the row
+  // clamps against the address arithmetic) then changes (docs/LAB_refactor_kernel_switches.md)
   const int srow = w * 8 + (lane >> 3);
   const uint32_t s_chunk = (uint32_t)(((lane & 7) ^ kv_swz(srow)) * 16);
   const char* gbase = (const char*)base + 768 * 2;               // K columns of this head; V is 768 elements further
@@ -151,10 +112,11 @@ __global__ __launch_bounds__(256, VC_BWD_DQ_MINW) void attn_bwd_dq_dma_kernel(co
     const char* a1_ = gbase + (size_t)r1_ * (QKV_LD * 2) + s_chunk;                                \
     glds16(a0_, sb_);                                                                              \
     glds16(a1_, sb_ + 4096);                                                                       \
-    glds16(a0_ + 768 * 2, sb_ + DT_B);                                                             \
-    glds16(a1_ + 768 * 2, sb_ + DT_B + 4096);                                                      \
+    glds16(a0_ + 768 * 2, sb_ + TILE_B);                                                           \
+    glds16(a1_ + 768 * 2, sb_ + TILE_B + 4096);                                                    \
   } while (0)
-  VC_BWD_READ_OFFSETS();
+  int koff[4], toff[2][2];
+  ATTN_READ_OFFSETS(koff, toff, 0, lane, half);
 
   f32x16 dqt[2];
 #pragma unroll
@@ -191,7 +153,7 @@ __global__ __launch_bounds__(256, VC_BWD_DQ_MINW) void attn_bwd_dq_dma_kernel(co
     __builtin_amdgcn_sched_barrier(0);                                                                               \
     {                                                                                                                \
       bf16x8 vfr[4];                                                                                                 \
-      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) vfr[ds] = *(const bf16x8*)(kl + DT_B + (KT_) * 4096 + koff[ds]); \
+      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) vfr[ds] = *(const bf16x8*)(kl + TILE_B + (KT_) * 4096 + koff[ds]); \
       dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[0], dof[0], VC_ZERO16, 0, 0, 0);                             \
       _Pragma("unroll") for (int ds = 1; ds < 4; ++ds) dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[ds], dof[ds], dpt, 0, 0, 0); \
     }                                                                                                                \
@@ -203,33 +165,23 @@ __global__ __launch_bounds__(256, VC_BWD_DQ_MINW) void attn_bwd_dq_dma_kernel(co
         ktr[0][dt][rd] = lds_tr_read<(KT_) * 4096>(kb_ + (uint32_t)toff[rd][dt]);                                    \
         ktr[1][dt][rd] = lds_tr_read<(KT_) * 4096 + 2048>(kb_ + (uint32_t)toff[rd][dt]);                             \
       }                                                                                                              \
-    if (VC_BWD_PREFETCH && (KT_) == 0) {      /* the second half's row-major fragments: in flight during this half's elementwise part */ \
-      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) {                                                             \
-        knx[ds] = *(const bf16x8*)(kl + 4096 + koff[ds]);                                                            \
-        vnx[ds] = *(const bf16x8*)(kl + DT_B + 4096 + koff[ds]);                                                     \
-      }                                                                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-    }                                                                                                                \
     if (TAIL && masked_) DQ_ELEM(KT_, t_, true);  /* wave-uniform: only the elementwise part exists twice */          \
     else DQ_ELEM(KT_, t_, false);                                                                                    \
     asm volatile("s_waitcnt lgkmcnt(0)"                                                                              \
                  : "+v"(ktr[0][0][0]), "+v"(ktr[0][0][1]), "+v"(ktr[0][1][0]), "+v"(ktr[0][1][1]),                   \
                    "+v"(ktr[1][0][0]), "+v"(ktr[1][0][1]), "+v"(ktr[1][1][0]), "+v"(ktr[1][1][1]));                  \
-    VC_BWD_PRIO_ON();                                                                                                \
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                               \
       bf16x8 sf;                                                                                                     \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) sf[j] = (__bf16)st[ks * 8 + j];                                  \
       _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                               \
         dqt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_pair(ktr[ks][dt][0], ktr[ks][dt][1]), sf, dqt[dt], 0, 0, 0); \
     }                                                                                                                \
-    VC_BWD_PRIO_OFF();                                                                                               \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
   } while (0)
 #define DQ_TILE(stg_, t_)                                                                                   \
   do {                                                                                                               \
     const char* kl = smem + (stg_) * DQ_STG;                                                                         \
     const uint32_t kb_ = lds_addr(kl);                                                                               \
-    bf16x8 knx[4], vnx[4];                                                                                           \
     DQ_HALF(0, t_);                                                                                                  \
     DQ_HALF(1, t_);                                                                                                  \
   } while (0)
@@ -363,13 +315,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const bf16_t* 
     r1_ = r1_ < S ? r1_ : S - 1;                                                                   \
     glds16(qg + (size_t)r0_ * (QKV_LD * 2) + s_chunk, sb_);                                        \
     glds16(qg + (size_t)r1_ * (QKV_LD * 2) + s_chunk, sb_ + 4096);                                 \
-    glds16(dg + (size_t)r0_ * (768 * 2) + s_chunk, sb_ + DT_B);                                    \
-    glds16(dg + (size_t)r1_ * (768 * 2) + s_chunk, sb_ + DT_B + 4096);                             \
+    glds16(dg + (size_t)r0_ * (768 * 2) + s_chunk, sb_ + TILE_B);                                  \
+    glds16(dg + (size_t)r1_ * (768 * 2) + s_chunk, sb_ + TILE_B + 4096);                           \
     int i_ = (t_) * KT + lane;                                                                     \
     i_ = i_ < S ? i_ : S - 1;                                                                      \
-    glds4(ldsrc + i_, st_ + 2 * DT_B + w * 256);                                                   \
+    glds4(ldsrc + i_, st_ + 2 * TILE_B + w * 256);                                                 \
   } while (0)
-  VC_BWD_READ_OFFSETS();
+  int koff[4], toff[2][2];
+  ATTN_READ_OFFSETS(koff, toff, 0, lane, half);
 
   f32x16 dvt[2], dkt[2];
 #pragma unroll
@@ -406,40 +359,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const bf16_t* 
 #define DKV_HALF(QT_, t_)                                                                                   \
   do {                                                                                                               \
     bf16x8 qfr[4], dfr[4];                                                                                           \
-    if (VC_BWD_PREFETCH && (QT_) == 1) {                                                                             \
-      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) { qfr[ds] = qnx[ds]; dfr[ds] = dnx[ds]; }                     \
-    } else {                                                                                                         \
-      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) {                                                             \
-        qfr[ds] = *(const bf16x8*)(ql + (QT_) * 4096 + koff[ds]);                                                    \
-        dfr[ds] = *(const bf16x8*)(ql + DT_B + (QT_) * 4096 + koff[ds]);                                             \
-      }                                                                                                              \
+    _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) {                                                               \
+      qfr[ds] = *(const bf16x8*)(ql + (QT_) * 4096 + koff[ds]);                                                      \
+      dfr[ds] = *(const bf16x8*)(ql + TILE_B + (QT_) * 4096 + koff[ds]);                                             \
     }                                                                                                                \
-    VC_BWD_PRIO_ON();                                                                                                \
     f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[0], kf[0], VC_ZERO16, 0, 0, 0);                          \
     f32x16 dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dfr[0], vf[0], VC_ZERO16, 0, 0, 0);                         \
     _Pragma("unroll") for (int ds = 1; ds < 4; ++ds) {                                                               \
       st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[ds], kf[ds], st, 0, 0, 0);                                    \
       dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dfr[ds], vf[ds], dpt, 0, 0, 0);                                  \
     }                                                                                                                \
-    VC_BWD_PRIO_OFF();                                                                                               \
     /* the transposed Q / dO fragments of this half go out now: their latency hides behind the elementwise part */  \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
     s16x4 qtr[2][2], dtr[2][2];          /* [dt][rd] of one 16-query block at a time */                              \
     _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                                 \
       _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                                             \
-        dtr[dt][rd] = lds_tr_read<DT_B + (QT_) * 4096>(qb_ + (uint32_t)toff[rd][dt]);                                \
+        dtr[dt][rd] = lds_tr_read<TILE_B + (QT_) * 4096>(qb_ + (uint32_t)toff[rd][dt]);                              \
         qtr[dt][rd] = lds_tr_read<(QT_) * 4096>(qb_ + (uint32_t)toff[rd][dt]);                                       \
       }                                                                                                              \
-    if (VC_BWD_PREFETCH && (QT_) == 0) {      /* the second half's row-major fragments: in flight during this half's elementwise part */ \
-      _Pragma("unroll") for (int ds = 0; ds < 4; ++ds) {                                                             \
-        qnx[ds] = *(const bf16x8*)(ql + 4096 + koff[ds]);                                                            \
-        dnx[ds] = *(const bf16x8*)(ql + DT_B + 4096 + koff[ds]);                                                     \
-      }                                                                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                             \
-    }                                                                                                                \
     if (masked_) DKV_ELEM(QT_, t_, true);         /* wave-uniform: only the elementwise part exists twice */          \
     else DKV_ELEM(QT_, t_, false);                                                                                   \
-    VC_BWD_PRIO_ON();                                                                                                \
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                               \
       bf16x8 pf, sf;                                                                                                 \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                                \
@@ -457,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const bf16_t* 
       if (ks == 0) {       /* the second block's fragments fly behind the first block's MFMAs */                     \
         _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                             \
           _Pragma("unroll") for (int rd = 0; rd < 2; ++rd) {                                                         \
-            dtr[dt][rd] = lds_tr_read<DT_B + (QT_) * 4096 + 2048>(qb_ + (uint32_t)toff[rd][dt]);                     \
+            dtr[dt][rd] = lds_tr_read<TILE_B + (QT_) * 4096 + 2048>(qb_ + (uint32_t)toff[rd][dt]);                   \
             qtr[dt][rd] = lds_tr_read<(QT_) * 4096 + 2048>(qb_ + (uint32_t)toff[rd][dt]);                            \
           }                                                                                                          \
       }                                                                                                              \
@@ -466,15 +405,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(const bf16_t* 
         dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[dt], sf, dkt[dt], 0, 0, 0);                             \
       }                                                                                                              \
     }                                                                                                                \
-    VC_BWD_PRIO_OFF();                                                                                               \
     __builtin_amdgcn_sched_barrier(0);                                                                               \
   } while (0)
 #define DKV_TILE(stg_, t_)                                                                                  \
   do {                                                                                                               \
     const char* ql = smem + (stg_) * DKV_STG;                                                                        \
-    const float* Ll = (const float*)(ql + 2 * DT_B);                                                                 \
+    const float* Ll = (const float*)(ql + 2 * TILE_B);                                                               \
     const uint32_t qb_ = lds_addr(ql);                                                                               \
-    bf16x8 qnx[4], dnx[4];                                                                                           \
     DKV_HALF(0, t_);                                                                                                 \
     DKV_HALF(1, t_);                                                                                                 \
   } while (0)

@@ -8,34 +8,13 @@
 // stage one workgroup per (image, target state) over the G*K survivors; nothing is sorted.  HBM-bound byte/float streaming: the
 // slot stage reads its logits row S times (L2 serves the repeats) and every fsm byte of the batch once per step.
 #include "common.h"
+#include "select.h"   // tk_key / tk_val / tk_idx: (value, index) as one unsigned key, larger value first, lower index on ties
 
 namespace {
 
 constexpr int CBS_MAXK = 8;          // beams per FSM state (vitcap_gen_opts.num_beams)
 constexpr int CBS_MAXS = 32;         // states: 2**3 main states x 4 words per constraint (utils_cbs.py:727-728)
 constexpr float CBS_MASKED = -1e20f; // utils_cbs.py:240: a transition the machine does not allow (NOT -inf)
-
-// (value, index) as one unsigned key: larger value first, lower index on ties = plain unsigned max
-__device__ __forceinline__ unsigned long long ck_key(float f, int i) {
-  unsigned u = __float_as_uint(f);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned)(~i);
-}
-__device__ __forceinline__ float ck_val(unsigned long long k) {
-  unsigned u = (unsigned)(k >> 32);
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ int ck_idx(unsigned long long k) { return (int)(~(unsigned)k); }
-__device__ __forceinline__ unsigned long long ck_wave_max(unsigned long long a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)a, o, 64), hi = __shfl_xor((unsigned)(a >> 32), o, 64);
-    const unsigned long long b = ((unsigned long long)hi << 32) | lo;
-    a = b > a ? b : a;
-  }
-  return a;
-}
 
 struct BadEnding { int32_t id[16]; };
 
@@ -68,7 +47,7 @@ struct TopK {
 __device__ __forceinline__ void block_topk(TopK& mine, int K, unsigned long long* s_w, unsigned long long* out) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int r = 0; r < K; ++r) {
-    const unsigned long long wbest = ck_wave_max(mine.k[0]);
+    const unsigned long long wbest = wave_max_u64(mine.k[0]);
     if (lane == 0) s_w[w] = wbest;
     __syncthreads();
     unsigned long long best = s_w[0];
@@ -106,13 +85,13 @@ __global__ __launch_bounds__(256) void cbs_start_kernel(const float* __restrict_
   const uint8_t* m = fsm + ((size_t)(b * S + 0) * S + i) * V;
   TopK top;
   top.clear();
-  for (int v = threadIdx.x; v < V; v += 256) top.push(ck_key(m[v] ? row[v] - l : -INFINITY, v));
+  for (int v = threadIdx.x; v < V; v += 256) top.push(tk_key(m[v] ? row[v] - l : -INFINITY, v));
   block_topk(top, K, s_w, s_out);
   if (threadIdx.x < K) {
     const unsigned long long key = s_out[threadIdx.x];
-    const int slot = b * G + i * K + threadIdx.x, word = ck_idx(key);
+    const int slot = b * G + i * K + threadIdx.x, word = tk_idx(key);
     ids_out[(size_t)slot * max_len + 1] = word;               // column 0 holds BOS since cbs_init
-    sc_out[slot] = ck_val(key);
+    sc_out[slot] = tk_val(key);
     parent[slot] = slot;
     if (!vc_is_eos(word, eos, ex)) atomicAdd(&unf[1], 1);
   }
@@ -173,14 +152,14 @@ __global__ __launch_bounds__(256) void cbs_candidates_kernel(const float* __rest
       if ((no_repeat && v == lastw) || (prev_bad && vc_is_eos(v, eos, ex))) x = -INFINITY;      // :187-198, before the finished override
     }
     if (!m[v]) x = CBS_MASKED;
-    top.push(ck_key(x, v));
+    top.push(tk_key(x, v));
   }
   block_topk(top, K, s_w, s_out);
   if (threadIdx.x < K) {
     const unsigned long long key = s_out[threadIdx.x];
     const size_t o = ((size_t)slot * S + i) * K + threadIdx.x;
-    cand_val[o] = ck_val(key);
-    cand_word[o] = ck_idx(key);
+    cand_val[o] = tk_val(key);
+    cand_word[o] = tk_idx(key);
   }
 }
 
@@ -208,17 +187,17 @@ __global__ __launch_bounds__(256) void cbs_select_kernel(const float* __restrict
   for (int c = threadIdx.x; c < n; c += 256) {
     const int r = c / K, j = c - r * K;
     const float x = cand_val[((size_t)(b * G + r) * S + i) * K + j] + sc_in[b * G + r];      // fp32, as `top + last` (:245-247)
-    top.push(ck_key(x, c));
+    top.push(tk_key(x, c));
   }
   block_topk(top, K, s_w, s_out);
   if (threadIdx.x < K) {
     const unsigned long long key = s_out[threadIdx.x];
-    const int c = ck_idx(key), r = c / K, j = c - r * K;
+    const int c = tk_idx(key), r = c / K, j = c - r * K;
     const int slot = b * G + i * K + threadIdx.x, src = b * G + r;
     const int word = cand_word[((size_t)src * S + i) * K + j];
     for (int p = 0; p < t; ++p) ids_out[(size_t)slot * max_len + p] = ids_in[(size_t)src * max_len + p];
     ids_out[(size_t)slot * max_len + t] = word;
-    sc_out[slot] = ck_val(key);
+    sc_out[slot] = tk_val(key);
     parent[slot] = src;
     if (!vc_is_eos(word, eos, ex)) atomicAdd(&unf[t], 1);
   }
@@ -248,18 +227,18 @@ __global__ __launch_bounds__(64) void cbs_finalize_kernel(const int64_t* __restr
     const int slot = b * G + lane * K;
     int words = 0;
     for (int p = 1; p <= T; ++p) words += vc_is_eos((int)ids[(size_t)slot * max_len + p], eos, ex) ? 0 : 1;
-    key = ck_key(sc[slot] / (float)(words + 1), lane);       // torch.argmax: first maximum = lowest state on ties
+    key = tk_key(sc[slot] / (float)(words + 1), lane);       // torch.argmax: first maximum = lowest state on ties
   }
-  const unsigned long long best = ck_wave_max(key);
+  const unsigned long long best = wave_max_u64(key);
   if (best == 0ull) {               // no main state of this machine can satisfy the request (2**given > S): the reference indexes out of range
     for (int p = lane; p < max_len; p += 64) out_ids[(size_t)b * max_len + p] = (int64_t)pad;
     if (lane == 0) out_lp[b] = -INFINITY;
     return;
   }
-  const int slot = b * G + ck_idx(best) * K;
+  const int slot = b * G + tk_idx(best) * K;
   for (int p = lane; p < max_len; p += 64)
     out_ids[(size_t)b * max_len + p] = p < T ? ids[(size_t)slot * max_len + 1 + p] : (int64_t)pad;
-  if (lane == 0) out_lp[b] = ck_val(best);
+  if (lane == 0) out_lp[b] = tk_val(best);
 }
 
 BadEnding make_bad(const int32_t* e) {

@@ -86,6 +86,16 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 __device__ __forceinline__ bf16x8 tr_pair(s16x4 lo, s16x4 hi) {
   return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
+// one LDS-DMA piece (global_load_lds): every lane fetches 16 (or 4) bytes from its own global address `g`; the wave's 64 pieces
+// land lane-linear, 1 KiB (256 B) from the wave-uniform LDS address `lds` on -- no VGPR round trip, no ds_write
+__device__ __forceinline__ void glds16(const void* g, void* lds) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+}
+__device__ __forceinline__ void glds4(const void* g, void* lds) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
+}
 
 // round-to-nearest-even fp32 -> bf16 (matches torch .to(bfloat16) for finite values and NaN->qNaN)
 __device__ __forceinline__ bf16_t f2bf(float f) {

@@ -39,11 +39,6 @@ int tile_group_n(int tiles_n) {
 int vc_tile_group_n(int tiles_n) { return tile_group_n(tiles_n); }
 namespace {
 
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -545,13 +540,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
   // residual rows are requested one chunk (2*MT iterations = 8*MT rows) ahead of their use
   const bool col_ok = ncol < p.N;
   f32x4 rres[2][2 * MT];
-#define ROWS_OF(m_, orow_, rrow_)                                             \
-  int orow_ = (m_), rrow_ = (m_);                                             \
-  if (p.row_group > 0) {                                                      \
-    const int g_ = (m_) / p.row_group, in_ = (m_) - g_ * p.row_group;         \
-    orow_ = g_ * p.out_group_rows + p.out_row_off + in_;                      \
-    rrow_ = p.res_periodic ? in_ : orow_;                                     \
-  }
 #define ISSUE_RES(c_)                                                                                        \
   if (HAS_RES) {                                                                                             \
     _Pragma("unroll") for (int it = 0; it < 2 * MT; ++it) {                                                  \
@@ -734,7 +722,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
     }
   }
 #undef ISSUE_RES
-#undef ROWS_OF
   if constexpr (LN) {
     // ---- LayerNorm of the row block by the LAST of its column tiles to get here (any placement of the tiles over XCDs / CUs):
     // every wave's write-through stores acknowledged -> barrier -> one relaxed agent-scope ticket; the workgroup that draws the last
@@ -783,9 +770,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& p, char* smem, cons
 // VGPR cap 224: two waves of this kernel per SIMD then leave 64 of the 512 registers (and 24 KB of LDS) free, which is what one wave
 // of the decode step's HBM-bound attention kernel needs (60 VGPRs, 8 KB): in the 2-slot batch pipeline that kernel can become
 // RESIDENT NEXT TO the GEMM's workgroups instead of waiting for CUs to drain -- K/V streaming overlaps the MFMA work.
-#ifndef VC_GEMM256_VGPRS
 #define VC_GEMM256_VGPRS 224
-#endif
 template <int ACT, int OUT_F32, bool HAS_RES, int PH, int MTS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(VC_GEMM256_VGPRS))) void gemm_nt_256_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -201,14 +201,6 @@ __device__ __forceinline__ void fence_accumulators(f32x4 (&acc)[MI][8]) {
     asm volatile("" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]), "+a"(acc[i][4]), "+a"(acc[i][5]), "+a"(acc[i][6]), "+a"(acc[i][7]));
 }
 
-#define ROWS_OF(m_, orow_, rrow_)                                             \
-  int orow_ = (m_), rrow_ = (m_);                                             \
-  if (p.row_group > 0) {                                                      \
-    const int g_ = (m_) / p.row_group, in_ = (m_) - g_ * p.row_group;         \
-    orow_ = g_ * p.out_group_rows + p.out_row_off + in_;                      \
-    rrow_ = p.res_periodic ? in_ : orow_;                                     \
-  }
-
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
 
 // ---- epilogue straight from the accumulators (no LDS: in the persistent kernel the k-tile buffers already hold the next tile's
@@ -282,10 +274,6 @@ __device__ __forceinline__ void epilogue_regs(f32x4 (&acc)[MI][8], const GemmArg
 // dropped by the range check, no predicate), one 32-bit per-lane offset serves the whole tile, the m-tile's row offset rides in
 // the scalar offset and the n-tile's in the immediate.  Same arithmetic per element.
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* base, long long bytes) {
-  const unsigned rec = bytes <= 0 ? 0u : (bytes > 0xffffffffll ? 0xffffffffu : (unsigned)bytes);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, rec, 0x00020000);
-}
 
 template <int ACT, int MI>
 __device__ __forceinline__ void epilogue_regs_fast(f32x4 (&acc)[MI][8], const GemmArgs& p, const int row_w, const int col_w, const int lane) {
@@ -293,7 +281,7 @@ __device__ __forceinline__ void epilogue_regs_fast(f32x4 (&acc)[MI][8], const Ge
   f32x4 bias4[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) bias4[j] = p.bias ? *(const f32x4*)(p.bias + col_w + j * 16 + fk * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const __amdgpu_buffer_rsrc_t rc = rows_rsrc((const bf16_t*)p.C + (size_t)row_w * p.ldc, (long long)(p.M - row_w) * p.ldc * 2);
+  const __amdgpu_buffer_rsrc_t rc = vc_rsrc((const bf16_t*)p.C + (size_t)row_w * p.ldc, (long long)(p.M - row_w) * p.ldc * 2);
   // The m-tile's row offset rides in the VECTOR offset, the scalar offset stays the constant 0: with a REGISTER soffset hipcc omits
   // the wait state between a 16-byte buffer store and a VALU write to its data registers (LLVM's hazard table says the hazard only
   // exists without one) -- on gfx950 it exists all the same: the next v_pk_add overwrote the store's last data dword in lanes
@@ -331,9 +319,9 @@ __device__ __forceinline__ void epilogue_regs_fast_x(f32x4 (&acc)[MI][8], const 
   f32x4 bias4[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) bias4[j] = p.bias ? *(const f32x4*)(p.bias + col_w + j * 16 + fk * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const __amdgpu_buffer_rsrc_t rc = rows_rsrc((const bf16_t*)p.C + (size_t)row_w * p.ldc, (long long)(p.M - row_w) * p.ldc * 2);
-  const __amdgpu_buffer_rsrc_t rz = rows_rsrc(p.zout ? p.zout + (size_t)row_w * p.ldz : nullptr, p.zout ? (long long)(p.M - row_w) * p.ldz * 2 : 0);
-  const __amdgpu_buffer_rsrc_t ra = rows_rsrc(p.aux ? p.aux + (size_t)row_w * p.ldaux : nullptr, p.aux ? (long long)(p.M - row_w) * p.ldaux * 2 : 0);
+  const __amdgpu_buffer_rsrc_t rc = vc_rsrc((const bf16_t*)p.C + (size_t)row_w * p.ldc, (long long)(p.M - row_w) * p.ldc * 2);
+  const __amdgpu_buffer_rsrc_t rz = vc_rsrc(p.zout ? p.zout + (size_t)row_w * p.ldz : nullptr, p.zout ? (long long)(p.M - row_w) * p.ldz * 2 : 0);
+  const __amdgpu_buffer_rsrc_t ra = vc_rsrc(p.aux ? p.aux + (size_t)row_w * p.ldaux : nullptr, p.aux ? (long long)(p.M - row_w) * p.ldaux * 2 : 0);
   unsigned voff = (unsigned)(frow * p.ldc + col_w + (fk & 1) * 16 + (fk >> 1) * 8) * 2u;
   unsigned voff_z = (unsigned)(frow * p.ldz + col_w + (fk & 1) * 16 + (fk >> 1) * 8) * 2u;
   unsigned voff_a = (unsigned)(frow * p.ldaux + col_w + fk * 4) * 2u;
@@ -453,7 +441,7 @@ __device__ __forceinline__ void epilogue_regs_fast_defer(f32x4 (&acc)[MI][8], co
   for (int j = 0; j < 8; ++j) bias4[j] = p.bias ? *(const f32x4*)(p.bias + col_w + j * 16 + fk * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
   const bf16_t* cbase = (const bf16_t*)p.C + (size_t)row_w * p.ldc;
   const long long cbytes = (long long)(p.M - row_w) * p.ldc * 2;
-  const __amdgpu_buffer_rsrc_t rc = rows_rsrc(cbase, cbytes);
+  const __amdgpu_buffer_rsrc_t rc = vc_rsrc(cbase, cbytes);
   unsigned voff = (unsigned)(frow * p.ldc + col_w + (fk & 1) * 16 + (fk >> 1) * 8) * 2u;
   const unsigned istep = 16u * p.ldc * 2u;
 #pragma unroll
@@ -503,8 +491,8 @@ __device__ __forceinline__ void epilogue_patch_fast(f32x4 (&acc)[MI][8], const G
   const int rr = lane >> 5, rcx = lane & 31;
   const f32x4 bias4 = p.bias ? *(const f32x4*)(p.bias + col_w + rcx * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int CB = OUT_F32 ? 4 : 2;
-  const __amdgpu_buffer_rsrc_t rc = rows_rsrc((const char*)p.C + (size_t)row_w * p.ldc * CB, (long long)(p.M - row_w) * p.ldc * CB);
-  const __amdgpu_buffer_rsrc_t rs = rows_rsrc(HAS_RES ? p.res + (size_t)row_w * p.ldr : nullptr, HAS_RES ? (long long)(p.M - row_w) * p.ldr * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rc = vc_rsrc((const char*)p.C + (size_t)row_w * p.ldc * CB, (long long)(p.M - row_w) * p.ldc * CB);
+  const __amdgpu_buffer_rsrc_t rs = vc_rsrc(HAS_RES ? p.res + (size_t)row_w * p.ldr : nullptr, HAS_RES ? (long long)(p.M - row_w) * p.ldr * 4 : 0);
   unsigned voff_c = (unsigned)(rr * p.ldc + col_w + rcx * 4) * CB;     // stores: row steps in the vector offset, soffset constant (see epilogue_regs_fast)
   const unsigned voff_r = (unsigned)(rr * p.ldr + col_w + rcx * 4) * 4u;
   const unsigned cstep = 2u * p.ldc * CB, rstep = 2u * p.ldr * 4u;     // two rows
@@ -659,7 +647,6 @@ __device__ __forceinline__ void epilogue_lds(f32x4 (&acc)[MI][8], const GemmArgs
   }
 #undef ISSUE_RES
 }
-#undef ROWS_OF
 
 // tile list position -> tile coordinates: column groups of group_n tiles (the tiles an XCD runs at once span few W tiles, which stay
 // in its L2 for the walk down M, and each A tile is fetched once for group_n consumers)

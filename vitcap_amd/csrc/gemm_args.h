@@ -38,6 +38,15 @@ struct GemmArgs {
   int rev;                     // 256-row-tile kernels: walk the tile list last-to-first (vc_tls_walk_rev)
 };
 
+// output row and residual row of GEMM row m_ (row groups: vitcap_gemm_desc.row_group; declares orow_ and rrow_; `p` is the GemmArgs)
+#define ROWS_OF(m_, orow_, rrow_)                                             \
+  int orow_ = (m_), rrow_ = (m_);                                             \
+  if (p.row_group > 0) {                                                      \
+    const int g_ = (m_) / p.row_group, in_ = (m_) - g_ * p.row_group;         \
+    orow_ = g_ * p.out_group_rows + p.out_row_off + in_;                      \
+    rrow_ = p.res_periodic ? in_ : orow_;                                     \
+  }
+
 // launch of a large-tile GEMM: with kernel-bound timing events when the engine's timing run asked for them (common.h)
 #define VC_LAUNCH_GEMM(kern, grid, block, smem, s, p)                                                              \
   do {                                                                                                             \

@@ -4,12 +4,12 @@
 // layers) therefore needs no transposed copies of the activations.
 //
 // MFMA fragments want 8 consecutive reduction elements per lane for a fixed row; here those are strided by the row
-// pitch.  The tiles are staged row-major ([64 m][256 cols], LDS-DMA, 16 B per lane) and read with the CDNA4 LDS
+// pitch.  The tiles are staged row-major ([32 m][256 cols] per stage, LDS-DMA, 16 B per lane) and read with the CDNA4 LDS
 // transpose read `ds_read_b64_tr_b16`: a 16-lane group fetches a [4 m][16 col] block and lane i receives column i of
 // the 4 rows (measured semantics: lane i, element j  <-  address of lane 4j + i/4, element i%4).
 //
-// Tile 256(n) x 256(k) per workgroup, 8 waves as 2(n) x 4(k), wave tile 128 x 64, mfma_f32_16x16x32_bf16, two
-// 64-row stages in LDS (128 KiB).  The reduction dimension (M = batch x tokens, 36 928 at B=64) is long and the output
+// Tile 256(n) x 256(k) per workgroup, 8 waves as 2(n) x 4(k), wave tile 128 x 64, mfma_f32_16x16x32_bf16, a ring of
+// four 32-row stages in LDS (128 KiB).  The reduction dimension (M = batch x tokens, 36 928 at B=64) is long and the output
 // small (768..3072 x 768..3072), so the grid is (output tiles) x (splits of M): every split writes its own fp32 slab
 // (deterministic, no atomics), reduced by vitcap_reduce_slabs.
 //
@@ -25,13 +25,7 @@ namespace {
 
 constexpr int TBN = 256, TBK = 256, TBM = 64;
 constexpr int ROW_B = 512;                       // bytes per tile row (256 bf16)
-constexpr int OP_BYTES = TBM * ROW_B;            // 32 KiB per operand per stage
-#ifndef VC_TN_ALTERNATE     // 1: the two wave groups one segment apart (needs VC_TN_RING4)
-#define VC_TN_ALTERNATE 1
-#endif
-#ifndef VC_TN_RING4
-#define VC_TN_RING4 1
-#endif
+constexpr int OP_BYTES = TBM * ROW_B;            // 32 KiB per operand per 64-row step of the split (TBM): two 32-row ring stages of OP_BYTES / 2
 constexpr int STAGE_BYTES = 2 * OP_BYTES;
 
 struct TnArgs {
@@ -46,10 +40,6 @@ struct TnArgs {
   int accumulate;
 };
 
-__device__ __forceinline__ void glds16(const void* g, void* lds) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
 __device__ __forceinline__ int swz(int m) { return ((m >> 3) & 3) * 4 + (m & 3); }
 
 __global__ __launch_bounds__(512) void gemm_tn_kernel(TnArgs p) {
@@ -78,22 +68,9 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(TnArgs p) {
   s_end = s_end < total_stages ? s_end : total_stages;
   const int nst = s_end > s_begin ? s_end - s_begin : 0;
 
-  // ---- DMA: wave w fills rows 8w .. 8w+7 of each operand tile, 4 instructions of 2 rows each per operand
+  // ---- DMA (STAGE32 below): wave w fills rows 4w .. 4w+3 of each operand's 32-row stage, 2 instructions of 2 rows each per operand
   const int drow = lane >> 5;                      // row within the instruction's pair
   const int dchunk = lane & 31;                    // physical 16-byte chunk within the row
-#define STAGE(buf_, st_)                                                                            \
-  do {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                 \
-      const int r_ = w * 8 + i * 2 + drow;           /* tile row 0..63 */                           \
-      const int lc_ = dchunk ^ (swz(r_) << 1);       /* logical 16-byte chunk this lane fetches */  \
-      const int m_ = (st_) * TBM + r_;                                                              \
-      const bf16_t* ys_ = m_ < p.M ? p.Y + (size_t)m_ * p.ldy + n0 + lc_ * 8 : p.zeros + lc_ * 8;   \
-      const bf16_t* xs_ = m_ < p.M ? p.X + (size_t)m_ * p.ldx + k0 + lc_ * 8 : p.zeros + lc_ * 8;   \
-      char* dst_ = smem + (buf_) * STAGE_BYTES + (w * 8 + i * 2) * ROW_B;                           \
-      glds16(ys_, dst_);                                                                            \
-      glds16(xs_, dst_ + OP_BYTES);                                                                 \
-    }                                                                                               \
-  } while (0)
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -106,64 +83,37 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(TnArgs p) {
   const int g = lane >> 4, gi = lane & 15;
   const int tj = gi >> 2, tq = gi & 3;
   const int fsw = g * 4 + tj;                      // swz(row) for both reads (rows +0..3 and +4..7 share it)
-  const int row_lo = g * 8 + tj;                   // + ms*32 (+4 for the second read)
+  const int row_lo = g * 8 + tj;                   // (+4 for the second read)
 
-  // Measured anatomy (M = 36928, N = 2304, K = 768, 9 splits; us incl. the 12 us slab reduction): full 200 | no DMA 116 | no
-  // transpose reads 136 | no MFMA 180 | DMA only 127 | reads only 79 | MFMA only 107 | barriers + slab stores only 41.
-  // The MFMAs are already hidden; the critical path is LDS-DMA in (25 B/clk/CU, the same ceiling the NT kernel sees) PLUS
-  // the transpose reads out, which do not overlap each other.  Tried and measured, both slower or equal, both reverted:
-  // the two n-halves one phase apart as in gemm_nt_256_kernel (+3 %), and a ring of four 32-row stages with the request
-  // issued three stages ahead (DMA-only 127 -> 104 us, but full 200 -> 242 -- with the waits of that time, see below: round 3
-  // built it again on counted waits and it is the shipped form, VC_TN_RING4); register-staged tiles (global_load -> VGPR ->
-  // ds_write_b128) instead of LDS-DMA: 195 -> 499 us.  SQ counters: no LDS bank conflicts, 67 % of wave cycles in
-  // s_waitcnt/barriers, MFMA pipe 33 % busy.
-  // Round 2, measured and reverted: the bias gradient (column sums of Y) as extra MFMAs against an all-ones fragment inside this
-  // kernel (8 per 32-row step on the wk = 0 waves of the k-tile-0 workgroups, or 2 per wave) instead of the separate colsum pass:
-  // the colsum launches disappear (-1.7 ms per training step) but this kernel slows from 13.15 to 14.6 / 14.9 ms per step -- the
-  // MFMA issue slots are not free although the pipe is a third busy.  No net gain.
+  // Measured anatomy of the first form, two 64-row stages (M = 36928, N = 2304, K = 768, 9 splits; us incl. the 12 us slab
+  // reduction): full 200 | no DMA 116 | no transpose reads 136 | no MFMA 180 | DMA only 127 | reads only 79 | MFMA only 107 |
+  // barriers + slab stores only 41.  The MFMAs are already hidden; the critical path is LDS-DMA in (25 B/clk/CU, the same ceiling the
+  // NT kernel sees) PLUS the transpose reads out, which did not overlap each other.  SQ counters: no LDS bank conflicts, 67 % of
+  // wave cycles in s_waitcnt/barriers, MFMA pipe 33 % busy.
   // Transpose reads as inline asm (common.h lds_tr_read): with the intrinsic, hipcc put `s_waitcnt vmcnt(0)` in front of the
   // first read of every stage, i.e. the stage requested a few instructions earlier was awaited before this one was
   // multiplied -- LDS-DMA in and reads + MFMAs out ran back to back (the "DMA + reads do not overlap" of the anatomy above).
-  // Per 32-row step: the X fragments and the first four Y fragments are requested, then -- behind their lgkmcnt(0) -- the
-  // other four Y fragments, whose latency hides behind the first 16 MFMAs.
+  // Tried and measured:
+  //  - a ring of four 32-row stages, requests three stages ahead: with the intrinsic's vmcnt(0) slower (DMA-only 127 -> 104 us, but
+  //    full 200 -> 242, four short stages pay the wait twice as often); round 3 built it again on counted waits with the asm reads
+  //    and it is the shipped form below, the two 64-row buffers and the ring without the two wave groups apart are gone;
+  //  - the two n-halves one phase apart as in gemm_nt_256_kernel: 3 % slower on the two-buffer form and reverted there; on the ring
+  //    +0.5 % of a training step and the shipped form (docs/LAB_r01_r04.md section 7);
+  //  - register-staged tiles (global_load -> VGPR -> ds_write_b128) instead of LDS-DMA: 195 -> 499 us, reverted;
+  //  - round 2: the bias gradient (column sums of Y) as extra MFMAs against an all-ones fragment inside this kernel (8 per 32-row
+  //    step on the wk = 0 waves of the k-tile-0 workgroups, or 2 per wave) instead of the separate colsum pass: the colsum launches
+  //    disappear (-1.7 ms per training step) but this kernel slows from 13.15 to 14.6 / 14.9 ms per step -- the MFMA issue slots
+  //    are not free although the pipe is a third busy.  No net gain, reverted.
   uint32_t yaddr[8], xaddr[4];
   {
     const uint32_t lane_base = (uint32_t)(row_lo * ROW_B + tq * 8);
 #pragma unroll
     for (int i = 0; i < 8; ++i) yaddr[i] = lane_base + (uint32_t)(((wn * 8 + i) ^ fsw) * 32);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) xaddr[j] = lane_base + (uint32_t)(VC_TN_RING4 ? OP_BYTES / 2 : OP_BYTES) + (uint32_t)(((wk * 4 + j) ^ fsw) * 32);
+    for (int j = 0; j < 4; ++j) xaddr[j] = lane_base + (uint32_t)(OP_BYTES / 2) + (uint32_t)(((wk * 4 + j) ^ fsw) * 32);
   }
   const uint32_t lds0 = lds_addr(smem);
-#define TN_STEP(MS_)                                                                                                  \
-  do {                                                                                                                \
-    s16x4 xl[4], xh[4], yl[8], yh[8];                                                                                 \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                   \
-      xl[j] = lds_tr_read<(MS_) * 32 * ROW_B>(sb + xaddr[j]);                                                         \
-      xh[j] = lds_tr_read<(MS_) * 32 * ROW_B + 4 * ROW_B>(sb + xaddr[j]);                                             \
-    }                                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                   \
-      yl[i] = lds_tr_read<(MS_) * 32 * ROW_B>(sb + yaddr[i]);                                                         \
-      yh[i] = lds_tr_read<(MS_) * 32 * ROW_B + 4 * ROW_B>(sb + yaddr[i]);                                             \
-    }                                                                                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                               \
-                 : "+v"(xl[0]), "+v"(xh[0]), "+v"(xl[1]), "+v"(xh[1]), "+v"(xl[2]), "+v"(xh[2]), "+v"(xl[3]), "+v"(xh[3]), \
-                   "+v"(yl[0]), "+v"(yh[0]), "+v"(yl[1]), "+v"(yh[1]), "+v"(yl[2]), "+v"(yh[2]), "+v"(yl[3]), "+v"(yh[3])); \
-    _Pragma("unroll") for (int i = 4; i < 8; ++i) {                                                                   \
-      yl[i] = lds_tr_read<(MS_) * 32 * ROW_B>(sb + yaddr[i]);                                                         \
-      yh[i] = lds_tr_read<(MS_) * 32 * ROW_B + 4 * ROW_B>(sb + yaddr[i]);                                             \
-    }                                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                     \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                   \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_pair(xl[j], xh[j]), tr_pair(yl[i], yh[i]), acc[i][j], 0, 0, 0); \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                               \
-                 : "+v"(yl[4]), "+v"(yh[4]), "+v"(yl[5]), "+v"(yh[5]), "+v"(yl[6]), "+v"(yh[6]), "+v"(yl[7]), "+v"(yh[7])); \
-    _Pragma("unroll") for (int i = 4; i < 8; ++i)                                                                     \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                   \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_pair(xl[j], xh[j]), tr_pair(yl[i], yh[i]), acc[i][j], 0, 0, 0); \
-  } while (0)
 
-#if VC_TN_RING4
   // ring of FOUR 32-row stages, requests three stages ahead: more bytes in flight per CU than the two 64-row buffers (the kernel
   // is bound by LDS-DMA throughput in), one barrier per 32-row step.  Round 2 measured this form slower -- with the transpose-read
   // intrinsic every step waited for vmcnt(0), which four short stages pay twice as often; with the asm reads the counted wait holds.
@@ -192,12 +142,14 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(TnArgs p) {
 #pragma unroll
   for (int q = 0; q < 3; ++q)
     if (q < nst32) STAGE32(q, s32_begin + q);
-#if VC_TN_ALTERNATE
   // The two wave groups (wn = 0 / 1: waves w and w + 4 share a SIMD) run one segment apart, as in gemm_nt_256_kernel: a step is a
   // LOAD segment (24 transpose reads) and an MFMA segment (32 MFMAs), each closed by a barrier, and while one wave of a SIMD
   // multiplies, the other reads.  Barrier 2t opens L_A(t) (stage t landed for everyone: every wave waited for its own pieces
   // before it) and M_B(t-1); barrier 2t+1 opens M_A(t) and L_B(t).  The buffer of stage t-1 was last read in L_B(t-1), which
   // barrier 2t closes, so either group requests stage t+3 right behind that barrier.
+  // Raw s_barrier, not __syncthreads(): its workgroup-scope fence makes hipcc drain vmcnt(0) in front of the barrier, i.e. wait for
+  // the stages just requested.  Nothing here needs the fence: LDS is written by the DMA only (awaited by the counted vmcnt of
+  // WAIT_STAGE) and read by the asm transpose reads, each fenced by its own lgkmcnt(0) before the barrier that follows.
   s16x4 xl[4], xh[4], yl[8], yh[8];
 #define TN_LOAD()                                                                                                     \
   do {                                                                                                                \
@@ -251,39 +203,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(TnArgs p) {
   }
 #undef TN_LOAD
 #undef TN_MFMA
-#else
-  for (int t = 0; t < nst32; ++t) {
-    WAIT_STAGE(t);
-    __builtin_amdgcn_s_barrier();            // stage t visible to all waves; every wave is done reading stage t-1 ...
-    if (t + 3 < nst32) STAGE32((t + 3) & 3, s32_begin + t + 3);      // ... whose buffer the request for stage t+3 refills
-    const uint32_t sb = lds0 + (uint32_t)((t & 3) * (STAGE_BYTES / 2));
-    TN_STEP(0);
-  }
-#endif
 #undef WAIT_STAGE
 #undef STAGE32
-#else
-  if (nst > 0) STAGE(0, s_begin);
-  for (int t = 0; t < nst; ++t) {
-    const int buf = t & 1;
-    if (t + 1 < nst) {
-      STAGE(buf ^ 1, s_begin + t + 1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // this stage's 8 pieces landed; the next 8 stay in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // raw s_barrier, not __syncthreads(): its workgroup-scope fence makes hipcc drain vmcnt(0) in front of the barrier, i.e.
-    // wait for the stage requested three lines up.  Nothing here needs the fence: LDS is written by the DMA only (awaited by the
-    // counted vmcnt above) and read by the asm transpose reads, each fenced by its own lgkmcnt(0) before the second barrier.
-    __builtin_amdgcn_s_barrier();
-    const uint32_t sb = lds0 + (uint32_t)(buf * STAGE_BYTES);
-    TN_STEP(0);
-    TN_STEP(1);
-    __builtin_amdgcn_s_barrier();                          // everyone done reading `buf` before it is refilled
-  }
-#endif
-#undef TN_STEP
-#undef STAGE
 
   // ---- store the slab: with the operands swapped the lane holds 4 consecutive k of ONE n (16-byte stores)
   float* cs = p.C + (size_t)split * p.N * p.K;

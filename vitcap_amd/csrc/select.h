@@ -1,5 +1,5 @@
 // Row selection on the device, stated once: ordered keys, the argmax candidate, workgroup sum / max, "a wave takes the k best",
-// radix selection, and the per-sequence bookkeeping of one generation step.  Used by decode.hip and norm.hip.
+// radix selection, and the per-sequence bookkeeping of one generation step.  Used by decode.hip, norm.hip and cbs.hip (the keys).
 //
 // Floating-point sums keep one order: xor butterfly 32 -> 1 inside a wave (wave_sum), then the wave partials added serially
 // 0 -> NW-1 (block_sum).  One site does NOT use block_sum and must keep its own expression, because its results are pinned bit

@@ -1,7 +1,6 @@
 // Training-step kernels other than GEMM/attention (gfx950): transposes for the weight-gradient GEMMs, LayerNorm
 // backward, split-K slab reduction, embedding backward, losses, global-norm clip + fused AdamW, weight re-packing.
 // All are HBM-bound streaming kernels (vectorised 8/16-byte accesses, one wave per 768-wide row where rows matter).
-#include <stdlib.h>
 
 #include "common.h"
 #include "rng.h"
@@ -553,7 +552,7 @@ extern "C" int vitcap_transpose_colsum(const void* x, int ldx, void* xt, int ldt
 }
 
 static int ln_bwd_grid(int M, int nw, int* rows_per_wave) {
-  static const int wg_per_cu = [] { const char* e = getenv("VITCAP_LNBWD_WG_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 4 ? v : 2; }();
+  constexpr int wg_per_cu = 2;       // with 8 waves each: the shape measured fastest (layernorm_bwd_kernel; docs/LAB_r01_r04.md section 7)
   static const int n_cu = [] {
     int dev = 0;
     hipDeviceProp_t prop;
@@ -582,24 +581,21 @@ extern "C" int vitcap_layernorm_bwd(const float* x, int ldx, const void* dy, int
                                     float* dx_bf16_colsum, int M, int D, void* stream) {
   VC_REQUIRE(x && dy && gamma && dgamma && dbeta && (dx_f32 || dx_bf16) && D == D768 && M > 0, "layernorm_bwd: bad arguments");
   VC_REQUIRE(!dx_bf16_colsum || dx_bf16, "layernorm_bwd: column sums are those of the bf16 output, which was not asked for");
-  static const int nw = [] { const char* e = getenv("VITCAP_LNBWD_WAVES"); const int v = e ? atoi(e) : 8; return v == 4 || v == 16 ? v : 8; }();
+  constexpr int nw = 8;              // waves per workgroup (the kernel stays a template on NW: cast_bf16_colsum_kernel<NW> shares the shape)
   int rpw = 0;
   const int wgs = ln_bwd_grid(M, nw, &rpw);
   dim3 grid(wgs);
   const bool cs = dx_bf16_colsum != nullptr;
   const size_t lds = (size_t)(cs ? 3 : 2) * nw * D768 * sizeof(float);
-#define LNB(F32_, NW_, CS_)                                                                                              \
+#define LNB(F32_, CS_)                                                                                                   \
   do {                                                                                                                  \
-    auto kern = layernorm_bwd_kernel<F32_, NW_, CS_>;                                                                    \
+    auto kern = layernorm_bwd_kernel<F32_, nw, CS_>;                                                                     \
     VC_FUNC_SMEM(kern, (int)lds);                                                                                       \
-    hipLaunchKernelGGL(kern, grid, dim3(NW_ * 64), lds, (hipStream_t)stream, x, ldx, dy, gamma, eps, dres, dx_f32,       \
+    hipLaunchKernelGGL(kern, grid, dim3(nw * 64), lds, (hipStream_t)stream, x, ldx, dy, gamma, eps, dres, dx_f32,        \
                        (bf16_t*)dx_bf16, dgamma, dbeta, dx_bf16_colsum, M, rpw);                                         \
   } while (0)
-#define LNB2(F32_, CS_)                                                                                                  \
-  do { if (nw == 4) LNB(F32_, 4, CS_); else if (nw == 8) LNB(F32_, 8, CS_); else LNB(F32_, 16, CS_); } while (0)
-  if (dy_is_f32) { if (cs) LNB2(true, true); else LNB2(true, false); }
-  else { if (cs) LNB2(false, true); else LNB2(false, false); }
-#undef LNB2
+  if (dy_is_f32) { if (cs) LNB(true, true); else LNB(true, false); }
+  else { if (cs) LNB(false, true); else LNB(false, false); }
 #undef LNB
   VC_LAUNCH_CHECK("layernorm_bwd");
   return VITCAP_OK;
