@@ -265,6 +265,25 @@ int vitcap_greedy_step(const float* logits, int ldl, int V, int64_t* ids, int32_
 /* raw_last (optional, int64 [B]): at t == max_len-1 the token actually chosen at the last position, before it is
  * overwritten by [SEP] for unfinished rows -- the returned log-prob is that of the chosen token (modeling_utils.py:
  * 850-877), which a teacher-forced re-computation of the sequence probability needs. */
+/* The same step with tokens handed in by the caller.  Restates the reference's step loop entered with a prefix
+ * (`_generate_no_beam_search(input_ids, cur_len, ...)` runs from any cur_len, modeling_utils.py:768-886; only ViTCAP.generate drops
+ * the prompt, modeling_bert.py:965) and, with every position given, the sequence score of modeling_utils.py:850-877 on given words.
+ *   forced_ids  int64 [B][max_len] or NULL: -1 (or any id outside [0, V)) = free; a token id f at column t = sequence b, if still
+ *               unfinished at step t, takes f instead of the argmax.  Column 0 is ignored.  Everything else is the step above:
+ *               add = unf ? tok : pad, any EOS id ends the sequence (entries behind the end are ignored), at t == max_len-1
+ *               unfinished rows get eos and raw_last the token taken.
+ *   lp of a forced token = (x[f] - max) - log(sum exp(x - max)) with the free choice's own max and sum: forcing the argmax gives
+ *               the free choice's value bit for bit.  margin_out keeps the top-2 margin of the free choice.
+ *   score_forced 1: forced tokens enter sum_lp / cnt like chosen ones (scoring a given caption);
+ *               0: they do not (a prompt: the reference's loops started at cur_len = P score the generated tokens only).
+ *               logprob = cnt > 0 ? sum_lp / cnt : 0.
+ *   token_logprobs fp32 [B][max_len] or NULL: column t = lp of the token taken at step t while the sequence was unfinished, forced
+ *               or free, counted or not.  Only those entries are written: the caller zeroes the array before step 1.
+ * forced_ids == NULL and token_logprobs == NULL: vitcap_greedy_step. */
+int vitcap_greedy_step_forced(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
+                              float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last, int B, int t,
+                              int max_len, int eos, int pad, const int64_t* forced_ids, int score_forced, float* token_logprobs,
+                              void* stream);
 
 /* Embeddings of the predicted tag tokens written over the last 50 text slots (ViTSplitCLSEmbModel.forward,
  * modeling_bert.py:1435-1489, encode_tag_to_embedding 1381-1406): rows (b, j < n), token = tag_ids[b][j] (int64 [B][50]; slot 49
@@ -290,6 +309,15 @@ int vitcap_greedy_select_embed(const float* rowstat, int pieces, int64_t* ids, i
                                float* logprob_out, int64_t* raw_last, int B, int t, int max_len, int eos, int pad,
                                int mask_token, const void* word_emb, const void* pos_emb, const void* type_emb,
                                const float* gamma, const float* beta, float eps, float* x_f32, void* x_bf16, void* stream);
+/* ... with forced tokens (vitcap_greedy_step_forced: same rule, same three arguments).  The row statistics do not hold x[f], so the
+ * kernel also takes the logits rows [B][ldl] (first V columns valid) the vocabulary GEMM wrote next to them, and reads the one value.
+ * The rows embedded for step t+1 are those of the token taken, i.e. the forced one (the reference feeds `input_ids` with the chosen
+ * token appended back into the model, modeling_utils.py:868).  logits may be NULL when forced_ids is. */
+int vitcap_greedy_select_embed_forced(const float* rowstat, int pieces, const float* logits, int ldl, int V, int64_t* ids,
+                                      int32_t* unfinished, float* sum_lp, float* cnt, float* logprob_out, int64_t* raw_last, int B,
+                                      int t, int max_len, int eos, int pad, int mask_token, const void* word_emb, const void* pos_emb,
+                                      const void* type_emb, const float* gamma, const float* beta, float eps, float* x_f32,
+                                      void* x_bf16, const int64_t* forced_ids, int score_forced, float* token_logprobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sampling variant of the step above (do_sample=True, modeling_utils.py:839-846 + top_k_top_p_filtering
@@ -314,6 +342,14 @@ int vitcap_sample_step(const float* logits, int ldl, int V, int64_t* ids, int32_
 int vitcap_sample_step_offset(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
                               float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last, int B, int t,
                               int max_len, int eos, int pad, const vitcap_sample_params* sp, int seq_offset, void* stream);
+/* ... with forced tokens (arguments and bookkeeping of vitcap_greedy_step_forced).  A forced row draws nothing and is not filtered:
+ * lp = log_softmax(logits / temperature)[f] over the whole row -- under the reference's filtered distribution (modeling_utils.py:
+ * 850-851) a forced token the top-k / top-p filter removes would score -inf.  Its margin_out entry is 0.  The free rows of the same
+ * launch draw exactly what vitcap_sample_step_offset draws: same stream (seed, seq_offset + b, t), same filter. */
+int vitcap_sample_step_forced(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
+                              float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last, int B, int t,
+                              int max_len, int eos, int pad, const vitcap_sample_params* sp, int seq_offset,
+                              const int64_t* forced_ids, int score_forced, float* token_logprobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Tag head tail: prob = sigmoid(logit); top-k (largest, sorted, lowest index first on ties);
@@ -591,6 +627,23 @@ int vitcap_engine_prefill(vitcap_engine* e, int B, const vitcap_gen_opts* opts, 
                           void* stream);
 int vitcap_engine_decode(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                          int64_t* out_ids, float* out_logprobs, int64_t* out_last_tok, void* stream);
+/* vitcap_engine_decode / vitcap_engine_generate with tokens handed in by the caller: caption prefixes (score_forced = 0) and the
+ * score of given captions (score_forced = 1) under the same [MASK]-probe procedure generate uses.  The rule is that of
+ * vitcap_greedy_step_forced / vitcap_sample_step_forced, applied at every step.
+ *   forced_ids         device, int64 [B*seqs_per_image][max_length], image-major (-1 = free); copied into the workspace by the call
+ *   out_token_logprobs device, fp32 [B*seqs_per_image][max_length] or NULL: lp of the token taken at each step, 0 at column 0 and
+ *                      behind the end of a sequence
+ * forced_ids == NULL runs every step free (with out_token_logprobs == NULL too: exactly the plain calls).  num_beams must be 1 and
+ * use_cbs 0: otherwise VITCAP_EINVAL, before anything is enqueued (forced tokens under beam search are not built).  seqs_per_image,
+ * sampling, tag_visible, eos_extra, repetition_penalty (a forced token is scored on the penalised row), decode_streams, encode_parts
+ * and use_graph work as in the plain calls; a replayed graph reads the forced ids of THIS call (they are staged in the workspace). */
+int vitcap_engine_decode_forced(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                float* out_token_logprobs, int64_t* out_last_tok, void* stream);
+int vitcap_engine_generate_forced(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                  void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
+                                  int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
+                                  int64_t* tag_topk_out, void* stream);
 /* copies the tag head's outputs of the last encode on this workspace (either pointer may be NULL) */
 int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                        int64_t* tag_topk_out, void* stream);

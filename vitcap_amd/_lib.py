@@ -179,6 +179,13 @@ _SIGS = {
     'vitcap_greedy_init': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'vitcap_greedy_step': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, vp]),
+    'vitcap_greedy_step_forced': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    'vitcap_greedy_select_embed_forced': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp,
+                                                    vp, C.c_int, vp, vp]),
+    'vitcap_sample_step_forced': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
     'vitcap_greedy_select_embed': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp]),
     'vitcap_sample_step': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
@@ -218,6 +225,9 @@ _SIGS = {
     'vitcap_engine_encode': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp]),
     'vitcap_engine_prefill': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp]),
     'vitcap_engine_decode': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, vp, vp, vp]),
+    'vitcap_engine_decode_forced': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp]),
+    'vitcap_engine_generate_forced': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,
+                                                vp, vp, vp, vp, vp, vp]),
     'vitcap_engine_tags': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, vp, vp, vp]),
     'vitcap_engine_graph_count': (C.c_int, [vp]),
     'vitcap_engine_tap': (vp, [vp, C.c_char_p, vp, C.c_int, C.POINTER(GenOpts)]),

@@ -31,8 +31,12 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const float* __restri
   float se = 0.f;
   for (int i = tid; i < V; i += 1024) se += expf(row[i] - best.v);
   const float tot = block_sum<16>(se, s_sum);
-  // log-prob = logit[tok] - max - log(sum exp(x - max)), tok is the max
-  if (tid == 0) st.commit(b, t, best.i, -logf(tot), best.v - best.second);
+  if (tid != 0) return;
+  const int f = st.forced_at(b, t, V);
+  // log-prob = logit[tok] - max - log(sum exp(x - max)); the free choice is the max itself.  A forced token is scored on the same
+  // row with the same max and sum, so forcing the argmax gives the free choice's own value.
+  if (f < 0) st.commit(b, t, best.i, -logf(tot), best.v - best.second);
+  else st.commit(b, t, f, (row[f] - best.v) - logf(tot), best.v - best.second, st.score_forced != 0);
 }
 
 
@@ -113,6 +117,21 @@ __device__ __forceinline__ float gumbel_score(float x, uint32_t hrow, int i) {
   return x - logf(-logf(vc_uniform(vc_mix(hrow, (uint32_t)i))));
 }
 
+// A forced token under sampling: nothing is filtered and nothing is drawn.  Its log-prob is log_softmax(logits / temperature)[f]
+// over the WHOLE row -- the top-k / top-p filter would score a token it removes at -inf.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void sample_take_forced(const SampleArgs& a, const StepState& st, int b, int t, int f, float* lds_f) {
+  const int tid = threadIdx.x;
+  const float* row = a.logits + (size_t)b * a.ldl;
+  auto scaled = [&](int i) { const float v = row[i]; return a.temperature != 1.0f ? v / a.temperature : v; };
+  float m = -INFINITY;
+  for (int i = tid; i < a.V; i += 1024) m = fmaxf(m, scaled(i));
+  m = block_max<16>(m, lds_f);
+  float se = 0.f;
+  for (int i = tid; i < a.V; i += 1024) se += expf(scaled(i) - m);
+  const float z = block_sum<16>(se, lds_f);
+  if (tid == 0) st.commit(b, t, f, (scaled(f) - m) - logf(z), 0.f, st.score_forced != 0);
+}
+
 // one draw: argmax(x + Gumbel noise) over the surviving set == multinomial(softmax(filtered)), then the step's bookkeeping
 __global__ __launch_bounds__(1024) void sample_step_kernel(SampleArgs a, StepState st, int t) {
   __shared__ SampleLds lds;
@@ -120,6 +139,11 @@ __global__ __launch_bounds__(1024) void sample_step_kernel(SampleArgs a, StepSta
   __shared__ int s_i[16];
   const int b = blockIdx.x, tid = threadIdx.x;
   if (st.skip_finished(b, t)) return;
+  const int f = st.forced_at(b, t, a.V);   // the same for every thread; the free rows of the launch draw what they always draw
+  if (f >= 0) {
+    sample_take_forced(a, st, b, t, f, lds.f);
+    return;
+  }
   float x[SM_NPT], m, z;
   uint32_t key[SM_NPT];
   const uint32_t thr = sample_filter(a, b, 1, x, key, m, z, lds);
@@ -650,15 +674,25 @@ extern "C" int vitcap_greedy_init(int64_t* ids, int32_t* unfinished, float* sum_
   return VITCAP_OK;
 }
 
+extern "C" int vitcap_greedy_step_forced(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
+                                         float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last,
+                                         int B, int t, int max_len, int eos, int pad, const int64_t* forced_ids, int score_forced,
+                                         float* token_logprobs, void* stream) {
+  VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out, "greedy_step: null pointer");
+  VC_REQUIRE(B > 0 && V > 0 && ldl >= V && t >= 1 && t < max_len, "greedy_step: bad sizes (t=%d)", t);
+  VC_REQUIRE(score_forced == 0 || score_forced == 1, "greedy_step: score_forced must be 0 or 1 (got %d)", score_forced);
+  hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V,
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad, forced_ids,
+                                   score_forced, token_logprobs), t);
+  VC_LAUNCH_CHECK("greedy_step");
+  return VITCAP_OK;
+}
+
 extern "C" int vitcap_greedy_step(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
                                   float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last,
                                   int B, int t, int max_len, int eos, int pad, void* stream) {
-  VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out, "greedy_step: null pointer");
-  VC_REQUIRE(B > 0 && V > 0 && ldl >= V && t >= 1 && t < max_len, "greedy_step: bad sizes (t=%d)", t);
-  hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V,
-                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad), t);
-  VC_LAUNCH_CHECK("greedy_step");
-  return VITCAP_OK;
+  return vitcap_greedy_step_forced(logits, ldl, V, ids, unfinished, sum_lp, cnt, logprob_out, margin_out, raw_last, B, t, max_len, eos,
+                                   pad, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int vitcap_sigmoid_topk(const float* logits, int ldl, int V, int k, float thresh, int64_t* out_ids,
@@ -767,18 +801,28 @@ static SampleArgs sample_args(const float* logits, int ldl, int V, const vitcap_
   return SampleArgs{logits, ldl, V, sp->temperature, sp->top_k, sp->top_p, sp->seed, seq_offset};
 }
 
+extern "C" int vitcap_sample_step_forced(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
+                                         float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last,
+                                         int B, int t, int max_len, int eos, int pad, const vitcap_sample_params* sp, int seq_offset,
+                                         const int64_t* forced_ids, int score_forced, float* token_logprobs, void* stream) {
+  VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out && sp, "sample_step: null pointer");
+  VC_REQUIRE(B > 0 && V > 0 && V <= SM_NPT * 1024 && ldl >= V && t >= 1 && t < max_len && seq_offset >= 0,
+             "sample_step: bad sizes (V=%d t=%d)", V, t);
+  VC_REQUIRE(score_forced == 0 || score_forced == 1, "sample_step: score_forced must be 0 or 1 (got %d)", score_forced);
+  if (const int rc = check_sample_params("sample_step", sp)) return rc;
+  hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, sample_args(logits, ldl, V, sp, seq_offset),
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad, forced_ids,
+                                   score_forced, token_logprobs), t);
+  VC_LAUNCH_CHECK("sample_step");
+  return VITCAP_OK;
+}
+
 extern "C" int vitcap_sample_step_offset(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,
                                          float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last,
                                          int B, int t, int max_len, int eos, int pad, const vitcap_sample_params* sp, int seq_offset,
                                          void* stream) {
-  VC_REQUIRE(logits && ids && unfinished && sum_lp && cnt && logprob_out && sp, "sample_step: null pointer");
-  VC_REQUIRE(B > 0 && V > 0 && V <= SM_NPT * 1024 && ldl >= V && t >= 1 && t < max_len && seq_offset >= 0,
-             "sample_step: bad sizes (V=%d t=%d)", V, t);
-  if (const int rc = check_sample_params("sample_step", sp)) return rc;
-  hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, sample_args(logits, ldl, V, sp, seq_offset),
-                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, margin_out, max_len, eos, pad), t);
-  VC_LAUNCH_CHECK("sample_step");
-  return VITCAP_OK;
+  return vitcap_sample_step_forced(logits, ldl, V, ids, unfinished, sum_lp, cnt, logprob_out, margin_out, raw_last, B, t, max_len, eos,
+                                   pad, sp, seq_offset, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int vitcap_sample_step(const float* logits, int ldl, int V, int64_t* ids, int32_t* unfinished,

@@ -205,6 +205,9 @@ struct Enq {
   void* const s;             // stream its launches go to
   const int32_t* const live; // live counter handed to the decode-step launches (null: encoder / prefill, or early_exit off)
   const bool owner;
+  // forced decoding (vitcap_engine_decode_forced): -1 = a plain call; 0 / 1 = score_forced, and the greedy loop reads lo.forced
+  // (staged by the caller of decode_loop) and writes lo.tok_lp
+  int forced = -1;
 
   Enq(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, void* s, Phase ph)
       : e(e), w(e->w), o(o), lo(lo), ws(ws), B(B), s(s),
@@ -619,6 +622,8 @@ struct Enq {
     const int NS = lo.NS, L = lo.L, K = lo.K;
     CK(vitcap_greedy_init(p<int64_t>(lo.ids), p<int32_t>(lo.unf), p<float>(lo.sum_lp), p<float>(lo.cnt), NS, L, o.bos_token_id,
                           o.pad_token_id, s));
+    if (forced >= 0)      // the step kernels write the positions a sequence takes a token at; column 0 and what lies behind its end stay 0
+      HIPCK(hipMemsetAsync(ws + lo.tok_lp, 0, (size_t)NS * lo.tok_lp.unit, (hipStream_t)s), "decode: token log-probs clear");
     // Plain greedy decoding of a small batch: the vocabulary GEMM also emits per-piece (max, argmax, sum exp) of its rows, and ONE
     // kernel turns them into the token, its log-prob, the bookkeeping and the NEXT step's embedded rows -- instead of reading the
     // 30522-wide fp32 rows back (greedy_step 18.7 us) and a separate embedding launch per step.
@@ -647,10 +652,15 @@ struct Enq {
         float *sum_lp = p<float>(lo.sum_lp, s0), *cnt = p<float>(lo.cnt, s0), *logprob = p<float>(lo.logprob, s0);
         float *logits = p<float>(lo.logits, s0), *margins = p<float>(lo.margins, s0);
         int64_t* last_tok = p<int64_t>(lo.last_tok, s0);
+        // a plain call hands the step kernels nulls, which is what the entry points without `_forced` do
+        const int64_t* fids = forced >= 0 ? p<int64_t>(lo.forced, s0) : nullptr;
+        float* tok_lp = forced >= 0 ? p<float>(lo.tok_lp, s0) : nullptr;
+        const int sf = forced > 0 ? 1 : 0;
         if (fused) {
-          CK(vitcap_greedy_select_embed(p<float>(lo.rowstat, s0), RS_PIECES, ids, unf, sum_lp, cnt, logprob, last_tok, pt.ns, t, L,
-                                        o.eos_token_id, o.pad_token_id, o.mask_token_id, w.word_emb, w.pos_emb, w.type_emb, w.emb_ln_g,
-                                        w.emb_ln_b, 1e-12f, p<float>(lo.xs_f, s0), p(lo.xs_b, s0), q.s));
+          CK(vitcap_greedy_select_embed_forced(p<float>(lo.rowstat, s0), RS_PIECES, logits, VP, VITCAP_VOCAB, ids, unf, sum_lp, cnt,
+                                               logprob, last_tok, pt.ns, t, L, o.eos_token_id, o.pad_token_id, o.mask_token_id,
+                                               w.word_emb, w.pos_emb, w.type_emb, w.emb_ln_g, w.emb_ln_b, 1e-12f, p<float>(lo.xs_f, s0),
+                                               p(lo.xs_b, s0), fids, sf, tok_lp, q.s));
           continue;
         }
         if (o.repetition_penalty != 1.0f)
@@ -658,11 +668,11 @@ struct Enq {
         if (o.sampling.do_sample) {
           // the draws are keyed by (seed, sequence index within the call): a slice passes its first sequence as the stream offset
           vitcap_sample_params sp = o.sampling;
-          CK(vitcap_sample_step_offset(logits, VP, VITCAP_VOCAB, ids, unf, sum_lp, cnt, logprob, margins, last_tok, pt.ns, t, L,
-                                       o.eos_token_id, o.pad_token_id, &sp, pt.s0, q.s));
+          CK(vitcap_sample_step_forced(logits, VP, VITCAP_VOCAB, ids, unf, sum_lp, cnt, logprob, margins, last_tok, pt.ns, t, L,
+                                       o.eos_token_id, o.pad_token_id, &sp, pt.s0, fids, sf, tok_lp, q.s));
         } else {
-          CK(vitcap_greedy_step(logits, VP, VITCAP_VOCAB, ids, unf, sum_lp, cnt, logprob, margins, last_tok, pt.ns, t, L, o.eos_token_id,
-                                o.pad_token_id, q.s));
+          CK(vitcap_greedy_step_forced(logits, VP, VITCAP_VOCAB, ids, unf, sum_lp, cnt, logprob, margins, last_tok, pt.ns, t, L,
+                                       o.eos_token_id, o.pad_token_id, fids, sf, tok_lp, q.s));
         }
       }
     }
@@ -769,7 +779,7 @@ struct Enq {
 
  private:
   Enq(const Enq& q, const Layout& lv, int Bv, void* sv)
-      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false) {}
+      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced) {}
 };
 
 vitcap_gen_opts opts_or_default(const vitcap_gen_opts* opts) { return opts ? *opts : default_opts(); }
@@ -789,25 +799,57 @@ int enter(vitcap_engine* e, int B, const vitcap_gen_opts& o, void* ws, size_t ws
   return VITCAP_OK;
 }
 
+// What the `_forced` entry points add to a decode call; a plain call passes the default.
+struct Forced {
+  const int64_t* ids = nullptr;     // device [NS][L] or null
+  int score = 0;
+  float* out_tok_lp = nullptr;      // device [NS][L] or null
+  bool on() const { return ids || out_tok_lp; }
+};
+// forced tokens are built for the greedy / sampling loop only: refused by name before anything is enqueued
+int check_forced(const vitcap_gen_opts& o, const Forced& f) {
+  if (!f.on()) return VITCAP_OK;
+  if (check_opts(o) != VITCAP_OK) return VITCAP_EINVAL;
+  if (o.num_beams > 1 || o.use_cbs) {
+    vitcap_set_error("forced decoding: forced_ids / token_logprobs need num_beams == 1 and no constrained beam search (got num_beams=%d, "
+                     "use_cbs=%d); forced tokens under beam search are not built", o.num_beams, o.use_cbs);
+    return VITCAP_EINVAL;
+  }
+  if (f.score != 0 && f.score != 1) { vitcap_set_error("forced decoding: score_forced must be 0 or 1 (got %d)", f.score); return VITCAP_EINVAL; }
+  return VITCAP_OK;
+}
+
 int decode_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, int64_t* out_ids, float* out_logprobs,
-                  int64_t* out_last_tok, void* s) {
+                  int64_t* out_last_tok, void* s, const Forced& f = Forced()) {
   if (!out_ids || !out_logprobs) { vitcap_set_error("decode: null outputs"); return VITCAP_EINVAL; }
   hipStream_t st = (hipStream_t)s;
   const bool graph = o.use_graph && !o.sampling.do_sample;
+  const int fmode = f.on() ? f.score : -1;
+  // The loop -- eager or replayed -- reads the forced ids from the workspace, never from the caller's array: a captured loop holds
+  // no pointer of the call it was captured in.  No ids given (only the per-token log-probs are wanted): every entry -1.
+  if (fmode >= 0) {
+    const size_t n = (size_t)lo.NS * lo.forced.unit;
+    if (f.ids) HIPCK(hipMemcpyAsync(ws + lo.forced, f.ids, n, hipMemcpyDeviceToDevice, st), "decode: forced ids copy");
+    else HIPCK(hipMemsetAsync(ws + lo.forced, 0xff, n, st), "decode: forced ids clear");
+  }
   if (!graph) {
-    CK(Enq(e, B, o, lo, ws, s, Enq::DECODE).decode_loop());
+    Enq q(e, B, o, lo, ws, s, Enq::DECODE);
+    q.forced = fmode;
+    CK(q.decode_loop());
   } else {
     GraphEntry* hit = nullptr;
     for (auto& g : e->graphs)
-      if (g.B == B && g.ws == (void*)ws && memcmp(&g.opts, &o, sizeof(o)) == 0) { hit = &g; break; }
+      if (g.B == B && g.ws == (void*)ws && g.forced == fmode && memcmp(&g.opts, &o, sizeof(o)) == 0) { hit = &g; break; }
     if (!hit) {
       // capture the loop once: every launch below becomes a kernel node with its arguments frozen (workspace pointers,
       // step index, option values), which is why the key holds all of them
       GraphEntry g;
-      g.B = B; g.ws = (void*)ws; g.opts = o; g.graph = nullptr; g.exec = nullptr;
+      g.B = B; g.ws = (void*)ws; g.opts = o; g.forced = fmode; g.graph = nullptr; g.exec = nullptr;
       if (!e->cap) HIPCK(hipStreamCreateWithFlags(&e->cap, hipStreamNonBlocking), "decode: capture stream");
       HIPCK(hipStreamBeginCapture(e->cap, hipStreamCaptureModeThreadLocal), "decode: begin capture");
-      const int rc = Enq(e, B, o, lo, ws, (void*)e->cap, Enq::DECODE).decode_loop();
+      Enq q(e, B, o, lo, ws, (void*)e->cap, Enq::DECODE);
+      q.forced = fmode;
+      const int rc = q.decode_loop();
       const hipError_t he = hipStreamEndCapture(e->cap, &g.graph);
       if (rc != VITCAP_OK) { if (g.graph) (void)hipGraphDestroy(g.graph); return rc; }
       HIPCK(he, "decode: end capture");
@@ -832,6 +874,8 @@ int decode_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layou
     // the token chosen at the last position before the forced [SEP] (its log-probability is what the score holds)
     if (out_last_tok)
       HIPCK(hipMemcpyAsync(out_last_tok, ws + lo.last_tok, (size_t)lo.NS * 8, hipMemcpyDeviceToDevice, st), "decode: last-token copy");
+    if (f.out_tok_lp)
+      HIPCK(hipMemcpyAsync(f.out_tok_lp, ws + lo.tok_lp, (size_t)lo.NS * lo.tok_lp.unit, hipMemcpyDeviceToDevice, st), "decode: token log-probs copy");
   }
   return VITCAP_OK;
 }
@@ -925,6 +969,19 @@ extern "C" int vitcap_engine_decode(vitcap_engine* e, int B, const vitcap_gen_op
   return decode_locked(e, B, o, lo, (char*)workspace, out_ids, out_logprobs, out_last_tok, s);
 }
 
+extern "C" int vitcap_engine_decode_forced(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                           const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                           float* out_token_logprobs, int64_t* out_last_tok, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs;
+  CK(check_forced(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  return decode_locked(e, B, o, lo, (char*)workspace, out_ids, out_logprobs, out_last_tok, s, f);
+}
+
 extern "C" int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                                   int64_t* tag_topk_out, void* s) {
   const vitcap_gen_opts o = opts_or_default(opts);
@@ -943,6 +1000,24 @@ extern "C" int vitcap_engine_generate(vitcap_engine* e, const void* image, int i
   CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
   CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
   CK(decode_locked(e, B, o, lo, ws, out_ids, out_logprobs, nullptr, s));
+  return tags_copy(lo, B, ws, tag_logits_out, tag_topk_out, s);
+}
+
+extern "C" int vitcap_engine_generate_forced(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                             void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
+                                             int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
+                                             int64_t* tag_topk_out, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs;
+  CK(check_forced(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  char* ws = (char*)workspace;
+  std::lock_guard<std::mutex> lk(e->mu);
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
+  CK(decode_locked(e, B, o, lo, ws, out_ids, out_logprobs, nullptr, s, f));
   return tags_copy(lo, B, ws, tag_logits_out, tag_topk_out, s);
 }
 

@@ -23,6 +23,7 @@ struct GraphEntry {
   int B;
   void* ws;
   vitcap_gen_opts opts;
+  int forced;         // Enq::forced of the captured loop: -1 plain, else score_forced (the staged ids themselves live in the workspace)
   hipGraph_t graph;
   hipGraphExec_t exec;
 };

@@ -80,6 +80,9 @@ struct Buf {
   X(margins, SEQ, L * 4, true)                                                                                                     \
   X(logprob, SEQ, 4, true)                                                                                                         \
   X(last_tok, SEQ, 8, true)                                                                                                        \
+  /* forced decoding (vitcap_engine_decode_forced): the call's copy of the caller's tokens and the per-token log-probs */         \
+  X(forced, SEQ, L * 8, !beam && !cbs)                                                                                             \
+  X(tok_lp, SEQ, L * 4, !beam && !cbs)                                                                                             \
   X(live, FIXED, 256, true)                                                                                                        \
   /* tag rows visible to the caption (tag_visible = NT > 0), per embedding branch A / B: state, then per decoder layer the tag */  \
   /* rows' packed q|k|v = their K/V cache */                                                                                       \

@@ -112,7 +112,10 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const int64_t* __restri
 //   tok = column of the overall maximum, lowest column on ties (torch.argmax);  lp = log_softmax(row)[tok] =
 //   -log(sum_pieces s_p * exp(m_p - M));  then the step's bookkeeping (StepState, select.h);
 //   rows (b,0) = word[ids[b][t]] + pos[t] + type[0], (b,1) = word[MASK] + pos[t+1] + type[0], LayerNorm -> x of step t+1.
-__global__ __launch_bounds__(128) void greedy_select_embed_kernel(const float* __restrict__ rowstat, int pieces, StepState st, int t,
+// With st.forced the token forced at (b, t) is taken instead (and embedded for step t+1): its logit x[f] comes from the logits row
+// the vocabulary GEMM wrote next to the statistics, lp = (x[f] - M) - log(sum) with the free choice's own M and sum.
+__global__ __launch_bounds__(128) void greedy_select_embed_kernel(const float* __restrict__ rowstat, int pieces,
+                                                                  const float* __restrict__ logits, int ldl, int V, StepState st, int t,
                                                                   int mask_token, EmbedTables tb, const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
                                                                   float* __restrict__ xf, bf16_t* __restrict__ xb) {
@@ -139,7 +142,11 @@ __global__ __launch_bounds__(128) void greedy_select_embed_kernel(const float* _
     }
     // 0 + s0 + s1 == s0 + s1: the two wave partials are added as before.  logit[tok] - M - log(sum exp(x - M)), tok is the maximum
     const float lp = -logf(block_sum<2>(se, s_s));
-    if (tid == 0) s_tok = st.commit(b, t, best.i, lp, 0.f);
+    if (tid == 0) {
+      const int f = logits ? st.forced_at(b, t, V) : -1;
+      if (f < 0) s_tok = st.commit(b, t, best.i, lp, 0.f);
+      else s_tok = st.commit(b, t, f, (logits[(size_t)b * ldl + f] - best.v) + lp, 0.f, st.score_forced != 0);
+    }
   }
   if (last) return;
   __syncthreads();
@@ -314,21 +321,35 @@ extern "C" int vitcap_embed_step(const int64_t* ids, int max_len, int t, int mas
   return VITCAP_OK;
 }
 
+extern "C" int vitcap_greedy_select_embed_forced(const float* rowstat, int pieces, const float* logits, int ldl, int V, int64_t* ids,
+                                                 int32_t* unfinished, float* sum_lp, float* cnt, float* logprob_out, int64_t* raw_last,
+                                                 int B, int t, int max_len, int eos, int pad, int mask_token, const void* word_emb,
+                                                 const void* pos_emb, const void* type_emb, const float* gamma, const float* beta,
+                                                 float eps, float* x_f32, void* x_bf16, const int64_t* forced_ids, int score_forced,
+                                                 float* token_logprobs, void* stream) {
+  VC_REQUIRE(rowstat && ids && unfinished && sum_lp && cnt && logprob_out, "greedy_select_embed: null pointer");
+  VC_REQUIRE(B > 0 && pieces > 0 && t >= 1 && t < max_len, "greedy_select_embed: bad sizes (t=%d, pieces=%d)", t, pieces);
+  VC_REQUIRE(t == max_len - 1 || (word_emb && pos_emb && type_emb && gamma && beta && x_f32 && x_bf16),
+             "greedy_select_embed: the embedding of step t+1 needs the tables and outputs");
+  VC_REQUIRE(!forced_ids || (logits && V > 0 && ldl >= V), "greedy_select_embed: forced tokens need the logits rows (ldl=%d, V=%d)", ldl, V);
+  VC_REQUIRE(score_forced == 0 || score_forced == 1, "greedy_select_embed: score_forced must be 0 or 1 (got %d)", score_forced);
+  hipLaunchKernelGGL(greedy_select_embed_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, rowstat, pieces, logits, ldl, V,
+                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, nullptr, max_len, eos, pad, forced_ids,
+                                   score_forced, token_logprobs), t, mask_token,
+                     EmbedTables{(const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb}, gamma, beta, eps, x_f32,
+                     (bf16_t*)x_bf16);
+  VC_LAUNCH_CHECK("greedy_select_embed");
+  return VITCAP_OK;
+}
+
 extern "C" int vitcap_greedy_select_embed(const float* rowstat, int pieces, int64_t* ids, int32_t* unfinished, float* sum_lp,
                                           float* cnt, float* logprob_out, int64_t* raw_last, int B, int t, int max_len, int eos,
                                           int pad, int mask_token, const void* word_emb, const void* pos_emb,
                                           const void* type_emb, const float* gamma, const float* beta, float eps, float* x_f32,
                                           void* x_bf16, void* stream) {
-  VC_REQUIRE(rowstat && ids && unfinished && sum_lp && cnt && logprob_out, "greedy_select_embed: null pointer");
-  VC_REQUIRE(B > 0 && pieces > 0 && t >= 1 && t < max_len, "greedy_select_embed: bad sizes (t=%d, pieces=%d)", t, pieces);
-  VC_REQUIRE(t == max_len - 1 || (word_emb && pos_emb && type_emb && gamma && beta && x_f32 && x_bf16),
-             "greedy_select_embed: the embedding of step t+1 needs the tables and outputs");
-  hipLaunchKernelGGL(greedy_select_embed_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, rowstat, pieces,
-                     vc_step_state(ids, unfinished, sum_lp, cnt, logprob_out, raw_last, nullptr, max_len, eos, pad), t, mask_token,
-                     EmbedTables{(const bf16_t*)word_emb, (const bf16_t*)pos_emb, (const bf16_t*)type_emb}, gamma, beta, eps, x_f32,
-                     (bf16_t*)x_bf16);
-  VC_LAUNCH_CHECK("greedy_select_embed");
-  return VITCAP_OK;
+  return vitcap_greedy_select_embed_forced(rowstat, pieces, nullptr, 0, 0, ids, unfinished, sum_lp, cnt, logprob_out, raw_last, B, t,
+                                           max_len, eos, pad, mask_token, word_emb, pos_emb, type_emb, gamma, beta, eps, x_f32, x_bf16,
+                                           nullptr, 0, nullptr, stream);
 }
 
 extern "C" int vitcap_tag_embed(const int64_t* tag_ids, int n, int pos0, int branch_a, int tagemb_cls, const void* cls_w, const void* word_emb,

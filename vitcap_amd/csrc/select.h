@@ -206,6 +206,19 @@ struct StepState {
   int32_t* live;         // null or the counter of unfinished sequences (call_state.h)
   int max_len, eos, pad;
   VcEosExtra eos_x;
+  // Tokens handed in by the caller (include/vitcap_hip.h: vitcap_greedy_step_forced).  All null / 0 from the plain entry points.
+  const int64_t* forced = nullptr;   // [B][max_len] or null: -1 = free, a token id = taken instead of the step's own choice
+  float* tok_lp = nullptr;           // [B][max_len] or null: log-prob of the token taken at position t (the caller zeroes the array)
+  int score_forced = 0;              // 1: forced tokens enter sum_lp / cnt like chosen ones; 0: they do not (a prompt)
+
+  // the token forced on sequence b at position t, or -1: none (an id outside [0, V) forces nothing)
+  __device__ __forceinline__ int forced_at(int b, int t, int V) const {
+    if (!forced) return -1;
+    const int64_t f = forced[(size_t)b * max_len + t];
+    return f >= 0 && f < (int64_t)V ? (int)f : -1;
+  }
+  // sum_lp / cnt; a sequence none of whose tokens were counted (a prompt that ends it) scores 0
+  __device__ __forceinline__ static float mean_lp(float s, float c) { return c > 0.f ? s / c : 0.f; }
 
   // Finished sequence: tokens_to_add = pad, the score is frozen (modeling_utils.py:855-858, 873-877).  Every thread of the
   // workgroup calls it; true = nothing else to do for sequence b (its logits need not even exist).
@@ -215,22 +228,24 @@ struct StepState {
       ids[(size_t)b * max_len + t] = pad;
       if (t == max_len - 1) {
         if (raw_last) raw_last[b] = pad;
-        logprob_out[b] = sum_lp[b] / cnt[b];
+        logprob_out[b] = mean_lp(sum_lp[b], cnt[b]);
       }
     }
     return true;
   }
   // Unfinished sequence b takes `token` with log-prob `logprob` at position t; one thread calls it.  Returns what ids[b][t] holds.
-  __device__ __forceinline__ int64_t commit(int b, int t, int token, float logprob, float margin) const {
+  // counted = false: a forced token in prompt mode -- taken like any other, but the score does not see it.
+  __device__ __forceinline__ int64_t commit(int b, int t, int token, float logprob, float margin, bool counted = true) const {
     if (margin_out) margin_out[(size_t)b * max_len + t] = margin;
-    const float s = sum_lp[b] + logprob;
-    const float c = cnt[b] + 1.0f;
+    if (tok_lp) tok_lp[(size_t)b * max_len + t] = logprob;
+    const float s = counted ? sum_lp[b] + logprob : sum_lp[b];
+    const float c = counted ? cnt[b] + 1.0f : cnt[b];
     const bool open = !vc_is_eos(token, eos, eos_x);   // any id of eos_token_ids finishes the sequence (modeling_utils.py:862-865)
     int64_t outtok = token;
     if (t == max_len - 1) {
       if (raw_last) raw_last[b] = token;               // the token actually chosen, before the forced [SEP]
       if (open) outtok = eos;                          // modeling_utils.py:870-871
-      logprob_out[b] = s / c;                          // modeling_utils.py:873-877
+      logprob_out[b] = mean_lp(s, c);                  // modeling_utils.py:873-877
     }
     ids[(size_t)b * max_len + t] = outtok;
     sum_lp[b] = s;
@@ -242,6 +257,8 @@ struct StepState {
 };
 // the state of the call being enqueued: the launcher's arguments plus the engine's per-call thread-locals
 static inline StepState vc_step_state(int64_t* ids, int32_t* unf, float* sum_lp, float* cnt, float* logprob_out, int64_t* raw_last,
-                                      float* margin_out, int max_len, int eos, int pad) {
-  return StepState{ids, unf, sum_lp, cnt, logprob_out, raw_last, margin_out, (int32_t*)vc_tls_live, max_len, eos, pad, vc_tls_eos_extra};
+                                      float* margin_out, int max_len, int eos, int pad, const int64_t* forced = nullptr,
+                                      int score_forced = 0, float* tok_lp = nullptr) {
+  return StepState{ids, unf, sum_lp, cnt, logprob_out, raw_last, margin_out, (int32_t*)vc_tls_live, max_len, eos, pad, vc_tls_eos_extra,
+                   forced, tok_lp, score_forced != 0};
 }

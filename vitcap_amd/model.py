@@ -368,45 +368,112 @@ class ImageCaptioning(nn.Module):
         return (torch.empty(shape + (o.max_length,), dtype=torch.int64, device=dev),
                 torch.empty(shape, dtype=torch.float32, device=dev))
 
-    def run(self, image, opts, want_tags=False, slot=0, want_last=False):
-        """One vitcap_engine_generate call on the current stream under `opts` (a vitcap_gen_opts from gen_options())."""
+    @staticmethod
+    def refuse_forced_search(num_beams, use_cbs):
+        """Forced tokens (a caption prefix, a caption to score) exist for the greedy / sampling loop only."""
+        if int(num_beams or 1) > 1 or use_cbs:
+            raise NotImplementedError('prefix_ids / forced tokens need num_beams == 1 and use_cbs off: forced tokens under beam search '
+                                      'are not built (got num_beams=%s, use_cbs=%s)' % (num_beams, bool(use_cbs)))
+
+    def run(self, image, opts, want_tags=False, slot=0, want_last=False, forced=None, score_forced=0, want_token_logprobs=False):
+        """One vitcap_engine_generate call on the current stream under `opts` (a vitcap_gen_opts from gen_options()).
+        forced (rows, max_length) int64 / score_forced: vitcap_amd.forced.pack_forced; with want_token_logprobs the per-token
+        log-probs (rows, max_length) are returned last.  Either one makes it a vitcap_engine_generate_forced call."""
+        use_forced = forced is not None or want_token_logprobs
+        if use_forced:
+            self.refuse_forced_search(opts.num_beams, opts.use_cbs)
         dev = self._check_image(image)
         B = image.shape[0]
+        rows = B * opts.seqs_per_image
+        fp = tp = tok_lp = None
+        if forced is not None:
+            if tuple(forced.shape) != (rows, opts.max_length):
+                raise ValueError('forced ids must be (%d, %d), got %s' % (rows, opts.max_length, tuple(forced.shape)))
+            forced = forced.to(device=dev, dtype=torch.int64).contiguous()
+            fp = C.c_void_p(forced.data_ptr())
+        if want_token_logprobs:
+            tok_lp = torch.empty((rows, opts.max_length), dtype=torch.float32, device=dev)
+            tp = C.c_void_p(tok_lp.data_ptr())
         ws, need = self._workspace(B, dev, slot, opts)
         ids, lp = self._out_buffers(B, opts, dev)
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         wp = C.c_void_p(ws.data_ptr())
+        extra = (tok_lp,) if want_token_logprobs else ()
         if want_last:
-            last = torch.empty((B * opts.seqs_per_image,), dtype=torch.int64, device=dev)
+            last = torch.empty((rows,), dtype=torch.int64, device=dev)
             check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
                                            C.byref(opts), wp, need, s), 'engine_encode')
             check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
-            check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()),
-                                           C.c_void_p(lp.data_ptr()), C.c_void_p(last.data_ptr()), s), 'engine_decode')
-            return ids, lp, last
+            if use_forced:
+                check(lib.vitcap_engine_decode_forced(self._engine, B, C.byref(opts), wp, need, fp, int(score_forced),
+                                                      C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tp,
+                                                      C.c_void_p(last.data_ptr()), s), 'engine_decode_forced')
+            else:
+                check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()),
+                                               C.c_void_p(lp.data_ptr()), C.c_void_p(last.data_ptr()), s), 'engine_decode')
+            return (ids, lp, last) + extra
         tag_logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev) if want_tags else None
         tag_topk = torch.empty((B, 50), dtype=torch.int64, device=dev) if want_tags else None
-        check(lib.vitcap_engine_generate(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                         C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()),
-                                         C.c_void_p(tag_logits.data_ptr()) if want_tags else None,
-                                         C.c_void_p(tag_topk.data_ptr()) if want_tags else None, s), 'engine_generate')
+        tl = C.c_void_p(tag_logits.data_ptr()) if want_tags else None
+        tk = C.c_void_p(tag_topk.data_ptr()) if want_tags else None
+        if use_forced:
+            check(lib.vitcap_engine_generate_forced(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                                    C.byref(opts), wp, need, fp, int(score_forced), C.c_void_p(ids.data_ptr()),
+                                                    C.c_void_p(lp.data_ptr()), tp, tl, tk, s), 'engine_generate_forced')
+        else:
+            check(lib.vitcap_engine_generate(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                             C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tl, tk, s),
+                  'engine_generate')
         if want_tags:
             self.last_tags = (tag_logits, tag_topk)
         self._last = (slot, opts, B)
-        return ids, lp
+        return (ids, lp) + extra
 
-    def generate(self, image, want_tags=False, slot=0, **over):
-        """Greedy captions.  image: (B,3,384,384) fp32 or bf16 on the GPU, normalised with mean=.5/std=.5."""
-        return self.run(image, self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over),
-                        want_tags=want_tags, slot=slot)
+    @staticmethod
+    def _prefix_forced(prefix_ids, B, K, max_length):
+        """prefix_ids (B, P) -- one prefix per image, shared by its K sequences -- or (B*K, P) -> pack_forced's (forced, 0)."""
+        from .forced import pack_forced
+        if prefix_ids is None:
+            return None, 0
+        p = torch.as_tensor(prefix_ids)
+        if K > 1 and p.dim() == 2 and p.shape[0] == B:
+            p = p.repeat_interleave(K, 0)
+        return pack_forced(prefix_ids=p, rows=B * K, max_length=max_length)
 
-    def generate_multi(self, image, seqs_per_image, slot=0, want_last=False, **over):
+    def generate(self, image, want_tags=False, slot=0, prefix_ids=None, want_token_logprobs=False, **over):
+        """Greedy captions.  image: (B,3,384,384) fp32 or bf16 on the GPU, normalised with mean=.5/std=.5.
+        prefix_ids (B, P), -1-padded: the captions start with these tokens (positions 1..P; they do not enter the score, like a
+        reference loop started at cur_len = P).  want_token_logprobs: returns (ids, logprobs, token_logprobs (B, L))."""
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        forced, sf = self._prefix_forced(prefix_ids, image.shape[0], 1, o.max_length)
+        return self.run(image, o, want_tags=want_tags, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs)
+
+    def generate_multi(self, image, seqs_per_image, slot=0, want_last=False, prefix_ids=None, want_token_logprobs=False, **over):
         """`seqs_per_image` sampled sequences per image (num_return_sequences of ViTCAP.generate): the encoder and the
         visual prefill run once per image, the sequences of an image share its visual K/V.  Returns (ids (B*n,1,L),
         logprobs (B*n,1)) image-major -- the same sequences generate() gives on the n-times repeated batch -- and, with
-        want_last, the token chosen at the last position (before the forced [SEP]) of every sequence."""
+        want_last, the token chosen at the last position (before the forced [SEP]) of every sequence.
+        prefix_ids (B, P) or (B*n, P) / want_token_logprobs: as generate(); the per-token log-probs come last."""
         o = self.gen_options(num_beams=1, num_keep_best=1, num_return_sequences=int(seqs_per_image), do_sample=True, **over)
-        return self.run(image, o, slot=slot, want_last=want_last)
+        forced, sf = self._prefix_forced(prefix_ids, image.shape[0], o.seqs_per_image, o.max_length)
+        return self.run(image, o, slot=slot, want_last=want_last, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs)
+
+    def score(self, image, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+        """Log-probability of GIVEN captions under the procedure generate() uses: one [MASK] probe per position on the tokens so
+        far, log_softmax gathered at the given token, averaged over the positions up to and including the first [SEP]
+        (modeling_utils.py:850-877 on given words).  caption_ids (B * seqs_per_image, L) image-major: [CLS] first,
+        [SEP]-terminated, 0-padded -- what generate() returns.  The K captions of an image share its encoder pass and visual K/V.
+        A [SEP] in the last column of a caption that has not ended before it was written by the max-length rule, not chosen: that
+        position is scored on the loop's own choice, or on last_tok[row] when given (vitcap_amd.forced.pack_forced).
+        -> (logprob (rows,), token_logprobs (rows, L)); with return_ids also the ids the loop wrote."""
+        from .forced import pack_forced
+        K = int(seqs_per_image)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        o.seqs_per_image = K
+        check(lib.vitcap_gen_opts_check(C.byref(o)), 'gen_opts')
+        forced, sf = pack_forced(caption_ids=caption_ids, rows=image.shape[0] * K, max_length=o.max_length, last_tok=last_tok)
+        ids, lp, tok_lp = self.run(image, o, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=True)
+        return (lp.view(-1), tok_lp, ids) if return_ids else (lp.view(-1), tok_lp)
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like
@@ -524,6 +591,10 @@ class ImageCaptioning(nn.Module):
             return eng.loss_dict(data)
         te = self.test_extra_input
         over = {}
+        # a caption prefix per image: batch key `prefix_ids` (B, P), or the same for every call in test_extra_input
+        prefix = data.pop('prefix_ids', te.get('prefix_ids'))
+        if prefix is not None:
+            self.refuse_forced_search(te.get('num_beams', 1), te.get('use_cbs', False))
         if te.get('do_sample', False):
             # every forward() call advances the stream of draws, like consecutive torch.multinomial calls would
             self._sample_calls = getattr(self, '_sample_calls', 0) + 1
@@ -534,6 +605,8 @@ class ImageCaptioning(nn.Module):
             # beyond the engine's sequences-per-image limit: expand the inputs like the reference does (modeling_bert.py:976-994)
             image = image.repeat_interleave(nret, 0).contiguous()
             over['num_return_sequences'] = 1
+            if prefix is not None and torch.as_tensor(prefix).shape[0] * nret == image.shape[0]:
+                prefix = torch.as_tensor(prefix).repeat_interleave(nret, 0)
         if te.get('use_cbs', False):
             # the batch carries the machines (modeling_bert.py:932: generate's own kwargs)
             n_tag = self.check_text_inputs(data, int(te.get('max_length', L.MAXLEN)))
@@ -549,4 +622,5 @@ class ImageCaptioning(nn.Module):
             if opts.tag_visible:
                 raise ValueError('test_extra_input tag_visible=%d but the attention_mask shows %d tag slots' % (opts.tag_visible, n_tag))
             opts = self.gen_options(tag_visible=n_tag, **over)      # the caller's mask decides
-        return self.run(image, opts)
+        forced, sf = self._prefix_forced(prefix, image.shape[0], opts.seqs_per_image, opts.max_length)
+        return self.run(image, opts, forced=forced, score_forced=sf)

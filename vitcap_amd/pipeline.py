@@ -136,7 +136,10 @@ class _PredictRun(object):
 
     def __init__(self, pipe, model):
         self.pipe, self.model = pipe, model
-        self.overlap = not model.test_extra_input.get('do_sample', False)
+        # cfg.caption_prefix: every caption starts with this text.  Forced tokens go through model.forward (batch key `prefix_ids`),
+        # which has no two-slot form: such a run decodes batch by batch
+        self.prefix = pipe.caption_prefix_ids()
+        self.overlap = not model.test_extra_input.get('do_sample', False) and self.prefix is None
         # the same option validation ImageCaptioning.forward applies (max_length, repetition_penalty, num_keep_best, use_cbs,
         # token ids ...): an option this build does not implement raises here instead of being decoded with defaults
         self.base = model.gen_options(gemm_mode=1) if self.overlap else None
@@ -157,6 +160,8 @@ class _PredictRun(object):
         """Starts one batch and queues (batch, output or its future, device-side mask verdict, count it was compared with)."""
         model, flag, expect_n = self.model, None, None
         if not self.overlap:
+            if self.prefix is not None:
+                batch = dict(batch, prefix_ids=torch.tensor([self.prefix] * batch['image'].shape[0], dtype=torch.int64))
             self.pending.append((batch, model(batch), flag, expect_n))
             return
         # host tensors (what the loader yields) are checked on the host; tensors already on the device cost ONE host
@@ -309,6 +314,19 @@ class CaptionUniPipeline(object):
                 raise FileNotFoundError('BERT vocab not found at %s (text_encoder_type: %s)' % (vf, self.cfg.text_encoder_type))
             self._tokenizer = CaptionDetokenizer(vf)
         return self._tokenizer
+
+    def caption_prefix_ids(self):
+        """Optional config key `caption_prefix: "<text>"` -> its WordPiece ids (no special tokens), or None."""
+        text = self.cfg.caption_prefix
+        if not text:
+            return None
+        from .tokenizer import BertWordPieceTokenizer
+        tok = BertWordPieceTokenizer(tokens=self.tokenizer.ids_to_tokens)
+        ids = tok.convert_tokens_to_ids(tok.tokenize(str(text)))
+        if not ids or len(ids) > int(self.cfg.max_gen_length) - 1:
+            raise ValueError('caption_prefix %r gives %d tokens; max_gen_length=%s leaves 1..%d'
+                             % (text, len(ids), self.cfg.max_gen_length, int(self.cfg.max_gen_length) - 1))
+        return ids
 
     def get_raw_model(self, is_train):
         from .model import ImageCaptioning
