@@ -284,6 +284,23 @@ int vitcap_greedy_step_forced(const float* logits, int ldl, int V, int64_t* ids,
                               float* sum_lp, float* cnt, float* logprob_out, float* margin_out, int64_t* raw_last, int B, int t,
                               int max_len, int eos, int pad, const int64_t* forced_ids, int score_forced, float* token_logprobs,
                               void* stream);
+/* The score of GIVEN captions from the logits of their [MASK] probe rows, all positions at once (one-pass scoring): what
+ * vitcap_greedy_step_forced(score_forced = 1) leaves after max_len - 1 steps.  Probe row g = caption g / (max_len-1), position
+ * t = g % (max_len-1) + 1; the call covers rows [rows0, rows0 + n_rows) of the n_caps * (max_len-1) rows and `logits` (fp32
+ * [n_rows][ldl], first V columns valid) holds exactly those, so that the vocabulary GEMM can run in row chunks.
+ *   caption_ids int64 [n_caps][max_len]; lp = (x[f] - max) - log(sum exp(x - max)) with f = caption_ids[b][t].  A position counts
+ *               while the caption is unfinished, up to and including its first EOS id (eos, or eos_extra: host, 3 ids, -1 = unused,
+ *               or NULL); behind the end token_logprobs is 0 and out_ids pad.  Column 0: token_logprobs 0, out_ids the caption's.
+ *   last column a caption that has not ended before it and holds `eos` there carries the max-length rule's [SEP], not a choice
+ *               (modeling_utils.py:870-871): the scored token is last_tok[b] (int64 [n_caps] or NULL) when that is an id of the
+ *               vocabulary, else the row's argmax (lowest index on ties); out_last_tok[b] (optional) receives it and out_ids keeps
+ *               eos.  Any other token there is scored as written (out_last_tok = that token; out_ids = eos unless it is an EOS id).
+ *   sums        sum_lp / cnt (optional) / logprob_out [n_caps] = cnt > 0 ? sum_lp / cnt : 0, added in position order, are written
+ *               by the call whose range holds the caption's LAST probe row: the chunks are enqueued in row order on one stream.
+ * Everything is decided on the device; a result does not depend on how the rows are chunked. */
+int vitcap_score_rows(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0, int n_rows,
+                      int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, float* sum_lp, float* cnt,
+                      float* token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* logprob_out, void* stream);
 
 /* Embeddings of the predicted tag tokens written over the last 50 text slots (ViTSplitCLSEmbModel.forward,
  * modeling_bert.py:1435-1489, encode_tag_to_embedding 1381-1406): rows (b, j < n), token = tag_ids[b][j] (int64 [B][50]; slot 49
@@ -472,6 +489,21 @@ int vitcap_attn_decode_beams(const void* qkv_step, const void* vis_qkv, const vo
 int vitcap_attn_decode_beam_groups(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
                                    int n_images, int seq_per_group, int groups_per_image, int S_vis, int t, int max_len, float scale,
                                    void* stream);
+/* Text-grid attention of the one-pass caption scorer: all steps of a GIVEN caption at once, the captions of an image sharing its
+ * visual K/V (csrc/attn_grid.hip).
+ *   qkv_text  bf16 [n_images * caps_per_image][R][2304], R = 2 * max_len - 1 rows per caption, image-major: rows 0..L-1 the caption's
+ *             tokens at positions 0..L-1, row L + j (j = 0..L-2) the [MASK] probe at position j + 1 -- what
+ *             vitcap_embed_rows(rows_per_seq = R, pos_wrap = max_len) embeds;
+ *   vis_qkv   one layer's prefill cache, bf16 [n_images * S_vis][2304] (K at column 768, V at 1536);
+ *   vis_vt    vitcap_attn_beam_vt of it;      out  bf16 [n_images * caps_per_image * R][768].
+ * Mask (modeling_bert.py:846-876 evaluated for every step): token row r attends the visual rows and token rows <= r; probe j attends
+ * the visual rows, token rows 0..j and itself; nobody else attends a probe.  Softmax as vitcap_attn_decode_step (log2 domain,
+ * m = ceil(max * c), P rounded to bf16 for the product, row sum from the unrounded P).  Every row of `out` is written; token row
+ * L-1 is attended by nobody and feeds nothing.  One workgroup per (head, image, group of <= 8 captions): the visual K rows and the
+ * V^T panel are loaded once per workgroup.  S_vis == 578, 2 <= max_len <= 40, 1 <= caps_per_image <= 32; anything else is refused
+ * (VITCAP_EINVAL) with `out` untouched. */
+int vitcap_attn_text_grid(const void* qkv_text, const void* vis_qkv, const void* vis_vt, void* out, int n_images, int caps_per_image,
+                          int S_vis, int max_len, float scale, void* stream);
 
 /* small data movers used by the engine and exposed for tests */
 int vitcap_assemble_visual(const float* hidden, const float* tag_hidden, float* vis_f32, void* vis_bf16,
@@ -644,6 +676,33 @@ int vitcap_engine_generate_forced(vitcap_engine* e, const void* image, int image
                                   void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
                                   int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
                                   int64_t* tag_topk_out, void* stream);
+/* One-pass scoring of GIVEN captions: every token is known in advance, so the max_length - 1 sequential steps of
+ * vitcap_engine_decode_forced(score_forced = 1) become one pass over a [token rows | [MASK] probe rows] grid of 2 * max_length - 1 rows
+ * per caption -- four decoder layers of full-size GEMMs, vitcap_attn_text_grid against the image's visual K/V, the LM head on the probe
+ * rows (vocabulary GEMM in chunks of 2048 rows) and vitcap_score_rows.  Same rounding points as the step loop (fp32 residual stream,
+ * bf16 GEMM operands and qkv); results agree with it within the bounds both meet against the reference, not bit for bit.
+ *   caps_per_image     1..32 captions per image, image-major (vitcap_gen_opts.seqs_per_image is not read by these calls)
+ *   caption_ids        device, int64 [B*caps_per_image][max_length]: [CLS] first, EOS-terminated, pad behind; copied by the call
+ *   last_tok           device, int64 [B*caps_per_image] or NULL: vitcap_score_rows' last-column rule
+ *   score_ws           device, 256-byte aligned, vitcap_engine_score_workspace_bytes(B, caps_per_image, opts) bytes: the text grid's
+ *                      buffers (csrc/engine_layout.h: 0.66 GB at 64 images x 5 captions, 2.51 GB at 64 x 32, max_length 20)
+ *   out_logprobs       fp32 [B*caps];  out_ids int64 [B*caps][max_length];  out_token_logprobs fp32 [B*caps][max_length] or NULL;
+ *                      out_last_tok int64 [B*caps] or NULL -- as vitcap_engine_decode_forced returns them
+ * vitcap_engine_score_text runs after vitcap_engine_encode + vitcap_engine_prefill on `workspace` and READS only the per-layer visual
+ * caches of it: the same images can be scored again with other captions without re-encoding.  vitcap_engine_score = encode + prefill
+ * + score_text.  Refused with VITCAP_EINVAL before anything is enqueued, the option named in vitcap_last_error(): num_beams > 1,
+ * use_cbs, tag_visible > 0, sampling.do_sample, repetition_penalty != 1 (the stepwise path scores the penalised row), caps_per_image
+ * outside 1..32, null ids / outputs; a score workspace that is too small: VITCAP_EWORKSPACE.  eos_extra and max_length 2..40 work as
+ * in the plain calls.  No hipGraph is captured for this path (use_graph is ignored). */
+size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image, const vitcap_gen_opts* opts);
+int vitcap_engine_score_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                             int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                             size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                             int64_t* out_last_tok, void* stream);
+int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts, void* workspace,
+                        size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                        size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
+                        void* stream);
 /* copies the tag head's outputs of the last encode on this workspace (either pointer may be NULL) */
 int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                        int64_t* tag_topk_out, void* stream);
@@ -655,7 +714,8 @@ int vitcap_repetition_penalty(float* logits, int ldl, int V, const int64_t* ids,
                               void* stream);
 
 /* Debug/parity taps into the workspace after a generate call (device pointers, valid until the next call): name in
- * {"hidden","tag_hidden","vis","logits_last","margins","tag_logits","tag_prob","tag_len","ids","last_token","live"} */
+ * {"hidden","tag_hidden","vis","logits_last","margins","tag_logits","tag_prob","tag_len","ids","last_token","live",
+ * "dqkv0".."dqkv3" (the per-layer visual q|k|v caches of the prefill, bf16 [B*578][2304])} */
 const void* vitcap_engine_tap(vitcap_engine* e, const char* name, void* workspace, int B, const vitcap_gen_opts* opts);
 
 /* ================================================================================================

@@ -652,7 +652,121 @@ __global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restri
   *x = v < 0.f ? v * penalty : v / penalty;
 }
 
+// ---- one-pass caption scoring (vitcap_score_rows, include/vitcap_hip.h) -------------------------------------------------------
+// Probe row g of the grid = caption g / (L-1), position t = g % (L-1) + 1.  One 1024-thread workgroup per row, the reductions of
+// greedy_step_kernel; every row decides on its own whether its caption has ended before it (its ids are all known), so a launch
+// may cover any range of rows.
+struct ScoreArgs {
+  const int64_t* ids;        // [n_caps][L] the captions
+  const int64_t* last_tok;   // [n_caps] or null
+  float* tok_lp;             // [n_caps][L]
+  int64_t* out_ids;          // [n_caps][L]
+  int64_t* out_last;         // [n_caps] or null
+  float *sum_lp, *cnt, *logprob;      // [n_caps] (sum_lp / cnt may be null)
+  int L, eos, pad;
+  VcEosExtra eos_x;
+};
+__global__ __launch_bounds__(1024) void score_rows_kernel(const float* __restrict__ logits, int ldl, int V, ScoreArgs a, int rows0) {
+  __shared__ float s_v[16], s_sum[16];
+  __shared__ int s_i[16];
+  const int tid = threadIdx.x, g = rows0 + blockIdx.x;
+  const int b = g / (a.L - 1), t = g - b * (a.L - 1) + 1;
+  const int64_t* cap = a.ids + (size_t)b * a.L;
+  bool ended = false;                      // an EOS id strictly before position t
+  for (int j = 1; j < t; ++j) ended = ended || vc_is_eos((int)cap[j], a.eos, a.eos_x);
+  const size_t o = (size_t)b * a.L + t;
+  if (ended) {                             // behind the end: nothing is counted (the stepwise loop's skip_finished)
+    if (tid == 0) {
+      a.tok_lp[o] = 0.f;
+      a.out_ids[o] = a.pad;
+      if (t == a.L - 1 && a.out_last) a.out_last[b] = a.pad;
+    }
+    return;
+  }
+  const float* row = logits + (size_t)blockIdx.x * ldl;
+  Pick<false, false> best;
+  for (int i = tid; i < V; i += 1024) best.offer(row[i], i);
+  best = block_pick<16>(best, {s_v, s_i, nullptr, nullptr});
+  float se = 0.f;
+  for (int i = tid; i < V; i += 1024) se += expf(row[i] - best.v);
+  const float tot = block_sum<16>(se, s_sum);
+  if (tid != 0) return;
+  const int64_t given = cap[t];
+  int f = given >= 0 && given < (int64_t)V ? (int)given : best.i;
+  const bool last = t == a.L - 1;
+  if (last && given == (int64_t)a.eos) {   // the max-length rule's [SEP], not a choice: the caller's token, or the row's argmax
+    const int64_t lt = a.last_tok ? a.last_tok[b] : -1;
+    f = lt >= 0 && lt < (int64_t)V ? (int)lt : best.i;
+  }
+  a.tok_lp[o] = (row[f] - best.v) - logf(tot);
+  int64_t outtok = f;
+  if (last) {
+    if (a.out_last) a.out_last[b] = f;
+    if (!vc_is_eos(f, a.eos, a.eos_x)) outtok = a.eos;      // modeling_utils.py:870-871
+  }
+  a.out_ids[o] = outtok;
+}
+// the captions whose last probe row lies in [rows0, rows0 + n_rows): their sums, taken in position order like the step loop's
+__global__ void score_finish_kernel(ScoreArgs a, int n_caps, int rows0, int n_rows) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_caps) return;
+  const long long lastrow = (long long)b * (a.L - 1) + (a.L - 2);
+  if (lastrow < rows0 || lastrow >= (long long)rows0 + n_rows) return;
+  const int64_t* cap = a.ids + (size_t)b * a.L;
+  float s = 0.f, c = 0.f;
+  for (int t = 1; t < a.L; ++t) {
+    s += a.tok_lp[(size_t)b * a.L + t];
+    c += 1.0f;
+    if (vc_is_eos((int)cap[t], a.eos, a.eos_x)) break;
+  }
+  a.tok_lp[(size_t)b * a.L] = 0.f;
+  a.out_ids[(size_t)b * a.L] = cap[0];
+  if (a.sum_lp) a.sum_lp[b] = s;
+  if (a.cnt) a.cnt[b] = c;
+  a.logprob[b] = StepState::mean_lp(s, c);
+}
+// the grid's token ids for vitcap_embed_rows: [n_caps][2L-1] = the caption's L tokens, then L-1 [MASK]
+__global__ void score_grid_ids_kernel(const int64_t* __restrict__ ids, int64_t* __restrict__ grid, int n_caps, int L, int mask, int pad,
+                                      int V) {
+  const int R = 2 * L - 1;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)n_caps * R) return;
+  const int b = (int)(i / R), r = (int)(i - (long long)b * R);
+  int64_t tok = mask;
+  if (r < L) {
+    tok = ids[(size_t)b * L + r];
+    if (tok < 0 || tok >= (int64_t)V) tok = pad;      // never an index outside the embedding table
+  }
+  grid[i] = tok;
+}
+
 }  // namespace
+
+int vc_score_grid_ids(const int64_t* ids, int64_t* grid, int n_caps, int L, int mask, int pad, void* stream) {
+  VC_REQUIRE(ids && grid && n_caps > 0 && L >= 2, "score_grid_ids: bad arguments");
+  const long long n = (long long)n_caps * (2 * L - 1);
+  hipLaunchKernelGGL(score_grid_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ids, grid, n_caps, L, mask,
+                     pad, VITCAP_VOCAB);
+  VC_LAUNCH_CHECK("score_grid_ids");
+  return VITCAP_OK;
+}
+
+extern "C" int vitcap_score_rows(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0,
+                                 int n_rows, int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, float* sum_lp,
+                                 float* cnt, float* token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* logprob_out,
+                                 void* stream) {
+  VC_REQUIRE(logits && caption_ids && token_logprobs && out_ids && logprob_out, "score_rows: null pointer");
+  VC_REQUIRE(V > 0 && ldl >= V && n_caps > 0 && max_len >= 2 && max_len <= 40, "score_rows: bad sizes (max_len=%d)", max_len);
+  VC_REQUIRE(rows0 >= 0 && n_rows > 0 && (long long)rows0 + n_rows <= (long long)n_caps * (max_len - 1),
+             "score_rows: rows [%d, %d + %d) outside the %d x %d probe rows", rows0, rows0, n_rows, n_caps, max_len - 1);
+  ScoreArgs a{caption_ids, last_tok, token_logprobs, out_ids, out_last_tok, sum_lp, cnt, logprob_out, max_len, eos, pad,
+              VcEosExtra{{eos_extra ? eos_extra[0] : -1, eos_extra ? eos_extra[1] : -1, eos_extra ? eos_extra[2] : -1}}};
+  hipLaunchKernelGGL(score_rows_kernel, dim3(n_rows), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V, a, rows0);
+  VC_LAUNCH_CHECK("score_rows");
+  hipLaunchKernelGGL(score_finish_kernel, dim3((n_caps + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, n_caps, rows0, n_rows);
+  VC_LAUNCH_CHECK("score_rows (sums)");
+  return VITCAP_OK;
+}
 
 extern "C" int vitcap_repetition_penalty(float* logits, int ldl, int V, const int64_t* ids, int ld_ids, int t, float penalty,
                                          int rows, void* stream) {

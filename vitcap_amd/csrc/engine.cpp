@@ -1021,6 +1021,134 @@ extern "C" int vitcap_engine_generate_forced(vitcap_engine* e, const void* image
   return tags_copy(lo, B, ws, tag_logits_out, tag_topk_out, s);
 }
 
+// ---- one-pass scoring of given captions (include/vitcap_hip.h: vitcap_engine_score) ---------------------------------------------
+// Every token of a scored caption is known, so the max_length - 1 sequential steps of the forced decode loop become ONE pass over a
+// [token rows | [MASK] probe rows] grid per caption: full-size GEMMs on captions x (2L - 1) rows, vitcap_attn_text_grid against
+// the image's visual K/V of the prefill, the LM head on the probe rows only (vocabulary GEMM in chunks of SCORE_CHUNK rows) and
+// vitcap_score_rows.  Rounding points as step_forward: fp32 residual stream, bf16 GEMM operands, bf16 qkv.
+namespace {
+
+// what the one-pass path does not run, refused by name before anything is enqueued
+int check_score(const vitcap_gen_opts& o, int caps_per_image) {
+#define SC_REQ(cond, ...) do { if (!(cond)) { vitcap_set_error(__VA_ARGS__); return VITCAP_EINVAL; } } while (0)
+  SC_REQ(o.num_beams <= 1, "engine_score: num_beams must be 1 (got %d): a caption is scored, not searched", o.num_beams);
+  SC_REQ(!o.use_cbs, "engine_score: use_cbs is not run by the one-pass scorer");
+  SC_REQ(o.tag_visible <= 0, "engine_score: tag_visible > 0 (got %d) is not built for the one-pass scorer", o.tag_visible);
+  SC_REQ(!o.sampling.do_sample, "engine_score: sampling.do_sample is not run by the one-pass scorer (nothing is drawn)");
+  SC_REQ(o.repetition_penalty == 1.0f, "engine_score: repetition_penalty must be 1 (got %g): the stepwise path scores the penalised row, "
+         "the one-pass path does not build it", (double)o.repetition_penalty);
+  SC_REQ(caps_per_image >= 1 && caps_per_image <= SCORE_MAX_CAPS, "engine_score: caps_per_image must be 1..%d (got %d)", SCORE_MAX_CAPS,
+         caps_per_image);
+#undef SC_REQ
+  return check_opts(o);
+}
+
+struct ScoreIO {
+  const int64_t* caption_ids;
+  const int64_t* last_tok;
+  float* out_logprobs;
+  float* out_tok_lp;
+  int64_t* out_ids;
+  int64_t* out_last_tok;
+};
+
+int check_score_io(const ScoreIO& io, const ScoreLayout& sl, const void* sws, size_t sws_bytes) {
+  if (!io.caption_ids || !io.out_logprobs || !io.out_ids) { vitcap_set_error("engine_score: null caption_ids / outputs"); return VITCAP_EINVAL; }
+  if (!sws || ((uintptr_t)sws & 255) != 0) { vitcap_set_error("engine_score: score workspace null or not 256-byte aligned"); return VITCAP_EINVAL; }
+  if (sws_bytes < sl.off) {
+    vitcap_set_error("engine_score: score workspace %zu < required %zu bytes", sws_bytes, sl.off);
+    return VITCAP_EWORKSPACE;
+  }
+  return VITCAP_OK;
+}
+
+// reads lo.dqkv[0..3] of `ws` (the visual caches of the prefill) and nothing else of it
+int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, const ScoreLayout& sl, char* sw,
+                 const ScoreIO& io, void* s) {
+  hipStream_t st = (hipStream_t)s;
+  const int L = sl.L, R = sl.R, K = sl.K;
+  const int NC = (int)sl.NC, M = (int)sl.M, P = (int)sl.P;
+  Enq q(e, B, o, lo, ws, s, Enq::ENCODE);
+  const vitcap_weights& w = e->w;
+  int64_t* ids = sl.ids.at<int64_t>(sw);
+  int64_t* last = sl.last_tok.at<int64_t>(sw);
+  HIPCK(hipMemcpyAsync(ids, io.caption_ids, (size_t)NC * L * 8, hipMemcpyDeviceToDevice, st), "engine_score: caption ids copy");
+  if (io.last_tok) HIPCK(hipMemcpyAsync(last, io.last_tok, (size_t)NC * 8, hipMemcpyDeviceToDevice, st), "engine_score: last_tok copy");
+  else HIPCK(hipMemsetAsync(last, 0xff, (size_t)NC * 8, st), "engine_score: last_tok clear");
+  float* x_f = sl.x_f.at<float>(sw);
+  char* x_b = sw + sl.x_b;
+  CK(vc_score_grid_ids(ids, sl.grid_ids.at<int64_t>(sw), NC, L, o.mask_token_id, o.pad_token_id, s));
+  CK(vitcap_embed_rows(sl.grid_ids.at<int64_t>(sw), R, w.word_emb, w.pos_emb, w.type_emb, w.emb_ln_g, w.emb_ln_b, 1e-12f, nullptr, x_f, x_b,
+                       M, L, s));
+  for (int l = 0; l < 4; ++l) {
+    const vitcap_bert_layer_w& lw = w.dec[l];
+    const char* vis = ws + lo.dqkv[l];
+    CK(q.gemm(x_b, D, lw.qkv_w, lw.qkv_b, nullptr, 0, sw + sl.qkv, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
+    CK(vitcap_attn_beam_vt(vis, sw + sl.vt, B, SV, s));
+    CK(vitcap_attn_text_grid(sw + sl.qkv, vis, sw + sl.vt, sw + sl.ctx, B, K, SV, L, 0.125f, s));
+    // BertSelfOutput / BertIntermediate / BertOutput: dense + residual, then LayerNorm (post-LN), as prefill_part
+    CK(q.gemm_ln(sw + sl.ctx, D, lw.ao_w, lw.ao_b, x_f, sw + sl.tmp, M, D, lw.ao_g, lw.ao_beta, 1e-12f, sw + sl.sa_b, sl.sa_f.at<float>(sw)));
+    CK(q.gemm(sw + sl.sa_b, D, lw.i_w, lw.i_b, nullptr, 0, sw + sl.mlp, 4 * D, M, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16));
+    CK(q.gemm_ln(sw + sl.mlp, 4 * D, lw.o_w, lw.o_b, sl.sa_f.at<float>(sw), sw + sl.tmp, M, 4 * D, lw.o_g, lw.o_beta, 1e-12f, x_b, x_f));
+  }
+  // LM head on the probe rows (rows L .. 2L-2 of every caption): transform (dense + GELU + LayerNorm), then the vocabulary GEMM in chunks
+  CK(vitcap_copy_row_blocks(x_b, R, L, D, 0, sw + sl.hd_in, L - 1, 0, D, 0, L - 1, D, NC, s));
+  CK(q.gemm(sw + sl.hd_in, D, w.cls.dense_w, w.cls.dense_b, nullptr, 0, sw + sl.hd_f, D, P, D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_F32));
+  CK(vitcap_layernorm_fwd(sl.hd_f.at<float>(sw), D, w.cls.ln_g, w.cls.ln_b, 1e-12f, sw + sl.hd_b, nullptr, P, D, s));
+  float* tok_lp = io.out_tok_lp ? io.out_tok_lp : sl.tok_lp.at<float>(sw);
+  for (int r0 = 0; r0 < P; r0 += (int)sl.CH) {
+    const int n = P - r0 < (int)sl.CH ? P - r0 : (int)sl.CH;
+    CK(q.gemm(sl.hd_b.at<char>(sw, (size_t)r0), D, w.cls.dec_w, w.cls.dec_b, nullptr, 0, sw + sl.logits, VP, n, VP, D, VITCAP_ACT_NONE,
+              VITCAP_OUT_F32));
+    CK(vitcap_score_rows(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
+                         nullptr, nullptr, tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, s));
+  }
+  return VITCAP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image, const vitcap_gen_opts* opts) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  if (B <= 0 || check_score(o, caps_per_image) != VITCAP_OK) return 0;
+  return ScoreLayout(B, caps_per_image, o.max_length).off;
+}
+
+extern "C" int vitcap_engine_score_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                        int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                                        size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                                        int64_t* out_last_tok, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  CK(check_score(o, caps_per_image));
+  if (B <= 0) { vitcap_set_error("engine_score: bad batch"); return VITCAP_EINVAL; }
+  const ScoreLayout sl(B, caps_per_image, o.max_length);
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  return score_locked(e, B, o, lo, (char*)workspace, sl, (char*)score_ws, io, s);
+}
+
+extern "C" int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                   void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                   const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                   float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  CK(check_score(o, caps_per_image));
+  if (B <= 0) { vitcap_set_error("engine_score: bad batch"); return VITCAP_EINVAL; }
+  const ScoreLayout sl(B, caps_per_image, o.max_length);
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  char* ws = (char*)workspace;
+  std::lock_guard<std::mutex> lk(e->mu);
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
+  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s);
+}
+
 extern "C" const void* vitcap_engine_tap(vitcap_engine* e, const char* name, void* workspace, int B, const vitcap_gen_opts* opts) {
   const vitcap_gen_opts o = opts_or_default(opts);
   if (!e || !name || !workspace || B <= 0 || check_opts(o) != VITCAP_OK) return nullptr;
@@ -1038,5 +1166,6 @@ extern "C" const void* vitcap_engine_tap(vitcap_engine* e, const char* name, voi
   if (!strcmp(name, "ids")) return ws + lo.ids;
   if (!strcmp(name, "live")) return ws + lo.live;
   if (!strcmp(name, "cbs_npred")) return lo.cbs ? ws + lo.cbs_npred : nullptr;
+  if (!strncmp(name, "dqkv", 4) && name[4] >= '0' && name[4] <= '3' && !name[5]) return ws + lo.dqkv[name[4] - '0'];
   return nullptr;
 }

@@ -51,3 +51,7 @@ struct vitcap_engine {
   size_t used = 0;
   std::vector<GraphEntry> graphs;     // captured decode loops (vitcap_gen_opts.use_graph)
 };
+
+// decode.hip: the token ids of the one-pass scorer's text grid, [n_caps][2L-1] = the caption's L tokens (an id outside the vocabulary
+// is embedded as `pad`), then L-1 [MASK].  Internal to the engine (vitcap_engine_score*).
+int vc_score_grid_ids(const int64_t* ids, int64_t* grid, int n_caps, int L, int mask, int pad, void* stream);

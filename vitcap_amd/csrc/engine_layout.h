@@ -192,4 +192,53 @@ struct Layout {
   size_t tcache_at(int l, size_t s0) const { return ((size_t)l * NS + s0) * L * 2 * D * 2; }
 };
 
+// ---- the score workspace of the one-pass caption scorer (vitcap_engine_score*) ---------------------------------------------------
+// A second caller-provided block, separate from the table above (whose rows and sizes it leaves alone).  Units: NC = B * K
+// captions, M = NC * (2L - 1) grid rows, P = NC * (L - 1) probe rows, CH = min(P, SCORE_CHUNK) rows of one vocabulary-GEMM chunk.
+// Sizes at L = 20: 64 images x 5 captions 0.66 GB, 64 x 32 captions 2.51 GB, of which the logits chunk is 0.25 GB (unchunked it
+// would be 4.7 GB at 64 x 32).
+constexpr int SCORE_CHUNK = 2048;      // probe rows per vocabulary GEMM: the large-tile forms are at full size from 2048 rows on
+constexpr int SCORE_MAX_CAPS = 32;     // captions per image
+
+#define VC_SCORE_BUFFERS(X)                                                                                                        \
+  X(ids, NC, L * 8)              /* the call's copy of the caller's captions */                                                    \
+  X(last_tok, NC, 8)             /* ... and of last_tok (-1 everywhere when none is given) */                                      \
+  X(grid_ids, M, 8)              /* [tokens | [MASK] x (L-1)] per caption, for vitcap_embed_rows */                                \
+  X(x_f, M, D * 4)               /* residual stream */                                                                             \
+  X(x_b, M, D * 2)                                                                                                                 \
+  X(qkv, M, 3 * D * 2)                                                                                                             \
+  X(ctx, M, D * 2)                                                                                                                 \
+  X(tmp, M, D * 4)               /* GEMM output in front of a LayerNorm */                                                         \
+  X(sa_f, M, D * 4)                                                                                                                \
+  X(sa_b, M, D * 2)                                                                                                                \
+  X(mlp, M, 4 * D * 2)                                                                                                             \
+  X(vt, B, VT_BYTES)             /* V^T of the current layer's visual rows (vitcap_attn_beam_vt), rewritten per layer */           \
+  X(hd_in, P, D * 2)             /* the probe rows of the last layer, compact */                                                   \
+  X(hd_f, P, D * 4)                                                                                                                \
+  X(hd_b, P, D * 2)                                                                                                                \
+  X(logits, CH, VP * 4)                                                                                                            \
+  X(tok_lp, NC, L * 4)           /* per-token log-probs when the caller wants none */
+
+struct ScoreLayout {
+#define VC_DECL(name, ...) Buf name;
+  VC_SCORE_BUFFERS(VC_DECL)
+#undef VC_DECL
+  size_t off = 0;
+  int B = 0, K = 0, L = 0, R = 0;
+  size_t NC = 0, M = 0, P = 0, CH = 0;
+
+  ScoreLayout() {}
+  ScoreLayout(int B_, int K_, int L_) : B(B_), K(K_), L(L_), R(2 * L_ - 1) {
+    NC = (size_t)B * K;
+    M = NC * R;
+    P = NC * (L - 1);
+    CH = P < (size_t)SCORE_CHUNK ? P : (size_t)SCORE_CHUNK;
+#define VC_PLACE(name, count, bytes)                                \
+  name = Buf{off, (size_t)(bytes), FIXED};                          \
+  off += ((size_t)(count) * (size_t)(bytes) + 255) & ~(size_t)255;
+    VC_SCORE_BUFFERS(VC_PLACE)
+#undef VC_PLACE
+  }
+};
+
 }  // namespace vc

@@ -18,7 +18,7 @@ from torch import nn
 
 from . import _lib as L
 from . import weights as W
-from ._lib import lib, check
+from ._lib import lib, check, VitcapError
 
 
 class _Node(nn.Module):
@@ -116,6 +116,8 @@ class ImageCaptioning(nn.Module):
         self._engine = None
         self._packed = None
         self._ws = {}
+        self._score_ws = {}      # slot -> the one-pass scorer's workspace (vitcap_engine_score)
+        self._encoded = {}       # slot -> (opts, B) of the call whose encoder pass + prefill the slot's workspace holds
         self.last_tags = None
 
     # ---------------------------------------------------------------- weights
@@ -399,6 +401,7 @@ class ImageCaptioning(nn.Module):
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         wp = C.c_void_p(ws.data_ptr())
         extra = (tok_lp,) if want_token_logprobs else ()
+        self._encoded[slot] = (opts, B)
         if want_last:
             last = torch.empty((rows,), dtype=torch.int64, device=dev)
             check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
@@ -458,22 +461,102 @@ class ImageCaptioning(nn.Module):
         forced, sf = self._prefix_forced(prefix_ids, image.shape[0], o.seqs_per_image, o.max_length)
         return self.run(image, o, slot=slot, want_last=want_last, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs)
 
-    def score(self, image, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+    def score(self, image, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, one_pass=False, **over):
         """Log-probability of GIVEN captions under the procedure generate() uses: one [MASK] probe per position on the tokens so
         far, log_softmax gathered at the given token, averaged over the positions up to and including the first [SEP]
         (modeling_utils.py:850-877 on given words).  caption_ids (B * seqs_per_image, L) image-major: [CLS] first,
         [SEP]-terminated, 0-padded -- what generate() returns.  The K captions of an image share its encoder pass and visual K/V.
         A [SEP] in the last column of a caption that has not ended before it was written by the max-length rule, not chosen: that
         position is scored on the loop's own choice, or on last_tok[row] when given (vitcap_amd.forced.pack_forced).
+        one_pass: every position in ONE pass over a [token rows | probe rows] grid (vitcap_engine_score) instead of max_length - 1
+        forced decode steps; up to 32 captions per image; agrees with the stepwise path within the bounds both meet against the
+        reference, not bit for bit.  Repetition penalty, visible tags, sampling, beams and CBS are not built for it.
         -> (logprob (rows,), token_logprobs (rows, L)); with return_ids also the ids the loop wrote."""
         from .forced import pack_forced
         K = int(seqs_per_image)
+        if one_pass:
+            o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
+            dev = self._check_image(image)
+            return self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, return_ids)
         o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
         o.seqs_per_image = K
         check(lib.vitcap_gen_opts_check(C.byref(o)), 'gen_opts')
         forced, sf = pack_forced(caption_ids=caption_ids, rows=image.shape[0] * K, max_length=o.max_length, last_tok=last_tok)
         ids, lp, tok_lp = self.run(image, o, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=True)
         return (lp.view(-1), tok_lp, ids) if return_ids else (lp.view(-1), tok_lp)
+
+    def _score_inputs(self, B, caption_ids, K, last_tok, over):
+        """Host-side checks of the one-pass scorer, before anything touches the GPU: the engine's refusals by option name
+        (NotImplementedError), then pack_forced's checks of the captions.  -> (opts, caption ids (rows, L), last_tok or None)."""
+        from .forced import pack_forced
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if int(te.get('num_beams', 1) or 1) > 1:
+            raise NotImplementedError('one_pass scoring needs num_beams == 1 (got %s): a caption is scored, not searched' % te['num_beams'])
+        if te.get('use_cbs', False):
+            raise NotImplementedError('one_pass scoring does not run use_cbs')
+        if float(te.get('repetition_penalty', 1) or 1) != 1.0:
+            raise NotImplementedError('one_pass scoring is not built for repetition_penalty != 1 (got %s): the stepwise path scores the '
+                                      'penalised row' % te['repetition_penalty'])
+        if int(te.get('tag_visible', 0) or 0) > 0:
+            raise NotImplementedError('one_pass scoring is not built for tag_visible > 0 (got %s)' % te['tag_visible'])
+        if te.get('do_sample', False):
+            raise NotImplementedError('one_pass scoring does not run do_sample: nothing is drawn')
+        if not 1 <= K <= 32:
+            raise NotImplementedError('one_pass scoring takes seqs_per_image 1..32 (got %d)' % K)
+        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
+            over.pop(k, None)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        rows = int(B) * K
+        pack_forced(caption_ids=caption_ids, rows=rows, max_length=o.max_length, last_tok=last_tok)      # the refusals only
+        cap = torch.as_tensor(caption_ids).to(torch.int64).reshape(rows, o.max_length)
+        lt = None if last_tok is None else torch.as_tensor(last_tok).to(torch.int64).reshape(rows)
+        return o, cap, lt
+
+    def _score_workspace(self, B, K, o, dev, slot):
+        """The score workspace of a slot, cached like _workspace."""
+        need = lib.vitcap_engine_score_workspace_bytes(B, K, C.byref(o))
+        if need == 0:
+            raise VitcapError('engine_score_workspace_bytes: %s' % lib.vitcap_last_error().decode())
+        sws = self._score_ws.get(slot)
+        if sws is None or sws.numel() < need or sws.device != dev:
+            sws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._score_ws[slot] = sws
+        return sws, need
+
+    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids):
+        """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill)."""
+        rows = B * K
+        cap = cap.to(dev).contiguous()
+        lt = None if lt is None else lt.to(dev).contiguous()
+        ws, need = self._workspace(B, dev, slot, o)
+        sws, sneed = self._score_workspace(B, K, o, dev, slot)
+        lp = torch.empty((rows,), dtype=torch.float32, device=dev)
+        tok_lp = torch.empty((rows, o.max_length), dtype=torch.float32, device=dev)
+        ids = torch.empty((rows, 1, o.max_length), dtype=torch.int64, device=dev)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        tail = (K, C.c_void_p(cap.data_ptr()), C.c_void_p(lt.data_ptr()) if lt is not None else None, C.c_void_p(sws.data_ptr()), sneed,
+                C.c_void_p(lp.data_ptr()), C.c_void_p(tok_lp.data_ptr()), C.c_void_p(ids.data_ptr()), None, s)
+        if image is not None:
+            check(lib.vitcap_engine_score(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
+                                          C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score')
+            self._encoded[slot] = (o, B)
+        else:
+            check(lib.vitcap_engine_score_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score_text')
+        return (lp, tok_lp, ids) if return_ids else (lp, tok_lp)
+
+    def score_encoded(self, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+        """score(one_pass=True) against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
+        (vitcap_engine_score_text reads the visual K/V that call left in the slot's workspace).  The options that size the
+        workspace (max_length) must be those of that call."""
+        if slot not in self._encoded:
+            raise RuntimeError('score_encoded: no encoded images on slot %r (call run / generate / score on it first)' % (slot,))
+        o_last, B = self._encoded[slot]
+        o, cap, lt = self._score_inputs(B, caption_ids, int(seqs_per_image), last_tok, over)
+        o.seqs_per_image = o_last.seqs_per_image      # the workspace of that call, as it was laid out
+        if o.max_length != o_last.max_length or o_last.tag_visible > 0 or o_last.num_beams > 1 or o_last.use_cbs:
+            raise ValueError('score_encoded: the last call on slot %r ran other options (max_length / tags / beams)' % (slot,))
+        return self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], return_ids)
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like

@@ -193,6 +193,40 @@ def attn_decode_beams(qkv_step, vis_qkv, text_kv, n_images, K, S_vis, t, max_len
     return out
 
 
+def attn_text_grid(qkv_text, vis_qkv, n_images, caps_per_image, S_vis=578, max_len=20, scale=0.125, out=None):
+    """Text-grid attention of the one-pass caption scorer (vitcap_attn_text_grid): qkv_text bf16 (n_images * caps_per_image *
+    (2 * max_len - 1), 2304) against the images' visual q|k|v rows; builds V^T first.  -> bf16 (rows, 768)."""
+    _dev_bf16(qkv_text)
+    _dev_bf16(vis_qkv)
+    vt = torch.empty((n_images, 12, 64, 608), device=qkv_text.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_beam_vt(_p(vis_qkv), _p(vt), n_images, min(S_vis, 608), _stream()), 'attn_beam_vt')
+    if out is None:
+        out = torch.empty((n_images * caps_per_image * (2 * max_len - 1), 768), device=qkv_text.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_text_grid(_p(qkv_text), _p(vis_qkv), _p(vt), _p(out), n_images, caps_per_image, S_vis, max_len, scale,
+                                    _stream()), 'attn_text_grid')
+    return out
+
+
+def score_rows(logits, caption_ids, st=None, rows0=0, last_tok=None, V=L.VOCAB, eos=102, eos_extra=(), pad=0):
+    """vitcap_score_rows on the probe rows [rows0, rows0 + len(logits)) of caption_ids (n_caps, max_len).  st: the dict of outputs a
+    previous chunk's call returned (token_logprobs, ids, last_tok, sum_lp, cnt, logprob); a new one is made when None."""
+    _dev_f32(logits)
+    n_caps, max_len = caption_ids.shape
+    dev = logits.device
+    if st is None:
+        st = dict(token_logprobs=torch.zeros((n_caps, max_len), device=dev, dtype=torch.float32),
+                  ids=torch.zeros((n_caps, max_len), device=dev, dtype=torch.int64),
+                  last_tok=torch.full((n_caps,), -1, device=dev, dtype=torch.int64),
+                  sum_lp=torch.zeros((n_caps,), device=dev, dtype=torch.float32),
+                  cnt=torch.zeros((n_caps,), device=dev, dtype=torch.float32),
+                  logprob=torch.zeros((n_caps,), device=dev, dtype=torch.float32))
+    ex = [int(x) for x in eos_extra] + [-1] * 3
+    check(lib.vitcap_score_rows(_p(logits), logits.stride(0), V, _p(caption_ids), _p(last_tok), rows0, logits.shape[0], n_caps, max_len,
+                                eos, (C.c_int32 * 3)(*ex[:3]), pad, _p(st['sum_lp']), _p(st['cnt']), _p(st['token_logprobs']),
+                                _p(st['ids']), _p(st['last_tok']), _p(st['logprob']), _stream()), 'score_rows')
+    return st
+
+
 def embed_step(ids, t, word, pos, typ, gamma, beta, eps=1e-12, mask_token=103):
     B, max_len = ids.shape
     xf = torch.empty((2 * B, 768), device=ids.device, dtype=torch.float32)
