@@ -243,8 +243,6 @@ NO_DIRECT_GPU_TEST = {
     'vitcap_image_train_preproc_workspace_bytes': _IMAGEIO, 'vitcap_jpeg_backhalf_workspace_bytes': _IMAGEIO,
     'vitcap_resample_coeffs': 'host only (no GPU): test_image_transform_cpu.py',
     'vitcap_resized_geometry': 'host only (no GPU): test_image_transform_cpu.py',
-    'vitcap_attn_dense_fwd_train': 'one-line forwarder to vitcap_attn_dense_fwd_train_rows with the whole range [0, S), which ops.attn_dense_train calls',
-    'vitcap_attn_dense_bwd': 'one-line forwarder to vitcap_attn_dense_bwd_rows with the whole range [0, S), which ops.attn_dense_bwd calls',
 }
 
 

@@ -515,6 +515,8 @@ extern "C" int vitcap_attn_dense_bwd_rows(const void* qkv, const void* out, cons
              (double)p_drop, ld_rows);
   VC_REQUIRE(causal_from == 0 || (causal_from >= (S / KT) * KT && causal_from <= S),
              "attn_dense_bwd: causal_from %d must lie in the last key tile of S=%d", causal_from, S);
+  VC_REQUIRE(mask_from == 0 || (causal_from > 0 && mask_from > causal_from && mask_from <= S),
+             "attn_dense_bwd: mask_from %d must lie in (causal_from %d, S %d]", mask_from, causal_from, S);
   VC_REQUIRE(q_lo >= 0 && q_lo < q_hi && q_hi <= S && (q_lo & 127) == 0,
              "attn_dense_bwd: query range [%d, %d) must start on a multiple of 128 inside S=%d", q_lo, q_hi, S);
   const float c = scale * 1.4426950408889634f;
