@@ -504,6 +504,30 @@ int vitcap_attn_decode_beam_groups(const void* qkv_step, const void* vis_qkv, co
  * (VITCAP_EINVAL) with `out` untouched. */
 int vitcap_attn_text_grid(const void* qkv_text, const void* vis_qkv, const void* vis_vt, void* out, int n_images, int caps_per_image,
                           int S_vis, int max_len, float scale, void* stream);
+/* Attention maps of given captions: the normalised softmax rows of the [MASK] probes of ONE decoder layer, written out
+ * (csrc/attn_maps.hip; the reference's attention_probs[b, h, cur_len, :] at step cur_len = t, modeling_bert.py:320-342, collected
+ * by BertEncoder under config.output_attentions, 484-510; mask 846-876).  qkv_text / vis_qkv as vitcap_attn_text_grid takes them;
+ * caption_ids device int64 [n_images * caps_per_image][max_len]; eos / eos_extra (host, 3 ids, -1 = unused, or NULL) as
+ * vitcap_score_rows takes them.
+ *   row      caption c (image-major), position t = 1..L-1 (L = max_len): the probe at grid row L + t - 1, which attends the image's
+ *            S_vis visual rows, token rows 0..t-1 and itself.  Width W = S_vis + L: columns 0..577 the visual keys in the cache's
+ *            order (0 = tag_hidden[:, 0], 1 = the encoder's cls row, 2..577 the 24 x 24 patches row-major), column 578 + k (k < t)
+ *            token key k, column 578 + t the probe's own key, every column behind it exactly 0.
+ *   softmax  scores from the same bf16 q / k and MFMA order as vitcap_attn_text_grid, log2 domain, m = ceil(max * c),
+ *            p = exp2(s * c - m) NOT rounded to bf16; the row is p / sum(p) in fp32.
+ *   zeros    position 0, and every position behind the caption's first end token (an EOS id at a position 1..t-1), hold no
+ *            decision: all zeros, like token_logprobs.
+ *   out      fp32, this layer's slice of the full array of all four decoder layers, whose strides the call derives:
+ *            per_head = 0: head mean [n_caps][L][4][W], out = base + layer * W, row (c, t) at out + (c * L + t) * 4 * W; the 12 heads
+ *                          are added in the order 0..11 by one lane and multiplied by 1/12 -- no atomics, the same bits on every run;
+ *            per_head = 1: [n_caps][L][4][12][W], out = base + layer * 12 * W, row (c, t, h) at out + (c * L + t) * 48 * W + h * W.
+ *            Only this layer's slice is written (every position 0..L-1 of it); the other layers' slices are left untouched.
+ * One workgroup per (16-probe query tile, caption), the 12 heads in a loop.  S_vis == 578, 2 <= max_len <= 40,
+ * 1 <= caps_per_image <= 32, n_images * caps_per_image <= 65535, per_head 0 or 1, pointers non-null and aligned (qkv 16 bytes);
+ * anything else is refused (VITCAP_EINVAL, the argument named) with `out` untouched. */
+int vitcap_attn_probe_maps(const void* qkv_text, const void* vis_qkv, const int64_t* caption_ids, float* out, int n_images,
+                           int caps_per_image, int S_vis, int max_len, int per_head, int eos, const int32_t* eos_extra, float scale,
+                           void* stream);
 
 /* small data movers used by the engine and exposed for tests */
 int vitcap_assemble_visual(const float* hidden, const float* tag_hidden, float* vis_f32, void* vis_bf16,
@@ -703,6 +727,24 @@ int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, 
                         size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
                         size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
                         void* stream);
+/* "Where did the model look for this word": the one-pass scoring pass, which also writes the attention maps of the captions' [MASK]
+ * probes (vitcap_attn_probe_maps after the qkv GEMM of every selected decoder layer; the reference's attention_probs,
+ * modeling_bert.py:320-342, 484-510, mask 846-876).  Arguments, refusals and results as vitcap_engine_score_text /
+ * vitcap_engine_score -- the scores are returned too and are bit-identical to those calls' -- plus
+ *   maps        device fp32, per_head = 0: [B*caps][max_length][4][W] (head mean), per_head = 1: [B*caps][max_length][4][12][W],
+ *               W = 578 + max_length; rows, columns and zeros as vitcap_attn_probe_maps defines them
+ *   per_head    0 or 1
+ *   layer_mask  bit l selects decoder layer l (1..15).  The slices of unselected layers are left untouched.
+ * A null `maps`, a layer_mask outside 1..15 or a per_head other than 0 / 1 is VITCAP_EINVAL.  The score workspace is that of
+ * vitcap_engine_score_workspace_bytes: the maps go straight to the caller's array. */
+int vitcap_engine_explain_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                               int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                               size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                               int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* stream);
+int vitcap_engine_explain(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts, void* workspace,
+                          size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok,
+                          void* score_ws, size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                          int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* stream);
 /* copies the tag head's outputs of the last encode on this workspace (either pointer may be NULL) */
 int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                        int64_t* tag_topk_out, void* stream);

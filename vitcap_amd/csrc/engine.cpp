@@ -1062,9 +1062,27 @@ int check_score_io(const ScoreIO& io, const ScoreLayout& sl, const void* sws, si
   return VITCAP_OK;
 }
 
+// Attention maps of the probes (vitcap_engine_explain*): off for the scoring entry points, the way Forced is for decode_locked.
+struct Maps {
+  float* out = nullptr;      // the caller's [NC][L][4]([12])[W] array
+  int per_head = 0;
+  int layer_mask = 0;        // bit l: decoder layer l
+  bool on() const { return out != nullptr; }
+};
+
+int check_maps(const Maps& m) {
+  if (!m.out) { vitcap_set_error("engine_explain: maps is null"); return VITCAP_EINVAL; }
+  if (m.per_head != 0 && m.per_head != 1) { vitcap_set_error("engine_explain: per_head must be 0 or 1 (got %d)", m.per_head); return VITCAP_EINVAL; }
+  if (m.layer_mask < 1 || m.layer_mask > 15) {
+    vitcap_set_error("engine_explain: layer_mask must select at least one of the 4 decoder layers (1..15, got %d)", m.layer_mask);
+    return VITCAP_EINVAL;
+  }
+  return VITCAP_OK;
+}
+
 // reads lo.dqkv[0..3] of `ws` (the visual caches of the prefill) and nothing else of it
 int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, const ScoreLayout& sl, char* sw,
-                 const ScoreIO& io, void* s) {
+                 const ScoreIO& io, void* s, const Maps& mp = Maps()) {
   hipStream_t st = (hipStream_t)s;
   const int L = sl.L, R = sl.R, K = sl.K;
   const int NC = (int)sl.NC, M = (int)sl.M, P = (int)sl.P;
@@ -1084,6 +1102,9 @@ int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout
     const vitcap_bert_layer_w& lw = w.dec[l];
     const char* vis = ws + lo.dqkv[l];
     CK(q.gemm(x_b, D, lw.qkv_w, lw.qkv_b, nullptr, 0, sw + sl.qkv, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
+    if (mp.on() && ((mp.layer_mask >> l) & 1))      // the caller's array, this layer's slice; reads qkv and the ids only
+      CK(vitcap_attn_probe_maps(sw + sl.qkv, vis, ids, mp.out + (size_t)l * (mp.per_head ? 12 : 1) * (SV + L), B, K, SV, L, mp.per_head,
+                                o.eos_token_id, o.eos_extra, 0.125f, s));
     CK(vitcap_attn_beam_vt(vis, sw + sl.vt, B, SV, s));
     CK(vitcap_attn_text_grid(sw + sl.qkv, vis, sw + sl.vt, sw + sl.ctx, B, K, SV, L, 0.125f, s));
     // BertSelfOutput / BertIntermediate / BertOutput: dense + residual, then LayerNorm (post-LN), as prefill_part
@@ -1114,39 +1135,72 @@ extern "C" size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image,
   return ScoreLayout(B, caps_per_image, o.max_length).off;
 }
 
+namespace {
+
+// The four entry points of the one-pass pass: every refusal in one order -- options, batch, maps (when asked for), io, workspace --
+// then, with an image, encode + prefill, then score_locked.  mp: the maps description of the explain pair, null for the scoring pair.
+int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool encode, int B, const vitcap_gen_opts* opts, void* workspace,
+                size_t workspace_bytes, int caps_per_image, const ScoreIO& io, void* score_ws, size_t score_ws_bytes, const Maps* mp,
+                void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  CK(check_score(o, caps_per_image));
+  if (B <= 0) { vitcap_set_error("%s: bad batch", mp ? "engine_explain" : "engine_score"); return VITCAP_EINVAL; }
+  if (mp) CK(check_maps(*mp));
+  const ScoreLayout sl(B, caps_per_image, o.max_length);
+  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  char* ws = (char*)workspace;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (encode) {
+    CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
+    CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
+  }
+  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps());
+}
+
+Maps maps_of(float* maps, int per_head, int layer_mask) {
+  Maps mp;
+  mp.out = maps; mp.per_head = per_head; mp.layer_mask = layer_mask;
+  return mp;
+}
+
+}  // namespace
+
 extern "C" int vitcap_engine_score_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                                         int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
                                         size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
                                         int64_t* out_last_tok, void* s) {
-  const vitcap_gen_opts o = opts_or_default(opts);
-  CK(check_score(o, caps_per_image));
-  if (B <= 0) { vitcap_set_error("engine_score: bad batch"); return VITCAP_EINVAL; }
-  const ScoreLayout sl(B, caps_per_image, o.max_length);
   const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
-  Layout lo;
-  CK(enter(e, B, o, workspace, workspace_bytes, lo));
-  std::lock_guard<std::mutex> lk(e->mu);
-  return score_locked(e, B, o, lo, (char*)workspace, sl, (char*)score_ws, io, s);
+  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s);
 }
 
 extern "C" int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
                                    void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
                                    const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
                                    float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, void* s) {
-  const vitcap_gen_opts o = opts_or_default(opts);
-  CK(check_score(o, caps_per_image));
-  if (B <= 0) { vitcap_set_error("engine_score: bad batch"); return VITCAP_EINVAL; }
-  const ScoreLayout sl(B, caps_per_image, o.max_length);
   const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
-  Layout lo;
-  CK(enter(e, B, o, workspace, workspace_bytes, lo));
-  char* ws = (char*)workspace;
-  std::lock_guard<std::mutex> lk(e->mu);
-  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
-  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
-  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s);
+  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
+                     nullptr, s);
+}
+
+extern "C" int vitcap_engine_explain_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                          int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                                          size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                                          int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  const Maps mp = maps_of(maps, per_head, layer_mask);
+  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, &mp, s);
+}
+
+extern "C" int vitcap_engine_explain(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                     void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                     const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                     float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* maps, int per_head,
+                                     int layer_mask, void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  const Maps mp = maps_of(maps, per_head, layer_mask);
+  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, &mp, s);
 }
 
 extern "C" const void* vitcap_engine_tap(vitcap_engine* e, const char* name, void* workspace, int B, const vitcap_gen_opts* opts) {

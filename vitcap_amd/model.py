@@ -524,8 +524,9 @@ class ImageCaptioning(nn.Module):
             self._score_ws[slot] = sws
         return sws, need
 
-    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids):
-        """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill)."""
+    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None):
+        """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill).
+        maps = (per_head, layer_mask): vitcap_engine_explain / vitcap_engine_explain_text instead, -> (lp, tok_lp, ids, maps)."""
         rows = B * K
         cap = cap.to(dev).contiguous()
         lt = None if lt is None else lt.to(dev).contiguous()
@@ -537,6 +538,19 @@ class ImageCaptioning(nn.Module):
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         tail = (K, C.c_void_p(cap.data_ptr()), C.c_void_p(lt.data_ptr()) if lt is not None else None, C.c_void_p(sws.data_ptr()), sneed,
                 C.c_void_p(lp.data_ptr()), C.c_void_p(tok_lp.data_ptr()), C.c_void_p(ids.data_ptr()), None, s)
+        if maps is not None:
+            per_head, layer_mask = maps
+            W = 578 + o.max_length
+            out = torch.zeros((rows, o.max_length, 4) + ((12, W) if per_head else (W,)), dtype=torch.float32, device=dev)
+            tail = tail[:-1] + (C.c_void_p(out.data_ptr()), int(per_head), int(layer_mask), s)
+            if image is not None:
+                check(lib.vitcap_engine_explain(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                                C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_explain')
+                self._encoded[slot] = (o, B)
+            else:
+                check(lib.vitcap_engine_explain_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
+                      'engine_explain_text')
+            return lp, tok_lp, ids, out
         if image is not None:
             check(lib.vitcap_engine_score(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
                                           C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score')
@@ -549,14 +563,73 @@ class ImageCaptioning(nn.Module):
         """score(one_pass=True) against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
         (vitcap_engine_score_text reads the visual K/V that call left in the slot's workspace).  The options that size the
         workspace (max_length) must be those of that call."""
+        B, o, cap, lt = self._encoded_inputs('score_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
+        return self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], return_ids)
+
+    def _encoded_inputs(self, who, slot, caption_ids, K, last_tok, over):
+        """The checks of the calls that run against a slot's already encoded images (score_encoded, attention_maps_encoded):
+        -> (B, opts laid out as that call's, caption ids, last_tok or None)."""
         if slot not in self._encoded:
-            raise RuntimeError('score_encoded: no encoded images on slot %r (call run / generate / score on it first)' % (slot,))
+            raise RuntimeError('%s: no encoded images on slot %r (call run / generate / score on it first)' % (who, slot))
         o_last, B = self._encoded[slot]
-        o, cap, lt = self._score_inputs(B, caption_ids, int(seqs_per_image), last_tok, over)
+        o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
         o.seqs_per_image = o_last.seqs_per_image      # the workspace of that call, as it was laid out
         if o.max_length != o_last.max_length or o_last.tag_visible > 0 or o_last.num_beams > 1 or o_last.use_cbs:
-            raise ValueError('score_encoded: the last call on slot %r ran other options (max_length / tags / beams)' % (slot,))
-        return self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], return_ids)
+            raise ValueError('%s: the last call on slot %r ran other options (max_length / tags / beams)' % (who, slot))
+        return B, o, cap, lt
+
+    @staticmethod
+    def _layer_mask(layers):
+        """(0, 1, 2, 3)-style selection of decoder layers -> the engine's bit mask."""
+        ls = [int(l) for l in layers]
+        if not ls or any(l < 0 or l > 3 for l in ls):
+            raise ValueError('attention maps: layers must name at least one of the decoder layers 0..3 (got %r)' % (layers,))
+        mask = 0
+        for l in ls:
+            mask |= 1 << l
+        return mask
+
+    def attention_maps(self, image, caption_ids, seqs_per_image=1, per_head=False, layers=(0, 1, 2, 3), slot=0, last_tok=None, **over):
+        """Where the model looked for each word of GIVEN captions: the softmax row of the [MASK] probe at every position t >= 1, in
+        every selected decoder layer -- the reference's attention_probs[b, h, cur_len = t] (modeling_bert.py:320-342, 484-510) --
+        from the one-pass scoring pass (vitcap_engine_explain).  Inputs and refusals as score(one_pass=True).
+        -> (logprobs (rows,), token_logprobs (rows, L), maps): maps fp32 (rows, L, 4, W), the mean over the 12 heads, or with
+        per_head (rows, L, 4, 12, W); W = 578 + L, columns as vitcap_amd.attnmaps names them (0 tag cls, 1 encoder cls, 2..577 the
+        24 x 24 patches, 578 + k token k, 578 + t the probe itself).  Position 0 and the positions behind a caption's first [SEP]
+        are zeros; so are the layers not in `layers` (the engine leaves their slices untouched, the array starts zeroed)."""
+        K = int(seqs_per_image)
+        mask = self._layer_mask(layers)
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
+        dev = self._check_image(image)
+        lp, tok_lp, _, maps = self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, False, maps=(bool(per_head), mask))
+        return lp, tok_lp, maps
+
+    def attention_maps_encoded(self, caption_ids, seqs_per_image=1, per_head=False, layers=(0, 1, 2, 3), slot=0, last_tok=None, **over):
+        """attention_maps() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
+        (vitcap_engine_explain_text); the conditions of score_encoded()."""
+        mask = self._layer_mask(layers)
+        B, o, cap, lt = self._encoded_inputs('attention_maps_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
+        lp, tok_lp, _, maps = self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], False,
+                                                   maps=(bool(per_head), mask))
+        return lp, tok_lp, maps
+
+    def caption_with_maps(self, image, per_head=False, layers=(0, 1, 2, 3), slot=0, **over):
+        """Greedy captions and where the model looked for each of their words: generate() through the staged path, then
+        attention_maps_encoded() on its own output (the token chosen at the last position handed over as last_tok).
+        -> (ids (B, 1, L), logprobs (B, 1), maps)."""
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
+            raise NotImplementedError('caption_with_maps runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): attention '
+                                      'maps under beam search, CBS or sampling are not built'
+                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
+        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
+            over.pop(k, None)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        _, _, maps = self.attention_maps_encoded(ids.view(image.shape[0], o.max_length), 1, per_head=per_head, layers=layers, slot=slot,
+                                                 last_tok=last, **over)
+        return ids, lp, maps
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like

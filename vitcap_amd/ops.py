@@ -207,6 +207,27 @@ def attn_text_grid(qkv_text, vis_qkv, n_images, caps_per_image, S_vis=578, max_l
     return out
 
 
+def attn_probe_maps(qkv_text, vis_qkv, caption_ids, n_images, caps_per_image, S_vis=578, max_len=20, per_head=False, layer=0, out=None,
+                    eos=102, eos_extra=(), scale=0.125):
+    """Attention maps of the [MASK] probes of given captions, one decoder layer (vitcap_attn_probe_maps): qkv_text / vis_qkv as
+    attn_text_grid takes them, caption_ids int64 (n_caps, max_len).  Writes slice `layer` of `out`, fp32 (n_caps, max_len, 4, W) or,
+    per_head, (n_caps, max_len, 4, 12, W) with W = S_vis + max_len (a zeroed array is made when None); the other slices are left
+    untouched.  -> out."""
+    _dev_bf16(qkv_text)
+    _dev_bf16(vis_qkv)
+    n_caps, W = n_images * caps_per_image, S_vis + max_len
+    shape = (n_caps, max_len, 4, 12, W) if per_head else (n_caps, max_len, 4, W)
+    if out is None:
+        out = torch.zeros(shape, device=qkv_text.device, dtype=torch.float32)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape and 0 <= layer < 4
+    assert caption_ids.is_cuda and caption_ids.is_contiguous() and caption_ids.dtype == torch.int64
+    assert tuple(caption_ids.shape) == (n_caps, max_len)
+    ex = [int(x) for x in eos_extra] + [-1] * 3
+    check(lib.vitcap_attn_probe_maps(_p(qkv_text), _p(vis_qkv), _p(caption_ids), _p(out[:, :, layer]), n_images, caps_per_image, S_vis,
+                                     max_len, int(bool(per_head)), eos, (C.c_int32 * 3)(*ex[:3]), scale, _stream()), 'attn_probe_maps')
+    return out
+
+
 def score_rows(logits, caption_ids, st=None, rows0=0, last_tok=None, V=L.VOCAB, eos=102, eos_extra=(), pad=0):
     """vitcap_score_rows on the probe rows [rows0, rows0 + len(logits)) of caption_ids (n_caps, max_len).  st: the dict of outputs a
     previous chunk's call returned (token_logprobs, ids, last_tok, sum_lp, cnt, logprob); a new one is made when None."""

@@ -218,6 +218,35 @@ class _PredictRun(object):
             for entry in self.pending:
                 yield from self.collect(entry)
 
+    def attention_rows(self, batches, dev, pred_rows):
+        """cfg.attention_maps: the batches strictly one after the other through ImageCaptioning.caption_with_maps (no two-slot
+        overlap; throughput is not a target of this mode), with the GEMM form of the ordinary predict loop (gemm_mode = TILES) so
+        that the captions and their confidences are that loop's, bit for bit.  Yields the rows of the attention TSV, one per image
+        (about 30 KB each: they are streamed to their file); the (key, json) rows caption_rows would give (about 100 B each) are
+        appended to `pred_rows`."""
+        import base64
+        import numpy as np
+        from .attnmaps import patch_grid
+        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        vocab = self.pipe.tokenizer.ids_to_tokens
+        eos = set(int(e) for e in (model.test_extra_input.get('eos_token_ids') or [102]))
+        with torch.no_grad():
+            for batch in batches:
+                batch = dict(batch)
+                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
+                if model.check_text_inputs(batch, L) != 0:
+                    raise NotImplementedError('attention_maps: visible tag slots (tag_visible > 0) are not built for the attention maps')
+                ids, lp, maps = model.caption_with_maps(batch['image'], layers=(3,), gemm_mode=1)
+                ids_h, grids = ids.cpu(), patch_grid(maps[:, :, 3]).to(torch.float16).cpu().numpy()      # (B, L, 24, 24)
+                for b, key in enumerate(batch['key']):
+                    toks = ids_h[b, 0].tolist()
+                    ends = [t for t in range(1, L) if toks[t] in eos]
+                    n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
+                    data = np.ascontiguousarray(grids[b, 1:n + 1])
+                    yield key, json.dumps({'tokens': [vocab[i] for i in toks[1:n + 1]], 'layer': 3, 'shape': [n, 24, 24],
+                                           'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
+                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+
     def counted(self, rows):
         """images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
         workers running) to the last row -- the figure the reference's trainer logs as images/sec (trainer.py:155-170)."""
@@ -600,11 +629,29 @@ class CaptionUniPipeline(object):
         depth = int(self.cfg.loader_prefetch or os.environ.get('VITCAP_LOADER_PREFETCH', 0)) or max(2, min(24, 1536 // max(1, int(self.cfg.test_batch_size))))
         LOADER_TIMES.clear()
         batches = prefetched(self.iter_test_batches(), dev, depth=depth)
+        if self.cfg.attention_maps:
+            # a second TSV next to the predictions, one row per image: the last decoder layer's head-mean patch maps of the live positions
+            attn_file = self.get_attention_file(predict_result_file)
+            attn_sub = attn_file if self.world == 1 else '{}_{}_{}.tsv'.format(attn_file, self.rank, self.world)
+            pred_rows = []           # the small rows are held; the attention rows go to their file as they come
+            tsv_writer(run.counted(run.attention_rows(batches, dev, pred_rows)), attn_sub)
+            tsv_writer(iter(pred_rows), sub)
+            run.report()
+            if self.world > 1:
+                self.merge_rank_files(predict_result_file)
+                self.merge_rank_files(attn_file)
+            return predict_result_file
         tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)               # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
         run.report()
         if self.world > 1:
             self.merge_rank_files(predict_result_file)
         return predict_result_file
+
+    @staticmethod
+    def get_attention_file(predict_result_file):
+        """<predict file minus .tsv>.attn.tsv: written by predict when the config sets `attention_maps`."""
+        assert predict_result_file.endswith('.tsv')
+        return predict_result_file[:-len('.tsv')] + '.attn.tsv'
 
     def merge_rank_files(self, predict_result_file):
         """Rank 0 concatenates the ranks' files and de-duplicates by key (uni_pipeline.py:816-831); every rank waits for it."""
@@ -624,6 +671,12 @@ class CaptionUniPipeline(object):
 
     def ensure_predict(self, model_file=None):
         check_model_config(self.cfg, training=False)
+        if self.cfg.attention_maps and (self.cfg.num_beams not in (None, 1) or self.cfg.use_cbs):
+            raise NotImplementedError('attention_maps: the maps are those of greedy captions; beam search (num_beams=%r) and CBS '
+                                      '(use_cbs=%r) are not built for them' % (self.cfg.num_beams, self.cfg.use_cbs))
+        if self.cfg.attention_maps and self.cfg.caption_prefix:
+            raise NotImplementedError('attention_maps: caption_prefix=%r is not built together with the attention maps (the maps are '
+                                      'those of free greedy captions)' % (self.cfg.caption_prefix,))
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -634,7 +687,10 @@ class CaptionUniPipeline(object):
         if not op.isfile(model_file) and self.cfg.init_recipe_seed is None:
             logging.info('ignore to run predict since %s does not exist', model_file)
             return predict_result_file
-        if op.isfile(predict_result_file) and not self.cfg.force_predict:
+        have = op.isfile(predict_result_file)
+        if have and self.cfg.attention_maps and not op.isfile(self.get_attention_file(predict_result_file)):
+            have = False             # predictions from a run without the key: both files are written again
+        if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
             return predict_result_file
         return self.predict(model_file, predict_result_file)
