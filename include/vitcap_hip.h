@@ -129,8 +129,44 @@ int vitcap_gemm_tile_plan(int M, int N, int K, int* plan3);
  * -1 = the 8-wave 256x256 kernel (gemm.hip); otherwise form + 10 * MI of the 4-wave kernel (gemm4w.hip): form 1 = one tile per
  * workgroup, 2 = persistent pipeline; MI = 8 / 7 / 6 -> 256- / 224- / 192-row tiles.  Results do not depend on the choice.
  * tile_hint | 0x100 asks about a bf16-output GEMM without residual (qkv, fc1): under tile_hint 5 those run the 4-wave one-tile form,
- * the fp32 + residual GEMMs the 8-wave kernel. */
+ * the fp32 + residual GEMMs the 8-wave kernel.
+ * This is the LARGE-TILE family's choice only: under tile_hint 0 a launch reaches that family only when the auto cost model does not
+ * prefer 64x64 or 128x128 tiles (it does for narrow N or few rows), and the answer assumes a bf16 output with ldc == N.
+ * vitcap_gemm_plan reports what a given descriptor really launches. */
 int vitcap_gemm_large_form(int M, int N, int K, int tile_hint);
+
+/* The launch vitcap_gemm_ex would make for descriptor `d` with the given optional operands present (host-side query: no launch, no
+ * pointer is read).  Returns what vitcap_gemm_ex would return for that descriptor with well-aligned operands -- the same code and
+ * the same error text -- and on VITCAP_OK fills *out: the kernel family, that family's template arguments (the others are 0), the
+ * values patched into the kernel's argument block, the grid, the block size and the dynamic LDS size.  It reads what the launcher
+ * reads at launch time: vitcap_gemm_reserve_cus, the device's CU count, VITCAP_GEMM_4W_DEFER. */
+#define VITCAP_GEMM_FAMILY_RING 0          /* gemm_nt_kernel, LDS-staged ring: wm x wn waves of 32 x 32, `stages` ring slots */
+#define VITCAP_GEMM_FAMILY_RESIDENT 1      /* the same kernel with the whole 768-long k range resident (12 stages) */
+#define VITCAP_GEMM_FAMILY_ROWSTAT 2       /* the same kernel with the row-statistics epilogue */
+#define VITCAP_GEMM_FAMILY_SKINNY 3        /* register-fed skinny kernel (wm = waves along M; split-K partial slabs) */
+#define VITCAP_GEMM_FAMILY_8WAVE 4         /* 8-wave 256x256 kernel: ph = its phase / build bits, mts = height class of the short tiles */
+#define VITCAP_GEMM_FAMILY_4WAVE_TILE 5    /* 4-wave kernel, one tile per workgroup: form 0 = LDS epilogue, 1 = register epilogue */
+#define VITCAP_GEMM_FAMILY_4WAVE_PERSISTENT 6  /* 4-wave persistent pipeline (form 2): variant = VITCAP_GEMM_4W_* */
+#define VITCAP_GEMM_4W_PLAIN 0
+#define VITCAP_GEMM_4W_EXTRAS 1            /* training extras (aux / zout / colsum) in the register epilogue */
+#define VITCAP_GEMM_4W_DEFER 2             /* upper half of every wave tile's stores deferred behind the next tile */
+#define VITCAP_GEMM_4W_PREFETCH 3          /* A-panel prefetch one tile ahead */
+typedef struct {
+  int family;                   /* VITCAP_GEMM_FAMILY_* */
+  int wm, wn, stages;           /* ring / resident / rowstat (skinny: wm only) */
+  int act, out_f32, has_res;    /* the kernel's epilogue build (slab-writing launches: none / fp32) */
+  int partial;                  /* skinny: raw fp32 partial slabs */
+  int ph, mts;                  /* 8-wave */
+  int form, mi, variant;        /* 4-wave: mi = 16-row m-tiles per wave (8 / 7 / 6 -> 256- / 224- / 192-row tiles) */
+  int ln_fused, ln_follows;     /* LayerNorm inside the kernel / a LayerNorm launch follows the GEMM */
+  int split_k, kt_per_split;
+  long long slab;               /* elements between partial slabs */
+  int tiles_m, tiles_n, n_big, tiles_m_small, group_n;
+  int grid[3], block, lds_bytes;
+} vitcap_gemm_plan_info;
+int vitcap_gemm_plan(const vitcap_gemm_desc* d, int has_bias, int has_residual, int has_aux, int ldaux, int has_zout, int ldz,
+                     vitcap_gemm_plan_info* out);
+
 /* CUs the persistent large-GEMM grids (one 512-register workgroup per CU) leave free from now on, for launches of this process
  * (0 = none; rounded up to a multiple of 8 so that every XCD keeps the same number of workgroups; at most the device's CUs - 8).
  * Returns the previous value.  Why it exists: a collective's kernel (RCCL over xGMI, the data-parallel gradient exchange of

@@ -217,10 +217,18 @@ def _run(lib, P, hint=0, f32=True, act=ACT_NONE, bias=True, res=None, pads=(0, 0
                  res_periodic=rowmap[3] if rowmap else 0, tile_hint=hint, split_k=split_k,
                  live=livebuf.data_ptr() if livebuf is not None else None, colsum=csbuf.data_ptr() + 16 if colsum else None)
     r = Result()
+    # what vitcap_gemm_plan says this very launch is (host query): family, template arguments, grid
+    from vitcap_amd._lib import GemmPlanInfo
+    r.plan = GemmPlanInfo()
+    r.plan_rc = lib.vitcap_gemm_plan(C.byref(d), int(bptr is not None), int(rptr is not None), int(auxptr is not None), ldaux, int(zptr is not None), ldz,
+                                     C.byref(r.plan))
+    r.plan_err = lib.vitcap_last_error() if r.plan_rc != 0 else b''
+    r.family = GemmPlanInfo.FAMILIES[r.plan.family] if r.plan_rc == 0 else None
     r.rc = lib.vitcap_gemm_ex(C.c_void_p(aptr), C.c_void_p(wptr), C.c_void_p(bptr) if bptr else None, C.c_void_p(rptr) if rptr else None,
                               C.c_void_p(cptr), C.byref(d), C.c_void_p(auxptr) if auxptr else None, ldaux,
                               C.c_void_p(zptr) if zptr else None, ldz, _s())
     r.err = lib.vitcap_last_error() if r.rc != 0 else b''
+    assert (r.plan_rc, r.plan_err) == (r.rc, r.err), 'vitcap_gemm_plan and vitcap_gemm_ex disagree: %d %r / %d %r' % (r.plan_rc, r.plan_err, r.rc, r.err)
     torch.cuda.synchronize()
     r.f32, r.M, r.N, r.ldc, r.S, r.out_rows, r.orow = f32, M, N, ldc, S, out_rows, orow
     r.C = cbuf.cpu()
@@ -584,11 +592,25 @@ def test_4wave_epilogues(lib, hint):
     _n_sweep_256(lib, hint, 257, 192, '4-wave hint %d' % hint)
 
 
+def _took(r, family, what, **fields):
+    """the launch went to `family` (vitcap_gemm_plan, asked with the launch's own descriptor) with these plan fields"""
+    assert r.rc == 0, '%s refused: %s' % (what, r.err)
+    got = dict((k, getattr(r.plan, k)) for k in fields)
+    assert (r.family, got) == (family, fields), '%s: planned %s %s, expected %s %s' % (what, r.family, got, family, fields)
+
+
 @pytest.mark.parametrize('hint', [0, 5])
 def test_large_m_forms_and_downgrades(lib, hint):
-    """What tile_hint 0 and 5 choose at M = 2049, with the form vitcap_gemm_large_form reports asserted: under hint 0 the persistent
-    4-wave pipeline (form 2), downgraded to the one-tile register-epilogue form (1) at K = 128 or N % 256 != 0 and to the LDS-epilogue
-    form (0) at N % 8 != 0; under hint 5 the one-tile form for plain bf16 outputs and the 8-wave kernel (-1) for the rest"""
+    """What tile_hint 0 and 5 launch at M = 2049, exact against the reference, with the kernel family of every launch asserted through
+    vitcap_gemm_plan.
+    hint 0: the auto cost model sits in front of the large-tile family.  For K <= 768 it prices 64x64 tiles at 4 + 0.0165 T64 (T64 =
+    33 ceil(N / 64) tiles here), 128x128 tiles at no less than 16 and 256x256 tiles at 23 per round, so every N of this test (<= 516:
+    T64 <= 297, 8.9) runs the 64x64 ring -- NOT the 4-wave kernel.  (The 4-wave downgrades 42 -> 41 -> 40 are covered numerically under
+    their own hints by test_4wave_shapes / test_4wave_epilogues and test_4wave_downgrades_the_old_queries_cannot_see.)
+    hint 5: the 4-wave one-tile form for bf16 outputs without residual from K = 128 on -- register epilogue (form 1) where N and ldc
+    are multiples of 8, LDS epilogue (form 0) otherwise -- and the 8-wave kernel for the rest.
+    vitcap_gemm_large_form answers for the large-tile family alone (what hint 0 would pick if its cost model got that far); its
+    answers are asserted as they always were."""
     M = 2049
     q = lambda N, K, plain=False: lib.vitcap_gemm_large_form(M, N, K, hint | (0x100 if plain else 0))
     if hint == 0:
@@ -598,17 +620,71 @@ def test_large_m_forms_and_downgrades(lib, hint):
         assert q(256, 64) == -1                                                             # K < 128: the 8-wave kernel
     else:
         assert q(256, 192) == -1 and q(256, 192, True) % 10 == 1 and q(260, 192, True) % 10 == 0 and q(256, 64, True) == -1
+
+    def took(r, N, K, ldc, plain, what):
+        if hint == 0:
+            _took(r, 'ring', what, wm=2, wn=2, stages=4, block=256, lds_bytes=4 * 128 * 128, tiles_m=33, tiles_n=(N + 63) // 64)
+            assert (r.plan.grid[0], r.plan.grid[1]) == (33 * ((N + 63) // 64), 1)
+        elif plain and K >= 128:
+            _took(r, '4wave_tile', what, form=1 if N % 8 == 0 and ldc % 8 == 0 else 0, tiles_n=(N + 255) // 256, block=256)
+        else:
+            _took(r, '8wave', what, ph=4, mts=0, tiles_m=9, tiles_m_small=0, tiles_n=(N + 255) // 256, block=512)
+
     for K in (64, 128, 192, 448):
         for N in N256:
             P = Problem(M, N, K, seed=hint)
-            _exact(_run(lib, P, hint, f32=False, pads=(8, 16, 8, 0)), 'hint %d M=2049 N=%d K=%d bf16' % (hint, N, K))
-            _exact(_run(lib, P, hint, f32=True, res='inplace', pads=(8, 16, 4, 0)), 'hint %d M=2049 N=%d K=%d fp32+residual' % (hint, N, K))
+            r = _run(lib, P, hint, f32=False, pads=(8, 16, 8, 0))
+            _exact(r, 'hint %d M=2049 N=%d K=%d bf16' % (hint, N, K))
+            took(r, N, K, N + 8, True, 'hint %d N=%d K=%d bf16' % (hint, N, K))
+            r = _run(lib, P, hint, f32=True, res='inplace', pads=(8, 16, 4, 0))
+            _exact(r, 'hint %d M=2049 N=%d K=%d fp32+residual' % (hint, N, K))
+            took(r, N, K, N + 4, False, 'hint %d N=%d K=%d fp32+residual' % (hint, N, K))
         for N in (252, 256, 264):
             P = Problem(M, N, K, seed=hint)
-            _exact(_run(lib, P, hint, f32=False, pads=(8, 16, 4, 0)), 'hint %d M=2049 N=%d K=%d bf16 8-byte rows' % (hint, N, K))
-            _close_act(_run(lib, P, hint, f32=False, act=ACT_GELU, pads=(8, 16, 8, 0)), 'large-M bf16+gelu')
-            _exact(_run(lib, P, hint, f32=True, pads=(8, 16, 4, 0)), 'hint %d M=2049 N=%d K=%d fp32+bias' % (hint, N, K))
-            _exact(_run(lib, P, hint, f32=False, res='sep', pads=(8, 16, 8, 12)), 'hint %d M=2049 N=%d K=%d bf16+residual' % (hint, N, K))
+            r = _run(lib, P, hint, f32=False, pads=(8, 16, 4, 0))
+            _exact(r, 'hint %d M=2049 N=%d K=%d bf16 8-byte rows' % (hint, N, K))
+            took(r, N, K, N + 4, True, 'hint %d N=%d K=%d bf16 8-byte rows' % (hint, N, K))
+            r = _run(lib, P, hint, f32=False, act=ACT_GELU, pads=(8, 16, 8, 0))
+            _close_act(r, 'large-M bf16+gelu')
+            took(r, N, K, N + 8, True, 'hint %d N=%d K=%d bf16+gelu' % (hint, N, K))
+            r = _run(lib, P, hint, f32=True, pads=(8, 16, 4, 0))
+            _exact(r, 'hint %d M=2049 N=%d K=%d fp32+bias' % (hint, N, K))
+            took(r, N, K, N + 4, False, 'hint %d N=%d K=%d fp32+bias' % (hint, N, K))
+            r = _run(lib, P, hint, f32=False, res='sep', pads=(8, 16, 8, 12))
+            _exact(r, 'hint %d M=2049 N=%d K=%d bf16+residual' % (hint, N, K))
+            took(r, N, K, N + 8, False, 'hint %d N=%d K=%d bf16+residual' % (hint, N, K))
+
+
+def test_4wave_downgrades_the_old_queries_cannot_see(lib):
+    """Two 4-wave choices that vitcap_gemm_large_form cannot report (it takes no ldc and answers -1 below 2048 rows), asserted through
+    vitcap_gemm_plan and exact against the reference.
+    (a) bf16 rows that are not 16-byte multiples (ldc = N + 4): the register epilogue's 16-byte stores do not apply, so tile_hint 41 and
+        42 both run the one-tile form with the LDS epilogue (form 0: 256-row tiles, MI = 8).
+    (b) tile_hint 42 below 2048 rows: 256 columns are one column tile, so M rows are ceil(M / (32 MI)) tiles -- one round of the GPU's
+        CUs whatever MI in {8, 7, 6} -- and a round costs 0.3 + MI, so the 192-row tile (MI = 6) wins: two tiles for 193, 225 and 257
+        rows, on a grid of two workgroups.  K = 192 is three k-tiles, fewer than the MI / 2 + 3 = 6 the deferred-store variant needs:
+        the plain persistent kernel runs."""
+    for hint in (41, 42):
+        P = Problem(2049, 256, 192, seed=hint)
+        r = _run(lib, P, hint, f32=False, pads=(8, 16, 4, 0))
+        _exact(r, 'hint %d 2049x256x192 bf16 ldc = N + 4' % hint)
+        _took(r, '4wave_tile', 'hint %d ldc = N + 4' % hint, form=0, mi=8, tiles_m=9, tiles_n=1, block=256)
+        assert r.plan.grid[0] == 9
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for M in (193, 225, 257):
+        # pick_mi's rule, restated: cost = rounds x (0.3 + MI), MI from 8 down, a shorter tile must win 1.5 %
+        best, best_c = 8, 1e30
+        for mi in (8, 7, 6):
+            c = -(-(-(-M // (32 * mi))) // cus) * (0.3 + mi)
+            if c < best_c * 0.985:
+                best, best_c = mi, c
+        assert cus < 2 or best == 6                # one round for every height on any GPU with 2+ CUs: the 192-row tile
+        P = Problem(M, 256, 192, seed=M)
+        r = _run(lib, P, 42, f32=False, pads=(8, 16, 8, 0))
+        _exact(r, 'hint 42 %dx256x192 bf16' % M)
+        tiles = -(-M // (32 * best))
+        _took(r, '4wave_persistent', 'hint 42 M=%d' % M, form=2, mi=best, variant=0, tiles_m=tiles, tiles_n=1, n_big=tiles, block=256)
+        assert r.plan.grid[0] == tiles
 
 
 class _Reserved(object):

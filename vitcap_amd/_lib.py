@@ -39,6 +39,17 @@ class GemmDesc(C.Structure):
         super().__init__(*a, **kw)
 
 
+class GemmPlanInfo(C.Structure):
+    """vitcap_gemm_plan_info: the launch vitcap_gemm_ex would make for a descriptor (vitcap_gemm_plan, host only)."""
+    FAMILIES = ('ring', 'resident', 'rowstat', 'skinny', '8wave', '4wave_tile', '4wave_persistent')      # VITCAP_GEMM_FAMILY_*
+    VARIANTS = ('plain', 'extras', 'defer', 'prefetch')                                                  # VITCAP_GEMM_4W_*
+    _fields_ = [(n, C.c_int) for n in ('family', 'wm', 'wn', 'stages', 'act', 'out_f32', 'has_res', 'partial', 'ph', 'mts', 'form', 'mi',
+                                       'variant', 'ln_fused', 'ln_follows', 'split_k', 'kt_per_split')] \
+        + [('slab', C.c_longlong)] \
+        + [(n, C.c_int) for n in ('tiles_m', 'tiles_n', 'n_big', 'tiles_m_small', 'group_n')] \
+        + [('grid', C.c_int * 3), ('block', C.c_int), ('lds_bytes', C.c_int)]
+
+
 class CtItem(C.Structure):
     _fields_ = [('w', C.c_void_p), ('w_bf16', C.c_void_p), ('wt_bf16', C.c_void_p), ('N', C.c_int32), ('K', C.c_int32),
                 ('ldt', C.c_int32), ('tile0', C.c_int32)]
@@ -120,6 +131,7 @@ _SIGS = {
     'vitcap_gemm_tile_plan': (C.c_int, [C.c_int, C.c_int, C.c_int, vp]),
     'vitcap_gemm_large_form': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'vitcap_gemm_reserve_cus': (C.c_int, [C.c_int]),
+    'vitcap_gemm_plan': (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmPlanInfo)]),
     'vitcap_set_dropout_salt': (C.c_int, [vp]),
     'vitcap_layernorm_fwd': (C.c_int, [vp, C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, vp]),
     'vitcap_sum_layernorm': (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp, C.c_int, C.c_int, vp, vp, C.c_float, vp, vp,

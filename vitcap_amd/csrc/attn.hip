@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
     const int qd = nwork >> 3, rm = nwork & 7, xcd = wid & 7;
     wid = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (wid >> 3);
   }
-  if (rev) wid = nwork - 1 - wid;      // images last-to-first (common.h: vc_tls_walk_rev)
+  if (rev) wid = nwork - 1 - wid;      // images last-to-first (call_state.h: vc_tls_walk_rev)
   const int qb = (q_lo >> 7) + wid % nqb;
   const int h = (wid / nqb) % NH, b = wid / (nqb * NH);
   const int q0 = qb * 128 + w * 32;

@@ -5,6 +5,14 @@
 #include <stdint.h>
 
 void vitcap_set_error(const char* fmt, ...);
+// argument check of an entry point: record the message, return VITCAP_EINVAL (include/vitcap_hip.h)
+#define VC_REQUIRE(cond, ...)                 \
+  do {                                        \
+    if (!(cond)) {                            \
+      vitcap_set_error(__VA_ARGS__);          \
+      return VITCAP_EINVAL;                   \
+    }                                         \
+  } while (0)
 
 // While vitcap_engine_decode enqueues its step loop, this pointer names the device counter of sequences (beam search: images) still
 // unfinished; the decode-step launchers pass it to their kernels, which return at entry once it reads 0 -- the reference's

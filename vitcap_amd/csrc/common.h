@@ -27,14 +27,6 @@ __device__ __forceinline__ bool vc_is_eos(int tok, int eos, const VcEosExtra& x)
     if ((live) != nullptr && *(live) == 0) return; \
   } while (0)
 
-#define VC_REQUIRE(cond, ...)                 \
-  do {                                        \
-    if (!(cond)) {                            \
-      vitcap_set_error(__VA_ARGS__);          \
-      return VITCAP_EINVAL;                   \
-    }                                         \
-  } while (0)
-
 #define VC_LAUNCH_CHECK(name)                                                   \
   do {                                                                          \
     hipError_t e_ = hipGetLastError();                                          \

@@ -13,30 +13,10 @@
 //
 // The accumulators are computed transposed (first MFMA operand = W fragment): each lane then holds
 // 4 consecutive n for one m, so bias/residual loads and the C store are 8/16-byte vectors.
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "common.h"
 #include "gemm_args.h"
+#include "gemm_plan.h"
 
-
-#include <algorithm>
-#include <mutex>
-#include <utility>
-#include <vector>
-
-namespace {
-
-// width (in 256-column tiles) of the column groups the 256x256 kernels walk
-int tile_group_n(int tiles_n) {
-  // measured at M = 36928 (column-group width swept 1..6): N = 3072 214 -> 199 us with groups of 2..6 tiles (W = 4.7 MB does not fit
-  // one XCD's 4 MB L2 next to the A tiles; HBM fetch 169 -> 152 MiB per launch); N = 2304 (W = 3.5 MB fits) same time with
-  // 7 % MORE fetch when grouped, so only wider outputs are grouped
-  return tiles_n > 9 ? 3 : tiles_n;
-}
-
-}  // namespace
-int vc_tile_group_n(int tiles_n) { return tile_group_n(tiles_n); }
 namespace {
 
 template <int N>
@@ -792,7 +772,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(VC_GEMM256_VGPR
   const int gw = gleft < p.group_n ? gleft : p.group_n;
   int tm = rem / gw;
   const int tn = gi * p.group_n + rem - tm * gw;
-  // walk direction (common.h: vc_tls_walk_rev): row tiles last-to-first, and every other column group the other way round (a
+  // walk direction (call_state.h: vc_tls_walk_rev): row tiles last-to-first, and every other column group the other way round (a
   // group's pass over A ends where the next one starts)
   if ((p.rev != 0) != ((gi & 1) != 0)) tm = tiles_m - 1 - tm;
   if (!small) {
@@ -802,107 +782,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(VC_GEMM256_VGPR
   }
 }
 
-// ---- tile plan of a launch: how many rows go to 256-row tiles, and the height of the tiles behind them ----------------------
-// A launch of T equal tiles on C CUs costs ceil(T / C) tile times: 435 tiles (M = 36928, N = 768) pay 2 rounds for 1.7 rounds of
-// work, 1305 (N = 2304) pay 6 for 5.1.  The plan keeps 256-row tiles for the rows that fill whole rounds and cuts the rest into
-// 192- or 128-row tiles, chosen by simulating the dispatch (earliest free CU takes the next workgroup) with tile costs relative
-// to the 256-row tile (a shorter tile has the same W traffic and per-phase overheads for fewer flops: measured, tools/gemm_bench.py).
-struct TilePlan { int tm_big, mts, tm_small; };
-TilePlan plan_tiles(int M, int tiles_n, int K) {
-  static const int n_cu = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      return prop.multiProcessorCount;
-    return 256;
-  }();
-  const int tm_full = (M + 255) / 256;
-  TilePlan best{tm_full, 0, 0};
-  struct Key { int M, tn, K; };
-  static std::mutex mu;
-  static std::vector<std::pair<Key, TilePlan>> cache;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    for (const auto& e : cache)
-      if (e.first.M == M && e.first.tn == tiles_n && e.first.K == K) return e.second;
-  }
-  // relative tile costs: main loop ~ (64 MT + overhead) cycles per phase, epilogue ~ MT; K = 768 tiles are about half epilogue
-  const float c3 = 0.80f, c2 = 0.60f;
-  float best_t = ceilf((float)(tm_full * tiles_n) / n_cu);
-  const float need = best_t * 0.97f;                         // a plan must win 3 % to replace the plain grid
-  const int span = (int)(2.5f * n_cu / tiles_n) + 2;         // rows worth ~2.5 rounds can move to short tiles
-  std::vector<float> heap;
-  for (int mts = 3; mts >= 2; --mts) {
-    const float cs = mts == 3 ? c3 : c2;
-    for (int tb = tm_full - 1; tb >= 0 && tb >= tm_full - span; --tb) {
-      const int rows_left = M - tb * 256;
-      const int ts = (rows_left + 64 * mts - 1) / (64 * mts);
-      const int nb = tb * tiles_n, ns = ts * tiles_n;
-      // big tiles: CU j is free at (nb / C + (j < nb % C)); the short tiles go to the earliest free CU
-      heap.assign(n_cu, 0.f);
-      for (int j = 0; j < n_cu; ++j) heap[j] = -(float)(nb / n_cu + (j < nb % n_cu ? 1 : 0));
-      std::make_heap(heap.begin(), heap.end());              // max-heap of negated free times
-      float end = nb ? (float)((nb + n_cu - 1) / n_cu) : 0.f;
-      for (int i = 0; i < ns; ++i) {
-        std::pop_heap(heap.begin(), heap.end());
-        const float f = -heap.back() + cs;
-        heap.back() = -f;
-        std::push_heap(heap.begin(), heap.end());
-        end = f > end ? f : end;
-      }
-      if (end < need && end < best_t - 1e-4f) { best_t = end; best = TilePlan{tb, mts, ts}; }
-    }
-  }
-  std::lock_guard<std::mutex> g(mu);
-  cache.push_back({Key{M, tiles_n, K}, best});
-  return best;
-}
-
 template <int ACT, int OUT_F32, bool HAS_RES, int PH, int MTS>
-int launch_256_t(const GemmArgs& p, int nwg, hipStream_t s) {
-  constexpr int smem = 8 * 64 * 272;   // max(2 x 64 KiB k-tile buffers, 8 x 17 KiB epilogue patches)
+int launch_256_t(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
   auto kern = gemm_nt_256_kernel<ACT, OUT_F32, HAS_RES, PH, MTS>;
-  VC_FUNC_SMEM(kern, smem);
-  VC_LAUNCH_GEMM(kern, dim3(nwg), dim3(512), smem, s, p);
+  VC_FUNC_SMEM(kern, pl.lds_bytes);
+  VC_LAUNCH_GEMM(kern, dim3(pl.grid[0]), dim3(512), pl.lds_bytes, s, p);
   VC_LAUNCH_CHECK("gemm_nt_256");
   return VITCAP_OK;
 }
 
-// mix: -1 = plan_tiles decides, 0 = 256-row tiles only, 3 / 2 = every tile 192 / 128 rows (tile-cost measurements)
-template <int ACT, int OUT_F32, bool HAS_RES, int PH>
-int launch_256(const GemmArgs& a, hipStream_t s, int mix = 0) {
-  if constexpr ((PH & 512) != 0) mix = 0;          // fused-LayerNorm launches: 256-row tiles only
-  GemmArgs p = a;
-  p.tiles_n = (a.N + 255) / 256;
-  p.group_n = tile_group_n(p.tiles_n);
-  TilePlan pl{(a.M + 255) / 256, 0, 0};
-  if (a.aux || a.zout || a.colsum) mix = 0;
-  if (mix < 0) pl = plan_tiles(a.M, p.tiles_n, a.K);
-  else if (mix > 0) pl = TilePlan{0, mix, (a.M + 64 * mix - 1) / (64 * mix)};
-  p.tiles_m = pl.tm_big;
-  p.tiles_m_small = pl.tm_small;
-  p.n_big = pl.tm_big * p.tiles_n;
-  const int nwg = p.n_big + pl.tm_small * p.tiles_n;
-  if constexpr ((PH & 512) == 0) {
-    if (a.aux || a.zout || a.colsum) return launch_256_t<ACT, OUT_F32, HAS_RES, PH | 8, 0>(p, nwg, s);   // training extras: 256-row tiles only
-    if (pl.mts == 3) return launch_256_t<ACT, OUT_F32, HAS_RES, PH, 3>(p, nwg, s);
-    if (pl.mts == 2) return launch_256_t<ACT, OUT_F32, HAS_RES, PH, 2>(p, nwg, s);
-  }
-  return launch_256_t<ACT, OUT_F32, HAS_RES, PH, 0>(p, nwg, s);
+// the plan's (ph, mts) onto the builds: training extras and fused LayerNorm run 256-row tiles only (gemm_plan.cpp: plan_8w)
+template <int ACT, int OUT_F32, bool HAS_RES>
+int launch_256(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  if (pl.ph == (4 | 8)) return launch_256_t<ACT, OUT_F32, HAS_RES, 4 | 8, 0>(p, pl, s);
+  if (pl.mts == 3) return launch_256_t<ACT, OUT_F32, HAS_RES, 4, 3>(p, pl, s);
+  if (pl.mts == 2) return launch_256_t<ACT, OUT_F32, HAS_RES, 4, 2>(p, pl, s);
+  return launch_256_t<ACT, OUT_F32, HAS_RES, 4, 0>(p, pl, s);
 }
 
-template <int PH>
-int dispatch_256(const GemmArgs& a, int act, int out_f32, hipStream_t s, int mix = 0) {
-  const bool res = a.res != nullptr;
-#define CASE(ACT_, OUT_)                                                  \
-  if (act == ACT_ && out_f32 == OUT_)                                     \
-    return res ? launch_256<ACT_, OUT_, true, PH>(a, s, mix) : launch_256<ACT_, OUT_, false, PH>(a, s, mix);
+int dispatch_256(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  if (pl.ln_fused)
+    return pl.has_res ? launch_256_t<VITCAP_ACT_NONE, 1, true, 4 | 512, 0>(p, pl, s) : launch_256_t<VITCAP_ACT_NONE, 1, false, 4 | 512, 0>(p, pl, s);
+#define CASE(ACT_, OUT_)                        \
+  if (pl.act == ACT_ && pl.out_f32 == OUT_)     \
+    return pl.has_res ? launch_256<ACT_, OUT_, true>(p, pl, s) : launch_256<ACT_, OUT_, false>(p, pl, s);
   CASE(VITCAP_ACT_NONE, 0)
   CASE(VITCAP_ACT_NONE, 1)
   CASE(VITCAP_ACT_GELU_ERF, 0)
   CASE(VITCAP_ACT_GELU_ERF, 1)
 #undef CASE
-  vitcap_set_error("gemm(256): unsupported act %d / out %d", act, out_f32);
+  vitcap_set_error("gemm(256): no build for act %d / out %d", pl.act, pl.out_f32);
   return VITCAP_EINVAL;
 }
 
@@ -1016,116 +925,64 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs q) {
   }
 }
 
+// ---- launchers: they take what the plan says (gemm_plan.cpp) and decide nothing ----------------------------------------------------
 template <int WAVES_M>
-int launch_skinny(const GemmArgs& a, int act, int out_f32, int split_k, hipStream_t s) {
-  constexpr int BM = 32 * WAVES_M, BN = 32 * (4 / WAVES_M);
+int launch_skinny(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
   SkinnyArgs q;
   q.g = a;
-  q.split_k = split_k;
-  q.kc = a.K / split_k;
-  q.slab = (size_t)a.M * a.ldc;
-  dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, split_k);
-  const bool res = a.res != nullptr;
-#define SK(ACT_, OUT_, RES_, PART_)                                                                       \
-  hipLaunchKernelGGL((gemm_skinny_kernel<WAVES_M, ACT_, OUT_, RES_, PART_>), grid, dim3(256), 0, s, q)
-  if (split_k > 1) SK(0, 1, false, true);
-  else if (act == VITCAP_ACT_NONE && !out_f32 && !res) SK(0, 0, false, false);
-  else if (act == VITCAP_ACT_NONE && out_f32 && !res) SK(0, 1, false, false);
-  else if (act == VITCAP_ACT_NONE && out_f32 && res) SK(0, 1, true, false);
-  else if (act == VITCAP_ACT_NONE && !out_f32 && res) SK(0, 0, true, false);
-  else if (act == VITCAP_ACT_GELU_ERF && !out_f32 && !res) SK(1, 0, false, false);
-  else if (act == VITCAP_ACT_GELU_ERF && out_f32 && !res) SK(1, 1, false, false);
-  else if (act == VITCAP_ACT_TANH && !out_f32 && !res) SK(2, 0, false, false);
-  else if (act == VITCAP_ACT_TANH && out_f32 && !res) SK(2, 1, false, false);
-  else {
-    vitcap_set_error("gemm(skinny): unsupported epilogue act=%d out=%d res=%d", act, out_f32, (int)res);
-    return VITCAP_EINVAL;
-  }
+  q.split_k = pl.split_k;
+  q.kc = pl.kt_per_split * 64;
+  q.slab = (size_t)pl.slab;
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+#define SK(ACT_, OUT_, RES_, PART_)                                                                 \
+  if (pl.act == ACT_ && pl.out_f32 == OUT_ && (pl.has_res != 0) == RES_ && (pl.partial != 0) == PART_) \
+    hipLaunchKernelGGL((gemm_skinny_kernel<WAVES_M, ACT_, OUT_, RES_, PART_>), grid, dim3(256), 0, s, q)
+  SK(0, 1, false, true);
+  SK(0, 0, false, false);
+  SK(0, 1, false, false);
+  SK(0, 1, true, false);
+  SK(0, 0, true, false);
+  SK(1, 0, false, false);
+  SK(1, 1, false, false);
+  SK(2, 0, false, false);
+  SK(2, 1, false, false);
 #undef SK
   VC_LAUNCH_CHECK("gemm_skinny");
   return VITCAP_OK;
 }
 
-template <int WM, int WN, int ACT, int OUT_F32, bool HAS_RES>
-int launch(const GemmArgs& a, hipStream_t s) {
-  constexpr int BM = 32 * WM, BN = 32 * WN;
-  constexpr int NST = (WM <= 2 && WN <= 2) ? 4 : 2;     // small tiles (decode shapes): 4 stages
-  constexpr int smem = NST * (BM + BN) * 64 * 2;
-  auto kern = gemm_nt_kernel<WM, WN, ACT, OUT_F32, HAS_RES, NST>;
-  if (smem > 48 * 1024) VC_FUNC_SMEM(kern, smem);
-  GemmArgs p = a;
-  p.tiles_m = (a.M + BM - 1) / BM;
-  p.tiles_n = (a.N + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, a.split_k > 1 ? a.split_k : 1), dim3(256), smem, s, p);
-  VC_LAUNCH_CHECK("gemm_nt");
+// gemm_nt_kernel, every family (ring / resident / rowstat): one instantiation of this launcher per kernel, so VC_FUNC_SMEM's
+// per-call-site memory is per kernel.  The ring's tiles of up to 48 KiB need no attribute
+template <int WM, int WN, int ACT, int OUT_F32, bool HAS_RES, int NST, bool ROWSTAT = false>
+int launch_nt(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  auto kern = gemm_nt_kernel<WM, WN, ACT, OUT_F32, HAS_RES, NST, ROWSTAT>;
+  if (pl.family != VITCAP_GEMM_FAMILY_RING || pl.lds_bytes > 48 * 1024) VC_FUNC_SMEM(kern, pl.lds_bytes);
+  hipLaunchKernelGGL(kern, dim3(pl.grid[0], pl.grid[1]), dim3(256), pl.lds_bytes, s, p);
+  VC_LAUNCH_CHECK(ROWSTAT ? "gemm_nt(rowstat)" : NST == 12 ? "gemm_nt(resident)" : "gemm_nt");
   return VITCAP_OK;
 }
 
-// "Resident" form for the decode-step shapes (M <= 256 rows, K a multiple of 768): NST = 12 stages = the WHOLE 768-long k
-// range of the workgroup is requested by LDS-DMA in the prologue (one HBM/L2 round trip instead of 12 / (NST-1) dependent
-// ones), then multiplied.  K > 768 is cut into K / 768 splits (blockIdx.y) that write fp32 partial slabs, summed by
-// vitcap_sum_layernorm.  LDS: 12 * (BM + BN) * 128 B <= 160 KiB, i.e. BM + BN <= 96.
-template <int WM, int WN, int ACT, int OUT_F32, bool HAS_RES>
-int launch_resident(const GemmArgs& a, hipStream_t s) {
-  constexpr int BM = 32 * WM, BN = 32 * WN, NST = 12;
-  constexpr int smem = NST * (BM + BN) * 64 * 2;
-  static_assert(smem <= 160 * 1024, "resident tile does not fit the LDS");
-  auto kern = gemm_nt_kernel<WM, WN, ACT, OUT_F32, HAS_RES, NST>;
-  VC_FUNC_SMEM(kern, smem);
-  GemmArgs p = a;
-  p.tiles_m = (a.M + BM - 1) / BM;
-  p.tiles_n = (a.N + BN - 1) / BN;
-  const int splits = a.K / 768;
-  if (splits > 1) {
-    p.split_k = splits;
-    p.kt_per_split = 12;
-    p.slab = (size_t)a.M * a.ldc;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, splits), dim3(256), smem, s, p);
-  VC_LAUNCH_CHECK("gemm_nt(resident)");
-  return VITCAP_OK;
-}
-
+// "Resident" form (12 stages = the whole 768-long k range of the workgroup in LDS: 12 * (BM + BN) * 128 B <= 160 KiB, BM + BN <= 96)
 template <int WM, int WN>
-int dispatch_resident(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
-  const bool res = a.res != nullptr;
-  if (a.K > 768) return launch_resident<WM, WN, VITCAP_ACT_NONE, 1, false>(a, s);      // partial slabs only
-  if (act == VITCAP_ACT_NONE && !out_f32 && !res) return launch_resident<WM, WN, VITCAP_ACT_NONE, 0, false>(a, s);
-  if (act == VITCAP_ACT_NONE && out_f32 && !res) return launch_resident<WM, WN, VITCAP_ACT_NONE, 1, false>(a, s);
-  if (act == VITCAP_ACT_NONE && out_f32 && res) return launch_resident<WM, WN, VITCAP_ACT_NONE, 1, true>(a, s);
-  if (act == VITCAP_ACT_GELU_ERF && !out_f32 && !res) return launch_resident<WM, WN, VITCAP_ACT_GELU_ERF, 0, false>(a, s);
-  if (act == VITCAP_ACT_GELU_ERF && out_f32 && !res) return launch_resident<WM, WN, VITCAP_ACT_GELU_ERF, 1, false>(a, s);
-  vitcap_set_error("gemm(resident): unsupported epilogue act=%d out=%d res=%d", act, out_f32, (int)res);
+int dispatch_resident(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  static_assert(12 * (32 * WM + 32 * WN) * 64 * 2 <= 160 * 1024, "resident tile does not fit the LDS");
+  const int act = pl.act, out = pl.out_f32, res = pl.has_res;
+  if (act == VITCAP_ACT_NONE && !out && !res) return launch_nt<WM, WN, VITCAP_ACT_NONE, 0, false, 12>(p, pl, s);
+  if (act == VITCAP_ACT_NONE && out && !res) return launch_nt<WM, WN, VITCAP_ACT_NONE, 1, false, 12>(p, pl, s);
+  if (act == VITCAP_ACT_NONE && out && res) return launch_nt<WM, WN, VITCAP_ACT_NONE, 1, true, 12>(p, pl, s);
+  if (act == VITCAP_ACT_GELU_ERF && !out && !res) return launch_nt<WM, WN, VITCAP_ACT_GELU_ERF, 0, false, 12>(p, pl, s);
+  if (act == VITCAP_ACT_GELU_ERF && out && !res) return launch_nt<WM, WN, VITCAP_ACT_GELU_ERF, 1, false, 12>(p, pl, s);
+  vitcap_set_error("gemm(resident): no build for act=%d out=%d res=%d", act, out, res);
   return VITCAP_EINVAL;
 }
 
-// Vocabulary GEMM + row statistics (vitcap_gemm_desc.rowstat): 64 x 64 tiles for the greedy decode step (M <= 256 rows: weights
-// stream once, most workgroups win), 128 x 128 tiles for beam batches (M = images x beams rows)
-template <int WM, int WN, int NST>
-int launch_rowstat_t(const GemmArgs& a, hipStream_t s) {
-  constexpr int BM = 32 * WM, BN = 32 * WN, smem = NST * (BM + BN) * 64 * 2;
-  auto kern = gemm_nt_kernel<WM, WN, VITCAP_ACT_NONE, 1, false, NST, true>;
-  VC_FUNC_SMEM(kern, smem);
-  GemmArgs p = a;
-  p.tiles_m = (a.M + BM - 1) / BM;
-  p.tiles_n = (a.N + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n, 1), dim3(256), smem, s, p);
-  VC_LAUNCH_CHECK("gemm_nt(rowstat)");
-  return VITCAP_OK;
-}
-
-int launch_rowstat(const GemmArgs& a, hipStream_t s) {
-  // re-measured with the ring's counted waits working (docs/LAB_r01_r04.md 4.2 x): 3 / 6 / 8 stages and 64x128 tiles are all slower than
-  // 64x64 x 4 stages in the decode loop (decode phase 5.10-5.18 ms against 5.17-5.26)
-  return a.M <= 256 ? launch_rowstat_t<2, 2, 4>(a, s) : launch_rowstat_t<4, 4, 2>(a, s);
-}
-
+// LDS-staged ring: small tiles (decode shapes) 4 stages, 128x128 tiles 2 (gemm_plan.cpp: plan_ring)
 template <int WM, int WN>
-int dispatch(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
-  const bool res = a.res != nullptr;
+int dispatch(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  constexpr int NST = (WM <= 2 && WN <= 2) ? 4 : 2;
 #define CASE(ACT_, OUT_)                                                         \
-  if (act == ACT_ && out_f32 == OUT_)                                            \
-    return res ? launch<WM, WN, ACT_, OUT_, true>(a, s) : launch<WM, WN, ACT_, OUT_, false>(a, s);
+  if (pl.act == ACT_ && pl.out_f32 == OUT_)                                      \
+    return pl.has_res ? launch_nt<WM, WN, ACT_, OUT_, true, NST>(p, pl, s) : launch_nt<WM, WN, ACT_, OUT_, false, NST>(p, pl, s);
   CASE(VITCAP_ACT_NONE, 0)
   CASE(VITCAP_ACT_NONE, 1)
   CASE(VITCAP_ACT_GELU_ERF, 0)
@@ -1133,59 +990,43 @@ int dispatch(const GemmArgs& a, int act, int out_f32, hipStream_t s) {
   CASE(VITCAP_ACT_TANH, 0)
   CASE(VITCAP_ACT_TANH, 1)
 #undef CASE
-  vitcap_set_error("gemm: unsupported act %d / out %d", act, out_f32);
+  vitcap_set_error("gemm: no build for act %d / out %d", pl.act, pl.out_f32);
+  return VITCAP_EINVAL;
+}
+
+// the one switch from the plan onto the template launchers
+int launch_plan(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  const int tile = pl.wm * 10 + pl.wn;
+  switch (pl.family) {
+    case VITCAP_GEMM_FAMILY_RING:
+      if (tile == 11) return dispatch<1, 1>(p, pl, s);
+      if (tile == 12) return dispatch<1, 2>(p, pl, s);
+      if (tile == 21) return dispatch<2, 1>(p, pl, s);
+      if (tile == 22) return dispatch<2, 2>(p, pl, s);
+      if (tile == 44) return dispatch<4, 4>(p, pl, s);
+      break;
+    case VITCAP_GEMM_FAMILY_RESIDENT:
+      if (tile == 21) return dispatch_resident<2, 1>(p, pl, s);
+      if (tile == 11) return dispatch_resident<1, 1>(p, pl, s);
+      if (tile == 12) return dispatch_resident<1, 2>(p, pl, s);
+      break;
+    case VITCAP_GEMM_FAMILY_ROWSTAT:
+      if (tile == 22) return launch_nt<2, 2, VITCAP_ACT_NONE, 1, false, 4, true>(p, pl, s);
+      if (tile == 44) return launch_nt<4, 4, VITCAP_ACT_NONE, 1, false, 2, true>(p, pl, s);
+      break;
+    case VITCAP_GEMM_FAMILY_SKINNY:
+      return pl.wm == 2 ? launch_skinny<2>(p, pl, s) : launch_skinny<4>(p, pl, s);
+    case VITCAP_GEMM_FAMILY_8WAVE:
+      return dispatch_256(p, pl, s);
+    case VITCAP_GEMM_FAMILY_4WAVE_TILE:
+    case VITCAP_GEMM_FAMILY_4WAVE_PERSISTENT:
+      return vc_launch_4w(p, pl, s);
+  }
+  vitcap_set_error("gemm: no launcher for family %d, tile %d x %d waves", pl.family, pl.wm, pl.wn);
   return VITCAP_EINVAL;
 }
 
 }  // namespace
-
-// Which kernel family runs a large GEMM under tile_hint `hint` (0 = auto, 5 = one tile per workgroup): -1 = the 8-wave kernel of this
-// file, 1 / 2 = the one-tile / persistent form of the 4-wave kernel (gemm4w.hip).  Measured end to end (docs/LAB_r01_r04.md 4.3):
-//   auto (one stream): the persistent 4-wave form, +1.8 % images/s at B = 64 and B = 512 against the 8-wave kernel + planned tile mix;
-//   tile_hint 5 (the 2-slot pipeline: another stream's small kernels must slip in between tiles): the 8-wave kernel -- a persistent
-//   grid owns every CU for the whole GEMM, and a 512-register workgroup leaves no room for a co-resident decode wave (B = 64: 3802
-//   vs 3517 img/s) -- except the bf16-output GEMMs without residual (qkv, fc1) below 64k rows, which gain on the 4-wave one-tile
-//   form (qkv alone 3 900, fc1 alone 3 907 against 3 856 / 3 866 img/s all 8-wave; proj / fc2 lose: 3 748;
-//   profiles/r05_pipeline_gemm_forms.txt).  From 64k rows per launch on that mix is a tie or slightly behind.
-static int large_gemm_form(int M, int hint, bool plain_bf16) {
-  if (M < 2048) return -1;
-  if (hint == 0) return 2;
-  if (hint == 5) return plain_bf16 && M < 65536 ? 1 : -1;
-  return -1;
-}
-
-// the tile_hint values vitcap_gemm_ex knows (include/vitcap_hip.h)
-static bool known_tile_hint(int h) {
-  return h == 0 || h == 1 || h == 2 || h == 4 || h == 5 || (h >= 13 && h <= 15) || (h >= 20 && h <= 24) || (h >= 30 && h <= 33) ||
-         (h >= 40 && h <= 42);
-}
-
-extern "C" int vitcap_gemm_large_form(int M, int N, int K, int tile_hint) {
-  // tile_hint | 0x100: the query is about a bf16-output GEMM without residual (under tile_hint 5 those run the 4-wave one-tile form)
-  const bool plain_bf16 = (tile_hint & 0x100) != 0;
-  tile_hint &= 0xff;
-  int form = large_gemm_form(M, tile_hint, plain_bf16);
-  if (form < 0) return -1;
-  if (K < 128) return -1;                                   // vc_4w_supports
-  // launch_4w's downgrade rules for plain rows (what the engine's large GEMMs use): the persistent pipeline needs three k-tiles and
-  // whole 256-column tiles, the register epilogue 16-byte bf16 stores
-  if (form == 2 && (K < 192 || (N & 255) != 0)) form = 1;
-  if (form != 0 && (N & 7) != 0) form = 0;
-  return form + 10 * vc_4w_pick_mi(M, (N + 255) / 256, form);
-}
-
-extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, const float* residual, void* C,
-                              const vitcap_gemm_desc* d, const void* aux_bf16, int ldaux, void* zout_bf16, int ldz,
-                              void* stream);
-
-extern "C" int vitcap_gemm_tile_plan(int M, int N, int K, int* plan3) {
-  VC_REQUIRE(M > 0 && N > 0 && K > 0 && plan3, "gemm_tile_plan: bad arguments");
-  const TilePlan pl = plan_tiles(M, (N + 255) / 256, K);
-  plan3[0] = pl.tm_big;
-  plan3[1] = pl.mts;
-  plan3[2] = pl.tm_small;
-  return VITCAP_OK;
-}
 
 extern "C" int vitcap_gemm_bias_act(const void* A, const void* W, const float* bias, const float* residual,
                                     void* C, const vitcap_gemm_desc* d, void* stream) {
@@ -1196,15 +1037,12 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
                               const vitcap_gemm_desc* d, const void* aux_bf16, int ldaux, void* zout_bf16, int ldz,
                               void* stream) {
   VC_REQUIRE(A && W && C && d, "gemm: null pointer");
-  VC_REQUIRE(d->abi == VITCAP_ABI_VERSION, "gemm: descriptor built against ABI %d, this library is ABI %d", d->abi, VITCAP_ABI_VERSION);
-  VC_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
-  VC_REQUIRE(d->K % 64 == 0, "gemm: K=%d must be a multiple of 64", d->K);
-  VC_REQUIRE(d->N % 4 == 0 && d->ldc % 4 == 0, "gemm: N=%d and ldc=%d must be multiples of 4", d->N, d->ldc);
-  VC_REQUIRE(d->lda % 8 == 0 && d->ldw % 8 == 0, "gemm: lda=%d ldw=%d must be multiples of 8", d->lda, d->ldw);
-  VC_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0,
-             "gemm: A/W/C must be 16-byte aligned");
-  VC_REQUIRE(!residual || (d->ldr % 4 == 0 && ((uintptr_t)residual & 15) == 0), "gemm: residual misaligned");
-  VC_REQUIRE(!bias || ((uintptr_t)bias & 15) == 0, "gemm: bias misaligned");
+  // every other check and the whole choice of the launch form: the plan (the pointer VALUES only enter as alignment bits)
+  const auto off16 = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+  const unsigned misaligned = (off16(A) || off16(W) || off16(C) ? 1u : 0u) | (off16(residual) ? 2u : 0u) | (off16(bias) ? 4u : 0u);
+  GemmPlan pl;
+  const int rc = vc_gemm_plan(d, GemmOperands{bias != nullptr, residual != nullptr, aux_bf16 != nullptr, zout_bf16 != nullptr, ldaux, ldz, misaligned}, &pl);
+  if (rc != VITCAP_OK) return rc;
   GemmArgs a;
   a.A = (const bf16_t*)A;
   a.W = (const bf16_t*)W;
@@ -1215,142 +1053,30 @@ extern "C" int vitcap_gemm_ex(const void* A, const void* W, const float* bias, c
   a.lda = d->lda; a.ldw = d->ldw; a.ldc = d->ldc; a.ldr = d->ldr;
   a.row_group = d->row_group; a.out_group_rows = d->out_group_rows;
   a.out_row_off = d->out_row_off; a.res_periodic = d->res_periodic;
-  a.tiles_m = a.tiles_n = 0;
+  a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
+  a.n_big = pl.n_big; a.tiles_m_small = pl.tiles_m_small; a.group_n = pl.group_n;
   a.aux = (const bf16_t*)aux_bf16; a.ldaux = ldaux;
   a.colsum = d->colsum;
   a.zout = (bf16_t*)zout_bf16; a.ldz = ldz;
   a.split_k = 1; a.kt_per_split = 0; a.slab = 0;
+  if (pl.family != VITCAP_GEMM_FAMILY_SKINNY) {      // the skinny kernel takes its splits beside the block (SkinnyArgs)
+    a.split_k = pl.split_k; a.kt_per_split = pl.kt_per_split; a.slab = (size_t)pl.slab;
+  }
   a.live = d->live;
   a.rev = vc_tls_walk_rev ? 1 : 0;
   a.rowstat = (float*)d->rowstat;
   a.ln_g = a.ln_b = nullptr; a.ln_eps = 0.f; a.ln_out = nullptr; a.ln_out_f = nullptr; a.ln_cnt = nullptr;
-  VC_REQUIRE(!(aux_bf16 && d->act != VITCAP_ACT_NONE), "gemm: aux (gelu') epilogue needs act == none");
-  VC_REQUIRE(!zout_bf16 || d->act == VITCAP_ACT_GELU_ERF, "gemm: zout stores the GELU's derivative and needs act == gelu_erf");
-  VC_REQUIRE(known_tile_hint(d->tile_hint), "gemm: unknown tile_hint %d", d->tile_hint);
-  hipStream_t s = (hipStream_t)stream;
-  const int hint = d->tile_hint;       // the values are listed at vitcap_gemm_desc.tile_hint (include/vitcap_hip.h)
-  const int split_k = d->split_k > 1 ? d->split_k : 1;
-  const bool plain_rows = d->row_group == 0;
-  if (d->ln_out_bf16 || d->ln_out_f32) {
-    // LayerNorm of the finished rows: inside the kernel where the launch form has the last-arriver pass, a LayerNorm launch behind
-    // the GEMM otherwise -- the same row function either way, so the outputs do not depend on which
-    VC_REQUIRE(d->ln_gamma && d->ln_beta, "gemm(ln): ln_gamma / ln_beta missing");
-    VC_REQUIRE(d->N == 768 && d->ldc == 768 && d->out_dtype == VITCAP_OUT_F32 && d->act == VITCAP_ACT_NONE && plain_rows && split_k == 1 &&
-                   !aux_bf16 && !zout_bf16 && !d->rowstat && !d->colsum,
-               "gemm(ln): needs N == ldc == 768, fp32 output, no activation / row remap / split-K / training extras");
-    // in-kernel only on request (ln_counters given) and under tile_hint 5 (an fp32 output runs the 8-wave kernel there).  MEASURED A LOSS
-    // (docs/LAB_r01_r04.md 4.3: a row block's last arriver pulls its 786 KB back at ~20 GB/s, 40 us per block on one CU, against 31 us
-    // for the LayerNorm kernel over ALL rows on the whole chip): the engine does not ask for it
-    const bool fused = d->ln_counters && d->M >= 2048 && hint == 5;
-    if (fused) {
-      a.ln_g = d->ln_gamma; a.ln_b = d->ln_beta; a.ln_eps = d->ln_eps;
-      a.ln_out = (bf16_t*)d->ln_out_bf16; a.ln_out_f = d->ln_out_f32; a.ln_cnt = d->ln_counters;
-      return residual ? launch_256<VITCAP_ACT_NONE, 1, true, 4 | 512>(a, s, 0) : launch_256<VITCAP_ACT_NONE, 1, false, 4 | 512>(a, s, 0);
-    }
-    vitcap_gemm_desc d2 = *d;
-    d2.ln_out_bf16 = nullptr; d2.ln_out_f32 = nullptr;
-    const int rc = vitcap_gemm_ex(A, W, bias, residual, C, &d2, aux_bf16, ldaux, zout_bf16, ldz, stream);
-    if (rc != VITCAP_OK) return rc;
-    // the LayerNorm reads the rows the GEMM has just written: it walks them the other way round (common.h: vc_tls_walk_rev; only the
-    // engine ever sets the flag, and only there does this flip have an effect worth having)
-    const bool dir = vc_tls_walk_rev;
-    if (vc_tls_zigzag && d->M >= 2048) vc_tls_walk_rev = !dir;
-    const int rc2 = vitcap_layernorm_fwd((const float*)C, d->ldc, d->ln_gamma, d->ln_beta, d->ln_eps, d->ln_out_bf16, d->ln_out_f32, d->M, 768, stream);
-    vc_tls_walk_rev = dir;
-    return rc2;
+  if (pl.ln_fused) {
+    a.ln_g = d->ln_gamma; a.ln_b = d->ln_beta; a.ln_eps = d->ln_eps;
+    a.ln_out = (bf16_t*)d->ln_out_bf16; a.ln_out_f = d->ln_out_f32; a.ln_cnt = d->ln_counters;
   }
-  if (d->rowstat) {
-    VC_REQUIRE(d->out_dtype == VITCAP_OUT_F32 && d->act == VITCAP_ACT_NONE && !residual && plain_rows && split_k == 1 && !aux_bf16 && !zout_bf16,
-               "gemm(rowstat): fp32 output, no activation / residual / split-K");
-    return launch_rowstat(a, s);
-  }
-  if (d->colsum) {
-    // column sums of the finished bf16 output ride in the 256x256 kernel's 16-byte-store epilogue (training extras build)
-    VC_REQUIRE(d->out_dtype == VITCAP_OUT_BF16 && !residual && plain_rows && split_k == 1 && d->M >= 2048 && d->N % 8 == 0 && d->ldc % 8 == 0 &&
-                   (!aux_bf16 || ldaux % 8 == 0) && (!zout_bf16 || ldz % 8 == 0) && d->act != VITCAP_ACT_TANH,
-               "gemm(colsum): needs bf16 output, no residual / row remap / split-K, M >= 2048, N, ldc (ldaux, ldz) multiples of 8");
-    // the persistent 4-wave kernel's register epilogue carries the column sums too (round 5), on request only (tile_hint 42): inside
-    // the training step it is slower than the 8-wave kernel (profiles/r05_train_extras_ab.txt: 52.2 against 52.5 / 53.1 ms per step)
-    if (hint == 42 && vc_4w_supports(a, d->act))
-      return vc_dispatch_4w(a, d->act, d->out_dtype, s, 2);
-    return dispatch_256<4>(a, d->act, d->out_dtype, s, 0);
-  }
-  if (hint == 23 || hint == 24) {
-    // the resident form's contract on the 4-stage ring: K > 768 -> K/768 raw fp32 partial slabs in C = [K/768][M][ldc], one per
-    // 768-long k range (blockIdx.y); 64x32 (23) or 32x32 (24) tiles
-    VC_REQUIRE(d->K % 768 == 0 && d->K > 768 && plain_rows && !aux_bf16 && !zout_bf16 && d->out_dtype == VITCAP_OUT_F32 && !bias && !residual &&
-                   d->act == VITCAP_ACT_NONE,
-               "gemm(ring slabs): needs K a multiple of 768 above it, plain rows, raw fp32 slabs (no bias / residual / activation)");
-    a.split_k = d->K / 768;
-    a.kt_per_split = 12;
-    a.slab = (size_t)d->M * d->ldc;
-    return hint == 23 ? dispatch<2, 1>(a, VITCAP_ACT_NONE, 1, s) : dispatch<1, 1>(a, VITCAP_ACT_NONE, 1, s);
-  }
-  if (hint == 20 || hint == 21 || hint == 22) {
-    // resident whole-K form (decode-step shapes); K > 768 -> K/768 fp32 partial slabs in C = [K/768][M][ldc]
-    VC_REQUIRE(d->K % 768 == 0 && plain_rows && !aux_bf16 && !zout_bf16, "gemm(resident): needs K %% 768 == 0, plain rows, no training extras");
-    VC_REQUIRE(d->K == 768 || (d->out_dtype == VITCAP_OUT_F32 && !bias && !residual && d->act == VITCAP_ACT_NONE),
-               "gemm(resident): K > 768 writes raw fp32 partial slabs");
-    if (hint == 20) return dispatch_resident<2, 1>(a, d->act, d->out_dtype, s);     // 64 x 32 tiles
-    if (hint == 21) return dispatch_resident<1, 1>(a, d->act, d->out_dtype, s);     // 32 x 32
-    return dispatch_resident<1, 2>(a, d->act, d->out_dtype, s);                     // 32 x 64
-  }
-  if (split_k > 1 && d->M > 256) {
-    // weight-gradient shape: few output tiles, very long K -> 128x128 tiles with ragged split-K into fp32 slabs
-    VC_REQUIRE(d->out_dtype == VITCAP_OUT_F32 && plain_rows && !aux_bf16 && !zout_bf16, "gemm: split-K writes fp32 partial slabs only");
-    const int nk = d->K / 64;
-    a.split_k = split_k;
-    a.kt_per_split = (nk + split_k - 1) / split_k;
-    a.slab = (size_t)d->M * d->ldc;
-    return dispatch<4, 4>(a, VITCAP_ACT_NONE, 1, s);
-  }
-  if (split_k > 1) {
-    VC_REQUIRE(d->K % (128 * split_k) == 0, "gemm: K=%d not divisible into %d splits of multiples of 128", d->K, split_k);
-    VC_REQUIRE(d->out_dtype == VITCAP_OUT_F32 && plain_rows, "gemm: split-K writes fp32 partial slabs only");
-  }
-  // measured at B=64 (tools/decode_bench.py): without split-K the LDS-staged 64x64 kernel is ~2x faster than the
-  // register-fed one (7.4 vs 14.6 us for 128x2304x768), so the skinny kernel is used for split-K only.
-  if (split_k > 1 || hint == 4) {
-    VC_REQUIRE(d->K % 128 == 0 && plain_rows, "gemm(skinny): needs K %% 128 == 0 and no row remap");
-    return d->M <= 64 ? launch_skinny<2>(a, d->act, d->out_dtype, split_k, s)
-                      : launch_skinny<4>(a, d->act, d->out_dtype, split_k, s);
-  }
-  if (hint == 13) return dispatch<2, 1>(a, d->act, d->out_dtype, s);
-  if (hint == 14) return dispatch<1, 1>(a, d->act, d->out_dtype, s);
-  if (hint == 15) return dispatch<1, 2>(a, d->act, d->out_dtype, s);
-  // decode shapes (M = 2 x sequences): weights stream from HBM once, the kernel is latency-bound, so the smallest
-  // tiles (most workgroups, most bytes in flight) win: cold-weight 128x2304x768 takes 10.8 / 9.4 / 8.9 us with
-  // 64x64 / 64x32 / 32x32 tiles (tools/cold_gemm.py), against a ~4.5 us launch floor
-  if (hint == 0 && d->M <= 128) return dispatch<1, 1>(a, d->act, d->out_dtype, s);
-  if (hint == 1 || (hint == 0 && d->M <= 256)) return dispatch<2, 2>(a, d->act, d->out_dtype, s);
-  if (hint == 0 && d->act != VITCAP_ACT_TANH) {
-    // Auto tile choice for 256 < M: the tile whose grid costs least under a linear model fitted to tools/gemm_bench.py on the
-    // hot shapes (M = 577 .. 36928; N = 768 / 2304 / 3072; K = 768 / 3072; us).  64x64: 4 + W * c; 128x128: max(one tile, 9 + W * c);
-    // 256x256: ceil(W / 256) * one tile.  A 256x256 grid of 30 workgroups (N = 768 at 1..8 images) leaves 7/8 of the chip idle
-    // for a whole tile time (fc2 at 4 images: 65 us, against 28 us on 64x64 tiles); one image's encoder 3.3 -> 2.6 ms.
-    const float kf = d->K > 768 ? (float)(d->K - 768) / 2304.f : 0.f;
-    const auto grid = [&](int t) { return (float)(((d->M + t - 1) / t) * ((d->N + t - 1) / t)); };
-    const float t64 = 4.f + grid(64) * (0.0165f + kf * 0.0385f);
-    const float t128 = fmaxf(16.f + kf * 26.f, 9.f + grid(128) * (0.0375f + kf * 0.0745f));
-    const float t256 = d->M >= 2048 ? ceilf(grid(256) / 256.f) * (23.f + kf * 57.f) : 1e30f;
-    if (t64 < t128 && t64 < t256) return dispatch<2, 2>(a, d->act, d->out_dtype, s);
-    if (t128 < t256) return dispatch<4, 4>(a, d->act, d->out_dtype, s);
-  }
-  if (hint == 2 || (hint == 0 && (d->M < 2048 || d->act == VITCAP_ACT_TANH)))
-    return dispatch<4, 4>(a, d->act, d->out_dtype, s);
-  if (hint >= 40 && hint <= 42) {      // 4 waves x 128x128, one wave per SIMD (gemm4w.hip): 40 LDS epilogue, 41 register epilogue, 42 persistent
-    VC_REQUIRE(!(aux_bf16 || zout_bf16 || d->colsum) || (hint == 42 && d->out_dtype == VITCAP_OUT_BF16),
-               "gemm(4-wave): aux / zout / colsum need the persistent form (tile_hint 42) and a bf16 output");
-    return vc_dispatch_4w(a, d->act, d->out_dtype, s, hint - 40);
-  }
-  if (hint == 30) return dispatch_256<4>(a, d->act, d->out_dtype, s, 3);    // every tile 192 x 256 (tile-cost measurement)
-  if (hint == 31) return dispatch_256<4>(a, d->act, d->out_dtype, s, 2);    // every tile 128 x 256
-  if (hint == 32) return dispatch_256<4>(a, d->act, d->out_dtype, s, 0);    // 256 x 256 tiles only (no short tail tiles)
-  if (hint == 33) return dispatch_256<4>(a, d->act, d->out_dtype, s, -1);   // 256-row tiles + the planned short tiles
-  // tile_hint 0 (M >= 2048) or 5: the 4-wave kernel where large_gemm_form says so and the launch carries none of the training extras
-  // (aux / zout / colsum: the 8-wave kernel's EXTRAS build unless tile_hint 42 asks otherwise), the 8-wave 256x256 kernel otherwise
-  const int form = large_gemm_form(d->M, hint, !(d->out_dtype == VITCAP_OUT_F32 || residual));
-  if (form >= 0 && !(aux_bf16 || zout_bf16 || d->colsum) && vc_4w_supports(a, d->act)) return vc_dispatch_4w(a, d->act, d->out_dtype, s, form);
-  // hint 5: 256 x 256 tiles only; auto: short tiles in the last round where the plan wins
-  return dispatch_256<4>(a, d->act, d->out_dtype, s, hint == 5 ? 0 : -1);
+  const int rc1 = launch_plan(a, pl, (hipStream_t)stream);
+  if (rc1 != VITCAP_OK || !pl.ln_follows) return rc1;
+  // the LayerNorm reads the rows the GEMM has just written: it walks them the other way round (call_state.h: vc_tls_walk_rev; only the
+  // engine ever sets the flag, and only there does this flip have an effect worth having)
+  const bool dir = vc_tls_walk_rev;
+  if (vc_tls_zigzag && d->M >= 2048) vc_tls_walk_rev = !dir;
+  const int rc2 = vitcap_layernorm_fwd((const float*)C, d->ldc, d->ln_gamma, d->ln_beta, d->ln_eps, d->ln_out_bf16, d->ln_out_f32, d->M, 768, stream);
+  vc_tls_walk_rev = dir;
+  return rc2;
 }

@@ -19,8 +19,8 @@
 // tile, same operand roles), so results are bit-identical to it (tests/test_hip_ops.py::test_gemm_4wave_bit_identical).
 #include "common.h"
 #include "gemm_args.h"
+#include "gemm_plan.h"
 
-#include <atomic>
 #include <utility>
 
 namespace {
@@ -843,168 +843,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-// Tile height by launch: a launch of T equal tiles on C CUs costs ceil(T / C) tile times, and a (32 * MI)-row tile costs about
-// (fixed + MI) units -- 435 tiles of 256 rows (M = 36928, N = 768) pay 2 rounds for 1.7 rounds of work, 495 tiles of 224 rows pay
-// 2 rounds of 7/8 the length; 1305 (N = 2304) pay 6, 1485 of 224 rows pay 6 x 7/8.  The kernel is the same code for every MI (the
-// wave tile is MI x 8 MFMA tiles, k order per output element unchanged: bit-identical results whatever the height).
-int device_cus() {
-  static const int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      return prop.multiProcessorCount;
-    return 256;
-  }();
-  return n;
-}
-// workgroups of the persistent grid = CUs it occupies (512 registers per lane: one workgroup owns a CU), less the CUs (a multiple of
-// 8: the XCDs stay balanced) that vitcap_gemm_reserve_cus leaves to whatever else runs on the GPU while a collective is in flight
-std::atomic<int> g_reserve_cus{0};
-int persistent_cus() {
-  const int n = device_cus() - g_reserve_cus.load(std::memory_order_relaxed);
-  return n >= 8 ? n : 8;
-}
+// ---- launchers: form, tile height and variant are the plan's (gemm_plan.cpp: plan_4w); one call site per kernel, because VC_FUNC_SMEM
+// remembers per call site that the attribute was set -------------------------------------------------------------------------------
+// every expansion is a call site of its own (VC_FUNC_SMEM) and returns from the launcher
+#define LAUNCH_4W(kern_, smem_)                                               \
+  do {                                                                        \
+    auto kern = kern_;                                                        \
+    VC_FUNC_SMEM(kern, smem_);                                                \
+    VC_LAUNCH_GEMM(kern, dim3(pl.grid[0]), dim3(256), smem_, s, p);           \
+    VC_LAUNCH_CHECK("gemm_nt_4w");                                            \
+    return VITCAP_OK;                                                         \
+  } while (0)
 
-int pick_mi(int M, int tiles_n, int form) {
-  const int n_cu = form == 2 ? persistent_cus() : device_cus();
-  const float fixed = form == 2 ? 0.3f : 0.9f;       // per-tile cost that does not shrink with the tile: pipeline fill, barriers' skew, W traffic
-  int best = 8;
-  float best_c = 1e30f;
-  for (int mi = 8; mi >= 6; --mi) {
-    const long long tiles = (long long)((M + 32 * mi - 1) / (32 * mi)) * tiles_n;
-    const float c = (float)((tiles + n_cu - 1) / n_cu) * (fixed + (float)mi);
-    if (c < best_c * 0.985f) { best_c = c; best = mi; }      // a shorter tile must win 1.5 % to be taken
-  }
-  return best;
-}
-
-// form: 0 = one tile per workgroup + LDS epilogue, 1 = one tile per workgroup + register epilogue, 2 = persistent
 template <int ACT, int OUT_F32, bool HAS_RES, int MI>
-int launch_4w_mi(GemmArgs& p, hipStream_t s, int form) {
-  p.tiles_m = (p.M + 32 * MI - 1) / (32 * MI);
-  p.n_big = p.tiles_m * p.tiles_n;
-  if (form == 2) {
-    const int n_cu = persistent_cus();
-    const bool extras = p.aux || p.zout || p.colsum;        // training extras: the bf16 register epilogue's second form (vc_4w_supports)
-    constexpr int smem = (OUT_F32 || HAS_RES) ? SMEM_4WP : 2 * BUF_BYTES;
-    const int grid = p.n_big < n_cu ? p.n_big : n_cu;
-    // one call site per kernel: VC_FUNC_SMEM remembers per call site that the attribute was set
-    bool launched = false;
-    if constexpr (!OUT_F32 && !HAS_RES) {
-      if (extras) {
-        auto kern = gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, true>;
-        VC_FUNC_SMEM(kern, smem);
-        VC_LAUNCH_GEMM(kern, dim3(grid), dim3(256), smem, s, p);
-        launched = true;
-      }
-      // A-panel prefetch one tile ahead (round 5's measured probe, shipped in round 6): from ~64k rows on the A panel streams from
-      // HBM and the same loop takes 32-37k instead of 25.4k cycles per tile; whole rows of the NEXT tile's panel, split over the column
-      // siblings, requested one per k-tile bring it to 29.7k (qkv +3.6 %, fc1 +2.1 % wall at M = 295 424, docs/LAB_r05.md section 1).
-      // Below the threshold the operands are cache-resident and the extra instruction only costs (+0.8 % loop cycles): plain form.
-      // deferred stores (round 6): the upper half of every wave tile's stores ride behind the next tile's first k-tiles.  Measured
-      // (profiles/r06_deferred_stores.txt): the epilogue shrinks as priced (qkv 8.7k -> 6.2k cycles per tile), but with ONE wave per
-      // SIMD a store's issue (~150 cycles each) stalls the wave wherever it stands, so the next tile's loop pays what the epilogue
-      // saved (25.3k -> 27.2k + 0.7k): a tie without an activation (qkv 138.9 -> 138.3 us, the training step 49.63 -> 49.23 ms),
-      // a loss with GELU (fc1 211.8 -> 221.0 us: its stores were already hidden behind the activation's arithmetic) and from 64k rows
-      // on, where the parked stores compete with the A panel's HBM stream (qkv 1 080 -> 1 153 us; B = 512 pipeline 4 160 -> 4 064
-      // img/s).  Policy: plain bf16 outputs below 64k rows.  VITCAP_GEMM_4W_DEFER: 0 = never, 1 = that policy (default), 2 = always.
-      {
-        const char* de = getenv("VITCAP_GEMM_4W_DEFER");      // read per launch (not cached): the parity test switches it
-        const int defer = de ? atoi(de) : 1;
-        const bool want = defer == 2 || (defer == 1 && ACT == VITCAP_ACT_NONE && p.M < 65536);
-        if (!launched && want && p.K / 64 >= Park<MI>::NP + 3) {
-          auto kern = gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, false, false, true>;
-          VC_FUNC_SMEM(kern, smem);
-          VC_LAUNCH_GEMM(kern, dim3(grid), dim3(256), smem, s, p);
-          launched = true;
-        }
-      }
-      if constexpr (MI == 8) {
-        if (!launched && p.M >= 65536 && p.tiles_m > 1) {
-          auto kern = gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, false, true>;
-          constexpr int smem_pf = 2 * BUF_BYTES + 1024;
-          VC_FUNC_SMEM(kern, smem_pf);
-          VC_LAUNCH_GEMM(kern, dim3(grid), dim3(256), smem_pf, s, p);
-          launched = true;
-        }
-      }
+int launch_4w_mi(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  constexpr int smem = (OUT_F32 || HAS_RES) ? SMEM_4WP : 2 * BUF_BYTES, smem_pf = 2 * BUF_BYTES + 1024;
+  const int want = pl.variant == VITCAP_GEMM_4W_PREFETCH ? smem_pf : smem;
+  VC_REQUIRE(pl.lds_bytes == want, "gemm(4-wave): the plan's LDS size %d is not the kernel's %d", pl.lds_bytes, want);
+  if (pl.form != 2) LAUNCH_4W((gemm_nt_4w_kernel<ACT, OUT_F32, HAS_RES, 1, MI>), smem);
+  if constexpr (!OUT_F32 && !HAS_RES) {      // the bf16 register epilogue's variants (gemm_plan.cpp: plan_4w)
+    if (pl.variant == VITCAP_GEMM_4W_EXTRAS) LAUNCH_4W((gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, true>), smem);
+    if (pl.variant == VITCAP_GEMM_4W_DEFER) LAUNCH_4W((gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, false, false, true>), smem);
+    if constexpr (MI == 8) {
+      if (pl.variant == VITCAP_GEMM_4W_PREFETCH) LAUNCH_4W((gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI, false, true>), smem_pf);
     }
-    if (!launched) {
-      auto kern = gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI>;
-      VC_FUNC_SMEM(kern, smem);
-      VC_LAUNCH_GEMM(kern, dim3(grid), dim3(256), smem, s, p);
-    }
-  } else {
-    auto kern = gemm_nt_4w_kernel<ACT, OUT_F32, HAS_RES, 1, MI>;
-    constexpr int smem = (OUT_F32 || HAS_RES) ? SMEM_4WP : 2 * BUF_BYTES;
-    VC_FUNC_SMEM(kern, smem);
-    VC_LAUNCH_GEMM(kern, dim3(p.n_big), dim3(256), smem, s, p);
   }
-  VC_LAUNCH_CHECK("gemm_nt_4w");
-  return VITCAP_OK;
+  VC_REQUIRE(pl.variant == VITCAP_GEMM_4W_PLAIN, "gemm(4-wave): no build of variant %d for this epilogue / tile height", pl.variant);
+  LAUNCH_4W((gemm_nt_4wp_kernel<ACT, OUT_F32, HAS_RES, MI>), smem);
 }
 
 template <int ACT, int OUT_F32, bool HAS_RES>
-int launch_4w(const GemmArgs& a, hipStream_t s, int form) {
-  GemmArgs p = a;
-  p.tiles_n = (a.N + 255) / 256;
-  p.group_n = vc_tile_group_n(p.tiles_n);
-  p.tiles_m_small = 0;
-  // the register epilogue's bf16 stores are 16 bytes wide
-  const bool regs_ok = OUT_F32 || HAS_RES || ((a.N & 7) == 0 && (a.ldc & 7) == 0);
-  if (form != 0 && !regs_ok) form = 0;
-  // the persistent pipeline's tile body needs three k-tiles; its epilogues address plain rows of whole 256-column tiles
-  if (form == 2 && (a.K < 192 || (a.N & 255) != 0 || a.row_group != 0 || (!OUT_F32 && (a.ldc & 7) != 0))) form = 1;
-  if (form == 0) {
-    p.tiles_m = (a.M + 255) / 256;
-    p.n_big = p.tiles_m * p.tiles_n;
-    auto kern = gemm_nt_4w_kernel<ACT, OUT_F32, HAS_RES, 0, 8>;
-    VC_FUNC_SMEM(kern, SMEM_4W);
-    VC_LAUNCH_GEMM(kern, dim3(p.n_big), dim3(256), SMEM_4W, s, p);
-    VC_LAUNCH_CHECK("gemm_nt_4w");
-    return VITCAP_OK;
+int launch_4w(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+  if (pl.form == 0) {
+    VC_REQUIRE(pl.lds_bytes == SMEM_4W && pl.mi == 8, "gemm(4-wave): the plan's LDS size %d is not the kernel's %d", pl.lds_bytes, SMEM_4W);
+    LAUNCH_4W((gemm_nt_4w_kernel<ACT, OUT_F32, HAS_RES, 0, 8>), SMEM_4W);
   }
-  switch (pick_mi(a.M, p.tiles_n, form)) {
-    case 7: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 7>(p, s, form);
-    case 6: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 6>(p, s, form);
-    default: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 8>(p, s, form);
+  switch (pl.mi) {
+    case 7: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 7>(p, pl, s);
+    case 6: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 6>(p, pl, s);
+    default: return launch_4w_mi<ACT, OUT_F32, HAS_RES, 8>(p, pl, s);
   }
 }
+#undef LAUNCH_4W
 
 }  // namespace
 
-extern "C" int vitcap_gemm_reserve_cus(int cus) {
-  if (cus < 0) cus = 0;
-  cus = (cus + 7) & ~7;
-  return g_reserve_cus.exchange(cus, std::memory_order_relaxed);
-}
-
-int vc_4w_pick_mi(int M, int tiles_n, int form) { return form == 0 ? 8 : pick_mi(M, tiles_n, form); }
-
-bool vc_4w_supports(const GemmArgs& a, int act) {
-  if (a.aux || a.zout || a.colsum) {
-    // training extras: the PERSISTENT form's bf16 register epilogue only (no downgrade of the form inside launch_4w: the caller checks
-    // that the persistent form was chosen) -- plain rows, whole 256-column tiles, 16-byte aligned rows of every operand
-    return !a.res && !a.rowstat && !a.live && a.split_k <= 1 && a.K >= 192 && (a.N & 255) == 0 && a.row_group == 0 && (a.ldc & 7) == 0 &&
-           (!a.aux || (a.ldaux & 7) == 0) && (!a.zout || (a.ldz & 7) == 0) && a.M >= 2048 &&
-           (act == VITCAP_ACT_NONE || act == VITCAP_ACT_GELU_ERF);
-  }
-  // a.live (decode loops: early exit once every sequence has finished) is honoured by the 8-wave kernels only: such launches stay there
-  return !a.aux && !a.zout && !a.colsum && !a.rowstat && !a.live && a.split_k <= 1 && a.K >= 128 &&
-         (act == VITCAP_ACT_NONE || act == VITCAP_ACT_GELU_ERF);
-}
-
-int vc_dispatch_4w(const GemmArgs& a, int act, int out_f32, hipStream_t s, int form) {
-  VC_REQUIRE(vc_4w_supports(a, act), "gemm(4-wave): unsupported options (training extras / split-K / activation %d / K < 128)", act);
-  const bool res = a.res != nullptr;
-#define CASE(ACT_, OUT_)              \
-  if (act == ACT_ && out_f32 == OUT_) \
-    return res ? launch_4w<ACT_, OUT_, true>(a, s, form) : launch_4w<ACT_, OUT_, false>(a, s, form);
+int vc_launch_4w(const GemmArgs& p, const GemmPlan& pl, hipStream_t s) {
+#define CASE(ACT_, OUT_)                      \
+  if (pl.act == ACT_ && pl.out_f32 == OUT_)   \
+    return pl.has_res ? launch_4w<ACT_, OUT_, true>(p, pl, s) : launch_4w<ACT_, OUT_, false>(p, pl, s);
   CASE(VITCAP_ACT_NONE, 0)
   CASE(VITCAP_ACT_NONE, 1)
   CASE(VITCAP_ACT_GELU_ERF, 0)
   CASE(VITCAP_ACT_GELU_ERF, 1)
 #undef CASE
-  vitcap_set_error("gemm(4-wave): unsupported act %d / out %d", act, out_f32);
+  vitcap_set_error("gemm(4-wave): no build for act %d / out %d", pl.act, pl.out_f32);
   return VITCAP_EINVAL;
 }

@@ -58,11 +58,6 @@ struct GemmArgs {
     }                                                                                                              \
   } while (0)
 
-// width (in 256-column tiles) of the column groups the 256x256 kernels walk (gemm.hip)
-int vc_tile_group_n(int tiles_n);
-// the 4-wave / 512-register 256x256 kernel (gemm4w.hip); mix = 0: 256-row tiles only
-// form: 0 = one tile per workgroup + LDS epilogue, 1 = one tile per workgroup + register epilogue, 2 = persistent
-int vc_dispatch_4w(const GemmArgs& a, int act, int out_f32, hipStream_t s, int form);
-bool vc_4w_supports(const GemmArgs& a, int act);
-// m-tiles of 16 rows per wave (8 / 7 / 6 -> 256- / 224- / 192-row tiles) the 4-wave kernel picks for a launch
-int vc_4w_pick_mi(int M, int tiles_n, int form);
+
+// the 4-wave / 512-register 256x256 kernel (gemm4w.hip), launched as the plan says (gemm_plan.h)
+int vc_launch_4w(const GemmArgs& p, const vitcap_gemm_plan_info& pl, hipStream_t s);

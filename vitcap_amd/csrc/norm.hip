@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* __restri
                                                            const float* __restrict__ beta, float eps,
                                                            bf16_t* __restrict__ yb, float* __restrict__ yf, int M, int rev) {
   const int lane = threadIdx.x & 63;
-  // rev: workgroups are dispatched in blockIdx order -- the rows are then visited last-to-first (common.h: vc_tls_walk_rev)
+  // rev: workgroups are dispatched in blockIdx order -- the rows are then visited last-to-first (call_state.h: vc_tls_walk_rev)
   const int row = (rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   const float* xr = x + (size_t)row * ldx;
