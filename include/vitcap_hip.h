@@ -337,6 +337,20 @@ int vitcap_greedy_step_forced(const float* logits, int ldl, int V, int64_t* ids,
 int vitcap_score_rows(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0, int n_rows,
                       int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, float* sum_lp, float* cnt,
                       float* token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* logprob_out, void* stream);
+/* What the [MASK] probe saw in the vocabulary, for the same probe rows: rows, ranges, live rows, the scored token f (the last-column
+ * rule included) and the expression of the log-probs as vitcap_score_rows.  Order of a row's entries: i before j iff x[i] > x[j], or
+ * x[i] == x[j] and i < j (float comparison: -0 == +0).  With m = max x, S = sum exp(x - m), T = sum exp(x - m) (x - m), per live row:
+ *   alt_ids  int32 [n_caps][max_len][k]  the first k indices of that order, k = 1..16 (V >= k)
+ *   alt_lp   fp32  [n_caps][max_len][k]  (x[id] - m) - log S; where alt_ids == f, vitcap_score_rows' token_logprobs bit for bit
+ *   rank     int32 [n_caps][max_len]     the number of entries that come before f (0: f is the argmax)
+ *   entropy  fp32  [n_caps][max_len]     log S - T / S, in nats (logits are finite by contract); log S is taken as log1p(S - 1) with
+ *                                        S - 1 summed without the maximum's own term, so a confident row keeps its relative accuracy
+ * Rows behind a caption's end get alt_ids = rank = -1, alt_lp = entropy = 0.  Only the positions of the rows [rows0, rows0 + n_rows)
+ * are written: column 0 and the uncovered rows are the caller's to initialise.  One workgroup per row reads the row once.
+ * Enqueue-only. */
+int vitcap_score_rows_alts(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0,
+                           int n_rows, int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, int k, int32_t* alt_ids,
+                           float* alt_lp, int32_t* rank, float* entropy, void* stream);
 
 /* Embeddings of the predicted tag tokens written over the last 50 text slots (ViTSplitCLSEmbModel.forward,
  * modeling_bert.py:1435-1489, encode_tag_to_embedding 1381-1406): rows (b, j < n), token = tag_ids[b][j] (int64 [B][50]; slot 49
@@ -781,6 +795,27 @@ int vitcap_engine_explain(vitcap_engine* e, const void* image, int image_is_bf16
                           size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok,
                           void* score_ws, size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
                           int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* stream);
+/* "What else could the model have said here": the one-pass scoring pass, which also keeps what it saw in the vocabulary at every
+ * position (vitcap_score_rows_alts on every chunk of the vocabulary GEMM, in one kernel that does vitcap_score_rows' job for the chunk
+ * too).  Arguments, refusals and results as vitcap_engine_score_text / vitcap_engine_score -- the scores, per-token log-probs and ids
+ * are bit-identical to those calls' -- plus
+ *   k                  1..16 alternatives per position
+ *   alt_ids, alt_lp    device, int32 / fp32 [B*caps][max_length][k]
+ *   rank, entropy      device, int32 / fp32 [B*caps][max_length]
+ * as vitcap_score_rows_alts defines them; column 0 and the positions behind a caption's end hold alt_ids = rank = -1 and
+ * alt_lp = entropy = 0 (the call sets all four arrays to that pattern first).  Refusals in this order: the options, the batch, k
+ * outside 1..16 or a null output array (VITCAP_EINVAL), io, workspace.  The score workspace is that of
+ * vitcap_engine_score_workspace_bytes: the results go straight to the caller's arrays. */
+int vitcap_engine_alternatives_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                    int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                                    size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                                    int64_t* out_last_tok, int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy,
+                                    void* stream);
+int vitcap_engine_alternatives(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                               void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
+                               float* alt_lp, int32_t* rank, float* entropy, void* stream);
 /* copies the tag head's outputs of the last encode on this workspace (either pointer may be NULL) */
 int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                        int64_t* tag_topk_out, void* stream);

@@ -213,6 +213,8 @@ _SIGS = {
     'vitcap_attn_probe_maps': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp]),
     'vitcap_score_rows': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp,
                                     vp, vp, vp]),
+    'vitcap_score_rows_alts': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                         vp, vp, vp, vp, vp]),
     'vitcap_row_topk_pieces': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     'vitcap_beam_init': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'vitcap_beam_step': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -253,6 +255,10 @@ _SIGS = {
                                              vp, vp, C.c_int, C.c_int, vp]),
     'vitcap_engine_explain': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
                                         vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    'vitcap_engine_alternatives_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp,
+                                                  vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    'vitcap_engine_alternatives': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
+                                             vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     'vitcap_engine_tags': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, vp, vp, vp]),
     'vitcap_engine_graph_count': (C.c_int, [vp]),
     'vitcap_engine_tap': (vp, [vp, C.c_char_p, vp, C.c_int, C.POINTER(GenOpts)]),

@@ -2,6 +2,7 @@
 #include "common.h"
 #include "rng.h"
 #include "select.h"
+#include "score_row.h"
 
 namespace {
 
@@ -655,32 +656,16 @@ __global__ __launch_bounds__(256) void repetition_penalty_kernel(float* __restri
 // ---- one-pass caption scoring (vitcap_score_rows, include/vitcap_hip.h) -------------------------------------------------------
 // Probe row g of the grid = caption g / (L-1), position t = g % (L-1) + 1.  One 1024-thread workgroup per row, the reductions of
 // greedy_step_kernel; every row decides on its own whether its caption has ended before it (its ids are all known), so a launch
-// may cover any range of rows.
-struct ScoreArgs {
-  const int64_t* ids;        // [n_caps][L] the captions
-  const int64_t* last_tok;   // [n_caps] or null
-  float* tok_lp;             // [n_caps][L]
-  int64_t* out_ids;          // [n_caps][L]
-  int64_t* out_last;         // [n_caps] or null
-  float *sum_lp, *cnt, *logprob;      // [n_caps] (sum_lp / cnt may be null)
-  int L, eos, pad;
-  VcEosExtra eos_x;
-};
+// may cover any range of rows.  The row's rules live in score_row.h, shared with the alternatives kernel.
 __global__ __launch_bounds__(1024) void score_rows_kernel(const float* __restrict__ logits, int ldl, int V, ScoreArgs a, int rows0) {
   __shared__ float s_v[16], s_sum[16];
   __shared__ int s_i[16];
-  const int tid = threadIdx.x, g = rows0 + blockIdx.x;
-  const int b = g / (a.L - 1), t = g - b * (a.L - 1) + 1;
+  const int tid = threadIdx.x;
+  int b, t;
+  score_row_place(rows0 + blockIdx.x, a.L, b, t);
   const int64_t* cap = a.ids + (size_t)b * a.L;
-  bool ended = false;                      // an EOS id strictly before position t
-  for (int j = 1; j < t; ++j) ended = ended || vc_is_eos((int)cap[j], a.eos, a.eos_x);
-  const size_t o = (size_t)b * a.L + t;
-  if (ended) {                             // behind the end: nothing is counted (the stepwise loop's skip_finished)
-    if (tid == 0) {
-      a.tok_lp[o] = 0.f;
-      a.out_ids[o] = a.pad;
-      if (t == a.L - 1 && a.out_last) a.out_last[b] = a.pad;
-    }
+  if (score_row_ended(cap, t, a.eos, a.eos_x)) {      // behind the end: nothing is counted
+    if (tid == 0) score_row_write_dead(a, b, t);
     return;
   }
   const float* row = logits + (size_t)blockIdx.x * ldl;
@@ -688,23 +673,11 @@ __global__ __launch_bounds__(1024) void score_rows_kernel(const float* __restric
   for (int i = tid; i < V; i += 1024) best.offer(row[i], i);
   best = block_pick<16>(best, {s_v, s_i, nullptr, nullptr});
   float se = 0.f;
-  for (int i = tid; i < V; i += 1024) se += expf(row[i] - best.v);
+  for (int i = tid; i < V; i += 1024) se += score_row_term(row[i], best.v);
   const float tot = block_sum<16>(se, s_sum);
   if (tid != 0) return;
-  const int64_t given = cap[t];
-  int f = given >= 0 && given < (int64_t)V ? (int)given : best.i;
-  const bool last = t == a.L - 1;
-  if (last && given == (int64_t)a.eos) {   // the max-length rule's [SEP], not a choice: the caller's token, or the row's argmax
-    const int64_t lt = a.last_tok ? a.last_tok[b] : -1;
-    f = lt >= 0 && lt < (int64_t)V ? (int)lt : best.i;
-  }
-  a.tok_lp[o] = (row[f] - best.v) - logf(tot);
-  int64_t outtok = f;
-  if (last) {
-    if (a.out_last) a.out_last[b] = f;
-    if (!vc_is_eos(f, a.eos, a.eos_x)) outtok = a.eos;      // modeling_utils.py:870-871
-  }
-  a.out_ids[o] = outtok;
+  const int f = score_row_token(cap, a.last_tok, b, t, a.L, a.eos, V, best.i);
+  score_row_write(a, b, t, f, score_row_lp(row[f], best.v, tot));
 }
 // the captions whose last probe row lies in [rows0, rows0 + n_rows): their sums, taken in position order like the step loop's
 __global__ void score_finish_kernel(ScoreArgs a, int n_caps, int rows0, int n_rows) {
@@ -751,6 +724,12 @@ int vc_score_grid_ids(const int64_t* ids, int64_t* grid, int n_caps, int L, int 
   return VITCAP_OK;
 }
 
+int vc_score_finish(const ScoreArgs& a, int n_caps, int rows0, int n_rows, void* stream) {
+  hipLaunchKernelGGL(score_finish_kernel, dim3((n_caps + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, n_caps, rows0, n_rows);
+  VC_LAUNCH_CHECK("score_rows (sums)");
+  return VITCAP_OK;
+}
+
 extern "C" int vitcap_score_rows(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0,
                                  int n_rows, int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, float* sum_lp,
                                  float* cnt, float* token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* logprob_out,
@@ -763,9 +742,7 @@ extern "C" int vitcap_score_rows(const float* logits, int ldl, int V, const int6
               VcEosExtra{{eos_extra ? eos_extra[0] : -1, eos_extra ? eos_extra[1] : -1, eos_extra ? eos_extra[2] : -1}}};
   hipLaunchKernelGGL(score_rows_kernel, dim3(n_rows), dim3(1024), 0, (hipStream_t)stream, logits, ldl, V, a, rows0);
   VC_LAUNCH_CHECK("score_rows");
-  hipLaunchKernelGGL(score_finish_kernel, dim3((n_caps + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, n_caps, rows0, n_rows);
-  VC_LAUNCH_CHECK("score_rows (sums)");
-  return VITCAP_OK;
+  return vc_score_finish(a, n_caps, rows0, n_rows, stream);
 }
 
 extern "C" int vitcap_repetition_penalty(float* logits, int ldl, int V, const int64_t* ids, int ld_ids, int t, float penalty,

@@ -1080,9 +1080,28 @@ int check_maps(const Maps& m) {
   return VITCAP_OK;
 }
 
+// Token alternatives of the probe rows (vitcap_engine_alternatives*): off for the scoring and the explain entry points.
+struct Alts {
+  int k = 0;
+  int32_t* ids = nullptr;    // the caller's [NC][L][k]
+  float* lp = nullptr;       // [NC][L][k]
+  int32_t* rank = nullptr;   // [NC][L]
+  float* entropy = nullptr;  // [NC][L]
+  bool on() const { return k > 0; }
+};
+
+int check_alts(const Alts& a) {
+  if (a.k < 1 || a.k > 16) { vitcap_set_error("engine_alternatives: k must be 1..16 (got %d)", a.k); return VITCAP_EINVAL; }
+  if (!a.ids || !a.lp || !a.rank || !a.entropy) {
+    vitcap_set_error("engine_alternatives: null alt_ids / alt_lp / rank / entropy");
+    return VITCAP_EINVAL;
+  }
+  return VITCAP_OK;
+}
+
 // reads lo.dqkv[0..3] of `ws` (the visual caches of the prefill) and nothing else of it
 int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, const ScoreLayout& sl, char* sw,
-                 const ScoreIO& io, void* s, const Maps& mp = Maps()) {
+                 const ScoreIO& io, void* s, const Maps& mp = Maps(), const Alts& al = Alts()) {
   hipStream_t st = (hipStream_t)s;
   const int L = sl.L, R = sl.R, K = sl.K;
   const int NC = (int)sl.NC, M = (int)sl.M, P = (int)sl.P;
@@ -1117,12 +1136,23 @@ int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout
   CK(q.gemm(sw + sl.hd_in, D, w.cls.dense_w, w.cls.dense_b, nullptr, 0, sw + sl.hd_f, D, P, D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_F32));
   CK(vitcap_layernorm_fwd(sl.hd_f.at<float>(sw), D, w.cls.ln_g, w.cls.ln_b, 1e-12f, sw + sl.hd_b, nullptr, P, D, s));
   float* tok_lp = io.out_tok_lp ? io.out_tok_lp : sl.tok_lp.at<float>(sw);
+  if (al.on()) {      // the dead pattern once: column 0 and whatever no launch covers; the chunks' launches write the rest
+    const size_t n = (size_t)NC * L;
+    HIPCK(hipMemsetAsync(al.ids, 0xff, n * al.k * 4, st), "engine_alternatives: alt_ids clear");
+    HIPCK(hipMemsetAsync(al.rank, 0xff, n * 4, st), "engine_alternatives: rank clear");
+    HIPCK(hipMemsetAsync(al.lp, 0, n * al.k * 4, st), "engine_alternatives: alt_lp clear");
+    HIPCK(hipMemsetAsync(al.entropy, 0, n * 4, st), "engine_alternatives: entropy clear");
+  }
   for (int r0 = 0; r0 < P; r0 += (int)sl.CH) {
     const int n = P - r0 < (int)sl.CH ? P - r0 : (int)sl.CH;
     CK(q.gemm(sl.hd_b.at<char>(sw, (size_t)r0), D, w.cls.dec_w, w.cls.dec_b, nullptr, 0, sw + sl.logits, VP, n, VP, D, VITCAP_ACT_NONE,
               VITCAP_OUT_F32));
-    CK(vitcap_score_rows(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
-                         nullptr, nullptr, tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, s));
+    if (al.on())      // one kernel does vitcap_score_rows' job too: the 250 MB chunk is read once
+      CK(vc_score_rows_alts(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
+                            tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, al.k, al.ids, al.lp, al.rank, al.entropy, s));
+    else
+      CK(vitcap_score_rows(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
+                           nullptr, nullptr, tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, s));
   }
   return VITCAP_OK;
 }
@@ -1137,15 +1167,17 @@ extern "C" size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image,
 
 namespace {
 
-// The four entry points of the one-pass pass: every refusal in one order -- options, batch, maps (when asked for), io, workspace --
-// then, with an image, encode + prefill, then score_locked.  mp: the maps description of the explain pair, null for the scoring pair.
+// The six entry points of the one-pass pass: every refusal in one order -- options, batch, maps / alternatives (when asked for), io,
+// workspace -- then, with an image, encode + prefill, then score_locked.  mp: the maps description of the explain pair, al: the
+// alternatives description of the alternatives pair; both null for the scoring pair.
 int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool encode, int B, const vitcap_gen_opts* opts, void* workspace,
                 size_t workspace_bytes, int caps_per_image, const ScoreIO& io, void* score_ws, size_t score_ws_bytes, const Maps* mp,
-                void* s) {
+                void* s, const Alts* al = nullptr) {
   const vitcap_gen_opts o = opts_or_default(opts);
   CK(check_score(o, caps_per_image));
-  if (B <= 0) { vitcap_set_error("%s: bad batch", mp ? "engine_explain" : "engine_score"); return VITCAP_EINVAL; }
+  if (B <= 0) { vitcap_set_error("%s: bad batch", mp ? "engine_explain" : al ? "engine_alternatives" : "engine_score"); return VITCAP_EINVAL; }
   if (mp) CK(check_maps(*mp));
+  if (al) CK(check_alts(*al));
   const ScoreLayout sl(B, caps_per_image, o.max_length);
   CK(check_score_io(io, sl, score_ws, score_ws_bytes));
   Layout lo;
@@ -1156,7 +1188,13 @@ int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool enc
     CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
     CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
   }
-  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps());
+  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps(), al ? *al : Alts());
+}
+
+Alts alts_of(int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy) {
+  Alts al;
+  al.k = k; al.ids = alt_ids; al.lp = alt_lp; al.rank = rank; al.entropy = entropy;
+  return al;
 }
 
 Maps maps_of(float* maps, int per_head, int layer_mask) {
@@ -1201,6 +1239,28 @@ extern "C" int vitcap_engine_explain(vitcap_engine* e, const void* image, int im
   const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
   const Maps mp = maps_of(maps, per_head, layer_mask);
   return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, &mp, s);
+}
+
+extern "C" int vitcap_engine_alternatives_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace,
+                                               size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
+                                               float* alt_lp, int32_t* rank, float* entropy, void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  const Alts al = alts_of(k, alt_ids, alt_lp, rank, entropy);
+  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s,
+                     &al);
+}
+
+extern "C" int vitcap_engine_alternatives(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                          void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                          const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                          float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
+                                          float* alt_lp, int32_t* rank, float* entropy, void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  const Alts al = alts_of(k, alt_ids, alt_lp, rank, entropy);
+  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
+                     nullptr, s, &al);
 }
 
 extern "C" const void* vitcap_engine_tap(vitcap_engine* e, const char* name, void* workspace, int B, const vitcap_gen_opts* opts) {

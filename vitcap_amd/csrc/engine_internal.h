@@ -55,3 +55,9 @@ struct vitcap_engine {
 // decode.hip: the token ids of the one-pass scorer's text grid, [n_caps][2L-1] = the caption's L tokens (an id outside the vocabulary
 // is embedded as `pad`), then L-1 [MASK].  Internal to the engine (vitcap_engine_score*).
 int vc_score_grid_ids(const int64_t* ids, int64_t* grid, int n_caps, int L, int mask, int pad, void* stream);
+// alternatives.hip: vitcap_score_rows_alts, and with token_logprobs != null vitcap_score_rows' results for the same rows from the same
+// read of the chunk (out_ids and logprob_out are then required; bit-identical to vitcap_score_rows).
+int vc_score_rows_alts(const float* logits, int ldl, int V, const int64_t* caption_ids, const int64_t* last_tok, int rows0, int n_rows,
+                       int n_caps, int max_len, int eos, const int32_t* eos_extra, int pad, float* token_logprobs, int64_t* out_ids,
+                       int64_t* out_last_tok, float* logprob_out, int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy,
+                       void* stream);

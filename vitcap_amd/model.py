@@ -524,9 +524,10 @@ class ImageCaptioning(nn.Module):
             self._score_ws[slot] = sws
         return sws, need
 
-    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None):
+    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None, alts=None):
         """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill).
-        maps = (per_head, layer_mask): vitcap_engine_explain / vitcap_engine_explain_text instead, -> (lp, tok_lp, ids, maps)."""
+        maps = (per_head, layer_mask): vitcap_engine_explain / vitcap_engine_explain_text instead, -> (lp, tok_lp, ids, maps).
+        alts = k: vitcap_engine_alternatives / vitcap_engine_alternatives_text instead, -> (lp, tok_lp, ids, Alternatives)."""
         rows = B * K
         cap = cap.to(dev).contiguous()
         lt = None if lt is None else lt.to(dev).contiguous()
@@ -551,6 +552,22 @@ class ImageCaptioning(nn.Module):
                 check(lib.vitcap_engine_explain_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
                       'engine_explain_text')
             return lp, tok_lp, ids, out
+        if alts is not None:
+            from .alternatives import Alternatives
+            k = int(alts)
+            res = Alternatives(torch.empty((rows, o.max_length, k), dtype=torch.int32, device=dev),
+                               torch.empty((rows, o.max_length, k), dtype=torch.float32, device=dev),
+                               torch.empty((rows, o.max_length), dtype=torch.int32, device=dev),
+                               torch.empty((rows, o.max_length), dtype=torch.float32, device=dev))      # the engine fills all of them
+            tail = tail[:-1] + (k,) + tuple(C.c_void_p(x.data_ptr()) for x in res) + (s,)
+            if image is not None:
+                check(lib.vitcap_engine_alternatives(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                                     C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_alternatives')
+                self._encoded[slot] = (o, B)
+            else:
+                check(lib.vitcap_engine_alternatives_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
+                      'engine_alternatives_text')
+            return lp, tok_lp, ids, res
         if image is not None:
             check(lib.vitcap_engine_score(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
                                           C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score')
@@ -630,6 +647,52 @@ class ImageCaptioning(nn.Module):
         _, _, maps = self.attention_maps_encoded(ids.view(image.shape[0], o.max_length), 1, per_head=per_head, layers=layers, slot=slot,
                                                  last_tok=last, **over)
         return ids, lp, maps
+
+    def alternatives(self, image, caption_ids, seqs_per_image=1, k=5, slot=0, last_tok=None, **over):
+        """What the model would have said instead, at every position of GIVEN captions: from the logits of the one-pass scoring pass
+        (vitcap_engine_alternatives) the k best vocabulary entries per position with their log-probs, the rank of the scored word
+        among all 30522 and the entropy of the position's distribution.  Inputs and refusals as score(one_pass=True); k is 1..16.
+        -> (logprobs (rows,), token_logprobs (rows, L), alts): alts a vitcap_amd.alternatives.Alternatives of ids int32 (rows, L, k)
+        best first (ties to the lower id), logprobs fp32 (rows, L, k), rank int32 (rows, L) (0 = the scored word is the first
+        choice) and entropy fp32 (rows, L) in nats.  Position 0 and the positions behind a caption's first [SEP] hold ids = rank =
+        -1 and logprobs = entropy = 0.  Where ids equals the scored word, logprobs equals token_logprobs bit for bit."""
+        from .alternatives import check_k
+        K, k = int(seqs_per_image), check_k(k)
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
+        dev = self._check_image(image)
+        lp, tok_lp, _, alts = self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, False, alts=k)
+        return lp, tok_lp, alts
+
+    def alternatives_encoded(self, caption_ids, seqs_per_image=1, k=5, slot=0, last_tok=None, **over):
+        """alternatives() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
+        (vitcap_engine_alternatives_text); the conditions of score_encoded()."""
+        from .alternatives import check_k
+        k = check_k(k)
+        B, o, cap, lt = self._encoded_inputs('alternatives_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
+        lp, tok_lp, _, alts = self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], False, alts=k)
+        return lp, tok_lp, alts
+
+    def caption_with_alternatives(self, image, k=5, slot=0, want_token_logprobs=False, **over):
+        """Greedy captions and, for each of their words, what else the model could have said: generate() through the staged path,
+        then alternatives_encoded() on its own output (the token chosen at the last position handed over as last_tok).
+        The alternatives are those of the ONE-PASS pass, which rounds differently from the step loop that chose the words: the
+        chosen word is therefore usually, but not always, rank 0, and its log-prob among the alternatives differs from the caption's
+        own in the last bits.  -> (ids (B, 1, L), logprobs (B, 1), alts); with want_token_logprobs the one-pass pass's per-token
+        log-probs of the caption's words (B, L) come last."""
+        from .alternatives import check_k
+        k = check_k(k)
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
+            raise NotImplementedError('caption_with_alternatives runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): '
+                                      'alternatives under beam search, CBS or sampling are not built'
+                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
+        for n in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
+            over.pop(n, None)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        _, tok_lp, alts = self.alternatives_encoded(ids.view(image.shape[0], o.max_length), 1, k=k, slot=slot, last_tok=last, **over)
+        return (ids, lp, alts, tok_lp) if want_token_logprobs else (ids, lp, alts)
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like

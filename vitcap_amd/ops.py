@@ -248,6 +248,30 @@ def score_rows(logits, caption_ids, st=None, rows0=0, last_tok=None, V=L.VOCAB, 
     return st
 
 
+def score_rows_alts(logits, caption_ids, k, out=None, rows0=0, last_tok=None, V=L.VOCAB, eos=102, eos_extra=(), pad=0):
+    """vitcap_score_rows_alts on the probe rows [rows0, rows0 + len(logits)) of caption_ids (n_caps, max_len).  out: the dict a
+    previous chunk's call returned (ids, logprobs (n_caps, max_len, k), rank, entropy (n_caps, max_len)); a new one, set to the dead
+    pattern (-1 / 0), is made when None.  Only the covered rows' positions are written."""
+    _dev_f32(logits)
+    n_caps, max_len = caption_ids.shape
+    dev = logits.device
+    if out is None:
+        out = dict(ids=torch.full((n_caps, max_len, k), -1, device=dev, dtype=torch.int32),
+                   logprobs=torch.zeros((n_caps, max_len, k), device=dev, dtype=torch.float32),
+                   rank=torch.full((n_caps, max_len), -1, device=dev, dtype=torch.int32),
+                   entropy=torch.zeros((n_caps, max_len), device=dev, dtype=torch.float32))
+    assert caption_ids.is_cuda and caption_ids.is_contiguous() and caption_ids.dtype == torch.int64
+    assert tuple(out['ids'].shape) == tuple(out['logprobs'].shape) == (n_caps, max_len, k)
+    assert tuple(out['rank'].shape) == tuple(out['entropy'].shape) == (n_caps, max_len)
+    assert all(out[n].is_cuda and out[n].is_contiguous() for n in ('ids', 'logprobs', 'rank', 'entropy'))
+    assert out['ids'].dtype == out['rank'].dtype == torch.int32 and out['logprobs'].dtype == out['entropy'].dtype == torch.float32
+    ex = [int(x) for x in eos_extra] + [-1] * 3
+    check(lib.vitcap_score_rows_alts(_p(logits), logits.stride(0), V, _p(caption_ids), _p(last_tok), rows0, logits.shape[0], n_caps,
+                                     max_len, eos, (C.c_int32 * 3)(*ex[:3]), pad, int(k), _p(out['ids']), _p(out['logprobs']),
+                                     _p(out['rank']), _p(out['entropy']), _stream()), 'score_rows_alts')
+    return out
+
+
 def embed_step(ids, t, word, pos, typ, gamma, beta, eps=1e-12, mask_token=103):
     B, max_len = ids.shape
     xf = torch.empty((2 * B, 768), device=ids.device, dtype=torch.float32)

@@ -247,6 +247,32 @@ class _PredictRun(object):
                                            'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
                 pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
 
+    def alternative_rows(self, batches, dev, pred_rows, k):
+        """cfg.alternatives = k: the batches strictly one after the other through ImageCaptioning.caption_with_alternatives, as
+        attention_rows runs them (gemm_mode = TILES: the captions and confidences are the ordinary predict loop's, bit for bit).
+        Yields the rows of the alternatives TSV, one per image: the key and a JSON list with one record per live position of the
+        predicted caption -- word, log-prob, rank, entropy and the k (word, log-prob) alternatives, all of the one-pass pass."""
+        from .alternatives import to_words
+        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        vocab = self.pipe.tokenizer.ids_to_tokens
+        with torch.no_grad():
+            for batch in batches:
+                batch = dict(batch)
+                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
+                if model.check_text_inputs(batch, L) != 0:
+                    raise NotImplementedError('alternatives: visible tag slots (tag_visible > 0) are not built for the alternatives')
+                ids, lp, alts, tok_lp = model.caption_with_alternatives(batch['image'], k=k, want_token_logprobs=True, gemm_mode=1)
+                ids_h, alts_h, tok_lp_h = ids.cpu(), type(alts)(*(x.cpu() for x in alts)), tok_lp.cpu()
+                for b, key in enumerate(batch['key']):
+                    toks, words = ids_h[b, 0].tolist(), to_words(self.pipe.tokenizer, alts_h, b)
+                    rank, ent, own = alts_h.rank[b].tolist(), alts_h.entropy[b].tolist(), tok_lp_h[b].tolist()
+                    # word: the caption's token as written (a [SEP] the max-length rule wrote into the last column is scored as the
+                    # loop's own choice there); logprob, rank: the scored word's in the one-pass pass
+                    recs = [{'word': vocab[toks[t]], 'logprob': own[t], 'rank': rank[t], 'entropy': ent[t],
+                             'alternatives': [[w, q] for w, q in words[t]]} for t in range(1, L) if rank[t] >= 0]
+                    yield key, json.dumps(recs)
+                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+
     def counted(self, rows):
         """images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
         workers running) to the last row -- the figure the reference's trainer logs as images/sec (trainer.py:155-170)."""
@@ -641,7 +667,19 @@ class CaptionUniPipeline(object):
                 self.merge_rank_files(predict_result_file)
                 self.merge_rank_files(attn_file)
             return predict_result_file
-        tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)               # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
+        if self.cfg.alternatives:
+            # a second TSV next to the predictions, one row per image: per word of the caption its alternatives, rank and entropy
+            alt_file = self.get_alternatives_file(predict_result_file)
+            alt_sub = alt_file if self.world == 1 else '{}_{}_{}.tsv'.format(alt_file, self.rank, self.world)
+            pred_rows = []
+            tsv_writer(run.counted(run.alternative_rows(batches, dev, pred_rows, int(self.cfg.alternatives))), alt_sub)
+            tsv_writer(iter(pred_rows), sub)
+            run.report()
+            if self.world > 1:
+                self.merge_rank_files(predict_result_file)
+                self.merge_rank_files(alt_file)
+            return predict_result_file
+        tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)              # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
         run.report()
         if self.world > 1:
             self.merge_rank_files(predict_result_file)
@@ -652,6 +690,31 @@ class CaptionUniPipeline(object):
         """<predict file minus .tsv>.attn.tsv: written by predict when the config sets `attention_maps`."""
         assert predict_result_file.endswith('.tsv')
         return predict_result_file[:-len('.tsv')] + '.attn.tsv'
+
+    @staticmethod
+    def get_alternatives_file(predict_result_file):
+        """<predict file minus .tsv>.alt.tsv: written by predict when the config sets `alternatives: k`."""
+        assert predict_result_file.endswith('.tsv')
+        return predict_result_file[:-len('.tsv')] + '.alt.tsv'
+
+    def check_alternatives(self):
+        """`alternatives: k` is refused by name with what the alternatives are not built for, before a model is built."""
+        from .alternatives import check_k
+        cfg = self.cfg
+        if not cfg.alternatives:
+            return
+        check_k(cfg.alternatives)
+        if cfg.num_beams not in (None, 1) or cfg.use_cbs:
+            raise NotImplementedError('alternatives: they are those of greedy captions; beam search (num_beams=%r) and CBS (use_cbs=%r) '
+                                      'are not built for them' % (cfg.num_beams, cfg.use_cbs))
+        if cfg.caption_prefix:
+            raise NotImplementedError('alternatives: caption_prefix=%r is not built together with the alternatives (they are those of '
+                                      'free greedy captions)' % (cfg.caption_prefix,))
+        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (alternative_rows)
+            raise NotImplementedError('alternatives: visible tag slots (tag_visible=%r) are not built for the alternatives' % (cfg.tag_visible,))
+        if cfg.attention_maps:
+            raise NotImplementedError('alternatives together with attention_maps: one explaining pass per run is built; run the two '
+                                      'configurations one after the other')
 
     def merge_rank_files(self, predict_result_file):
         """Rank 0 concatenates the ranks' files and de-duplicates by key (uni_pipeline.py:816-831); every rank waits for it."""
@@ -677,6 +740,7 @@ class CaptionUniPipeline(object):
         if self.cfg.attention_maps and self.cfg.caption_prefix:
             raise NotImplementedError('attention_maps: caption_prefix=%r is not built together with the attention maps (the maps are '
                                       'those of free greedy captions)' % (self.cfg.caption_prefix,))
+        self.check_alternatives()
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -690,6 +754,8 @@ class CaptionUniPipeline(object):
         have = op.isfile(predict_result_file)
         if have and self.cfg.attention_maps and not op.isfile(self.get_attention_file(predict_result_file)):
             have = False             # predictions from a run without the key: both files are written again
+        if have and self.cfg.alternatives and not op.isfile(self.get_alternatives_file(predict_result_file)):
+            have = False
         if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
             return predict_result_file
