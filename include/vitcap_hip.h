@@ -554,6 +554,17 @@ int vitcap_attn_decode_beam_groups(const void* qkv_step, const void* vis_qkv, co
  * (VITCAP_EINVAL) with `out` untouched. */
 int vitcap_attn_text_grid(const void* qkv_text, const void* vis_qkv, const void* vis_vt, void* out, int n_images, int caps_per_image,
                           int S_vis, int max_len, float scale, void* stream);
+/* vitcap_attn_text_grid with a per-caption set of VISIBLE visual keys (the reference's attention_mask zeros on caption rows / visual
+ * columns, (1 - mask) * -10000 on the score: modeling_bert.py:1498-1501).
+ *   vis_mask  device uint32 [n_images * caps_per_image][19], 4-byte aligned: bit k & 31 of word k >> 5 set = visual key k (0..577, in
+ *             the cache's order: 0 = tag_hidden[:, 0], 1 = the encoder's cls row, 2..577 the 24 x 24 patches row-major) is visible
+ *             to EVERY row of that caption, token rows and probe rows alike; bits 578..607 are ignored.
+ * A hidden key scores -inf before the row maximum is taken (the reference's -10000 has exp exactly 0 in fp32).  Token keys and the
+ * probe's own key are never masked, so no softmax row is empty even with all 578 keys hidden.  Everything else is
+ * vitcap_attn_text_grid: with all 578 bits set the output is bit-identical to it.  Refusals as vitcap_attn_text_grid, plus a null or
+ * misaligned vis_mask (VITCAP_EINVAL, the argument named, `out` untouched). */
+int vitcap_attn_text_grid_masked(const void* qkv_text, const void* vis_qkv, const void* vis_vt, const uint32_t* vis_mask, void* out,
+                                 int n_images, int caps_per_image, int S_vis, int max_len, float scale, void* stream);
 /* Attention maps of given captions: the normalised softmax rows of the [MASK] probes of ONE decoder layer, written out
  * (csrc/attn_maps.hip; the reference's attention_probs[b, h, cur_len, :] at step cur_len = t, modeling_bert.py:320-342, collected
  * by BertEncoder under config.output_attentions, 484-510; mask 846-876).  qkv_text / vis_qkv as vitcap_attn_text_grid takes them;
@@ -777,6 +788,25 @@ int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, 
                         size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
                         size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
                         void* stream);
+/* "Would this word survive without this region": the one-pass scoring pass with visual keys hidden from the captions
+ * (vitcap_attn_text_grid_masked in place of vitcap_attn_text_grid in all four decoder layers, the same mask in each, as the
+ * reference applies its attention_mask).  Arguments, refusals and results as vitcap_engine_score_text / vitcap_engine_score, plus
+ *   vis_mask    device uint32 [B*caps_per_image][19], 4-byte aligned, laid out as vitcap_attn_text_grid_masked takes it.  It is READ
+ *               IN PLACE by the enqueued kernels, not copied: the caller keeps it alive and unchanged until the stream gets there.
+ * The mask hides visual TOKENS from the CAPTION's rows.  It does not hide patches from the encoder: vitcap_engine_encode, the prefill
+ * and the visual rows' own attention among themselves are untouched, so a hidden patch has still shaped its neighbours' tokens.
+ * With all 578 bits set the results are bit-identical to vitcap_engine_score_text / vitcap_engine_score.  A null vis_mask is
+ * VITCAP_EINVAL, refused with the batch checks before anything is enqueued.  The score workspace is that of
+ * vitcap_engine_score_workspace_bytes. */
+int vitcap_engine_score_masked_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                    int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
+                                    size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
+                                    int64_t* out_last_tok, const uint32_t* vis_mask, void* stream);
+int vitcap_engine_score_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                               void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, const uint32_t* vis_mask,
+                               void* stream);
 /* "Where did the model look for this word": the one-pass scoring pass, which also writes the attention maps of the captions' [MASK]
  * probes (vitcap_attn_probe_maps after the qkv GEMM of every selected decoder layer; the reference's attention_probs,
  * modeling_bert.py:320-342, 484-510, mask 846-876).  Arguments, refusals and results as vitcap_engine_score_text /

@@ -210,6 +210,7 @@ _SIGS = {
     'vitcap_attn_decode_beams': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_decode_beam_groups': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_text_grid': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    'vitcap_attn_text_grid_masked': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_probe_maps': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp]),
     'vitcap_score_rows': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp,
                                     vp, vp, vp]),
@@ -251,6 +252,10 @@ _SIGS = {
                                            vp, vp]),
     'vitcap_engine_score': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
                                       vp, vp, vp, vp, vp]),
+    'vitcap_engine_score_masked_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp,
+                                                  vp, vp, vp, vp]),
+    'vitcap_engine_score_masked': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
+                                             vp, vp, vp, vp, vp, vp]),
     'vitcap_engine_explain_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp, vp,
                                              vp, vp, C.c_int, C.c_int, vp]),
     'vitcap_engine_explain': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,

@@ -27,11 +27,17 @@ constexpr int GRID_NKB = (GRID_S + 15) / 16;         // 37 visual score blocks
 constexpr int GRID_MAXB = (GRID_NKB + 3) / 4;        // 10 per wave
 constexpr int GRID_NVB = VT_KP / 32;                 // 19 visual P.V blocks
 constexpr int GRID_MAXV = (GRID_NVB + 3) / 4;        // 5 per wave
+constexpr int GRID_MW = VT_KP / 32;                  // 19 mask words per caption (vitcap_attn_text_grid_masked)
 constexpr size_t GRID_SMEM = (size_t)16 * GRID_SC_LD * 4 + (size_t)4 * 16 * HD * 4 + (size_t)HD * GRID_VT_LD * 2;   // 74 816 B
 
+// MASKED (vitcap_attn_text_grid_masked): vis_mask holds GRID_MW words per caption, bit k & 31 of word k >> 5 set = visual key k is
+// visible to every row of that caption; a hidden key scores -inf before the row maximum is taken.  Token keys and the probe's own key
+// are never masked, so no row is empty.  The word of a 16-key score block is wave-uniform: one scalar load per block.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void attn_text_grid_kernel(const bf16_t* __restrict__ qkv_text, const bf16_t* __restrict__ vis_qkv,
                                                              const bf16_t* __restrict__ vis_vt, bf16_t* __restrict__ out,
-                                                             int caps_per_image, int groups_per_image, int L, float c_log2) {
+                                                             const uint32_t* __restrict__ vis_mask, int caps_per_image,
+                                                             int groups_per_image, int L, float c_log2) {
   extern __shared__ __attribute__((aligned(16))) char grid_smem[];
   float (*sc)[GRID_SC_LD] = (float (*)[GRID_SC_LD])grid_smem;                                     // [16][705]
   float (*s_o)[HD] = (float (*)[HD])(grid_smem + (size_t)16 * GRID_SC_LD * 4);                    // [4 * 16][64]: wave w, query q -> row w * 16 + q
@@ -126,10 +132,15 @@ __global__ __launch_bounds__(256) void attn_text_grid_kernel(const bf16_t* __res
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i][0], qf[0], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i][1], qf[1], acc, 0, 0, 0);
+          uint32_t mbits = 0xfu;              // this lane's four keys of the block, bit e = key e visible
+          if (MASKED) {                       // the wave index through readfirstlane: the word's address is scalar, the load a scalar load
+            const int kbu = __builtin_amdgcn_readfirstlane(w) + 4 * i;
+            mbits = vis_mask[cap * GRID_MW + (kbu >> 1)] >> ((kbu & 1) * 16 + fk * 4);
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int key = kb * 16 + fk * 4 + e;
-            const float v = key < GRID_S ? acc[e] : -INFINITY;
+            const float v = key < GRID_S && (!MASKED || ((mbits >> e) & 1u)) ? acc[e] : -INFINITY;
             sc[frow][key] = v;
             mx = fmaxf(mx, v);
           }
@@ -231,10 +242,30 @@ extern "C" int vitcap_attn_text_grid(const void* qkv_text, const void* vis_qkv, 
   VC_REQUIRE(max_len >= 2 && max_len <= 40, "attn_text_grid: max_len must be 2..40 (got %d)", max_len);
   VC_REQUIRE(caps_per_image >= 1 && caps_per_image <= 32, "attn_text_grid: caps_per_image must be 1..32 (got %d)", caps_per_image);
   const int groups = (caps_per_image + GRID_G - 1) / GRID_G;
-  VC_FUNC_SMEM(attn_text_grid_kernel, (int)GRID_SMEM);
-  hipLaunchKernelGGL(attn_text_grid_kernel, dim3(NH, n_images * groups), dim3(256), GRID_SMEM, (hipStream_t)stream,
-                     (const bf16_t*)qkv_text, (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)out, caps_per_image, groups, max_len,
-                     scale * 1.4426950408889634f);
+  VC_FUNC_SMEM(attn_text_grid_kernel<false>, (int)GRID_SMEM);
+  hipLaunchKernelGGL(attn_text_grid_kernel<false>, dim3(NH, n_images * groups), dim3(256), GRID_SMEM, (hipStream_t)stream,
+                     (const bf16_t*)qkv_text, (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)out, (const uint32_t*)nullptr,
+                     caps_per_image, groups, max_len, scale * 1.4426950408889634f);
   VC_LAUNCH_CHECK("attn_text_grid");
+  return VITCAP_OK;
+}
+
+extern "C" int vitcap_attn_text_grid_masked(const void* qkv_text, const void* vis_qkv, const void* vis_vt, const uint32_t* vis_mask,
+                                            void* out, int n_images, int caps_per_image, int S_vis, int max_len, float scale,
+                                            void* stream) {
+  VC_REQUIRE(qkv_text && vis_qkv && vis_vt && out && n_images > 0, "attn_text_grid_masked: bad arguments");
+  VC_REQUIRE(((uintptr_t)qkv_text & 15) == 0 && ((uintptr_t)vis_qkv & 15) == 0 && ((uintptr_t)vis_vt & 15) == 0,
+             "attn_text_grid_masked: misaligned");
+  VC_REQUIRE(vis_mask != nullptr, "attn_text_grid_masked: vis_mask is null");
+  VC_REQUIRE(((uintptr_t)vis_mask & 3) == 0, "attn_text_grid_masked: vis_mask is not 4-byte aligned");
+  VC_REQUIRE(S_vis == GRID_S, "attn_text_grid_masked: S_vis must be %d (got %d)", GRID_S, S_vis);
+  VC_REQUIRE(max_len >= 2 && max_len <= 40, "attn_text_grid_masked: max_len must be 2..40 (got %d)", max_len);
+  VC_REQUIRE(caps_per_image >= 1 && caps_per_image <= 32, "attn_text_grid_masked: caps_per_image must be 1..32 (got %d)", caps_per_image);
+  const int groups = (caps_per_image + GRID_G - 1) / GRID_G;
+  VC_FUNC_SMEM(attn_text_grid_kernel<true>, (int)GRID_SMEM);
+  hipLaunchKernelGGL(attn_text_grid_kernel<true>, dim3(NH, n_images * groups), dim3(256), GRID_SMEM, (hipStream_t)stream,
+                     (const bf16_t*)qkv_text, (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)out, vis_mask, caps_per_image, groups,
+                     max_len, scale * 1.4426950408889634f);
+  VC_LAUNCH_CHECK("attn_text_grid_masked");
   return VITCAP_OK;
 }

@@ -1099,9 +1099,16 @@ int check_alts(const Alts& a) {
   return VITCAP_OK;
 }
 
+// Visual keys hidden from the captions (vitcap_engine_score_masked*): off for every other entry point.  The mask is the caller's
+// array, read in place by the attention launches of all four layers.
+struct Occl {
+  const uint32_t* vis_mask = nullptr;      // [NC][19], vitcap_attn_text_grid_masked's layout
+  bool on() const { return vis_mask != nullptr; }
+};
+
 // reads lo.dqkv[0..3] of `ws` (the visual caches of the prefill) and nothing else of it
 int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, const ScoreLayout& sl, char* sw,
-                 const ScoreIO& io, void* s, const Maps& mp = Maps(), const Alts& al = Alts()) {
+                 const ScoreIO& io, void* s, const Maps& mp = Maps(), const Alts& al = Alts(), const Occl& oc = Occl()) {
   hipStream_t st = (hipStream_t)s;
   const int L = sl.L, R = sl.R, K = sl.K;
   const int NC = (int)sl.NC, M = (int)sl.M, P = (int)sl.P;
@@ -1125,7 +1132,8 @@ int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout
       CK(vitcap_attn_probe_maps(sw + sl.qkv, vis, ids, mp.out + (size_t)l * (mp.per_head ? 12 : 1) * (SV + L), B, K, SV, L, mp.per_head,
                                 o.eos_token_id, o.eos_extra, 0.125f, s));
     CK(vitcap_attn_beam_vt(vis, sw + sl.vt, B, SV, s));
-    CK(vitcap_attn_text_grid(sw + sl.qkv, vis, sw + sl.vt, sw + sl.ctx, B, K, SV, L, 0.125f, s));
+    if (oc.on()) CK(vitcap_attn_text_grid_masked(sw + sl.qkv, vis, sw + sl.vt, oc.vis_mask, sw + sl.ctx, B, K, SV, L, 0.125f, s));
+    else CK(vitcap_attn_text_grid(sw + sl.qkv, vis, sw + sl.vt, sw + sl.ctx, B, K, SV, L, 0.125f, s));
     // BertSelfOutput / BertIntermediate / BertOutput: dense + residual, then LayerNorm (post-LN), as prefill_part
     CK(q.gemm_ln(sw + sl.ctx, D, lw.ao_w, lw.ao_b, x_f, sw + sl.tmp, M, D, lw.ao_g, lw.ao_beta, 1e-12f, sw + sl.sa_b, sl.sa_f.at<float>(sw)));
     CK(q.gemm(sw + sl.sa_b, D, lw.i_w, lw.i_b, nullptr, 0, sw + sl.mlp, 4 * D, M, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16));
@@ -1167,15 +1175,21 @@ extern "C" size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image,
 
 namespace {
 
-// The six entry points of the one-pass pass: every refusal in one order -- options, batch, maps / alternatives (when asked for), io,
-// workspace -- then, with an image, encode + prefill, then score_locked.  mp: the maps description of the explain pair, al: the
-// alternatives description of the alternatives pair; both null for the scoring pair.
+// The eight entry points of the one-pass pass: every refusal in one order -- options, batch (and, for the masked pair, the mask),
+// maps / alternatives (when asked for), io, workspace -- then, with an image, encode + prefill, then score_locked.  mp: the maps
+// description of the explain pair, al: the alternatives description of the alternatives pair, oc: the mask of the masked pair; all
+// null for the scoring pair.
 int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool encode, int B, const vitcap_gen_opts* opts, void* workspace,
                 size_t workspace_bytes, int caps_per_image, const ScoreIO& io, void* score_ws, size_t score_ws_bytes, const Maps* mp,
-                void* s, const Alts* al = nullptr) {
+                void* s, const Alts* al = nullptr, const Occl* oc = nullptr) {
   const vitcap_gen_opts o = opts_or_default(opts);
   CK(check_score(o, caps_per_image));
-  if (B <= 0) { vitcap_set_error("%s: bad batch", mp ? "engine_explain" : al ? "engine_alternatives" : "engine_score"); return VITCAP_EINVAL; }
+  if (B <= 0) {
+    vitcap_set_error("%s: bad batch", mp ? "engine_explain" : al ? "engine_alternatives" : oc ? "engine_score_masked" : "engine_score");
+    return VITCAP_EINVAL;
+  }
+  if (oc && !oc->vis_mask) { vitcap_set_error("engine_score_masked: vis_mask is null"); return VITCAP_EINVAL; }
+  if (oc && ((uintptr_t)oc->vis_mask & 3) != 0) { vitcap_set_error("engine_score_masked: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
   if (mp) CK(check_maps(*mp));
   if (al) CK(check_alts(*al));
   const ScoreLayout sl(B, caps_per_image, o.max_length);
@@ -1188,7 +1202,7 @@ int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool enc
     CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
     CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
   }
-  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps(), al ? *al : Alts());
+  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps(), al ? *al : Alts(), oc ? *oc : Occl());
 }
 
 Alts alts_of(int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy) {
@@ -1220,6 +1234,30 @@ extern "C" int vitcap_engine_score(vitcap_engine* e, const void* image, int imag
   const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
   return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
                      nullptr, s);
+}
+
+extern "C" int vitcap_engine_score_masked_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace,
+                                               size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
+                                               const uint32_t* vis_mask, void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  Occl oc;
+  oc.vis_mask = vis_mask;
+  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s,
+                     nullptr, &oc);
+}
+
+extern "C" int vitcap_engine_score_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                          void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
+                                          const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
+                                          float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, const uint32_t* vis_mask,
+                                          void* s) {
+  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
+  Occl oc;
+  oc.vis_mask = vis_mask;
+  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
+                     nullptr, s, nullptr, &oc);
 }
 
 extern "C" int vitcap_engine_explain_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,

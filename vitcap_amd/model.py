@@ -524,8 +524,10 @@ class ImageCaptioning(nn.Module):
             self._score_ws[slot] = sws
         return sws, need
 
-    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None, alts=None):
+    def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None, alts=None, vis=None):
         """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill).
+        vis = packed visibility words int32 (rows, 19) (vitcap_amd.occlusion.pack_visible): vitcap_engine_score_masked /
+        vitcap_engine_score_masked_text instead; same results as the plain pair.
         maps = (per_head, layer_mask): vitcap_engine_explain / vitcap_engine_explain_text instead, -> (lp, tok_lp, ids, maps).
         alts = k: vitcap_engine_alternatives / vitcap_engine_alternatives_text instead, -> (lp, tok_lp, ids, Alternatives)."""
         rows = B * K
@@ -568,6 +570,19 @@ class ImageCaptioning(nn.Module):
                 check(lib.vitcap_engine_alternatives_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
                       'engine_alternatives_text')
             return lp, tok_lp, ids, res
+        if vis is not None:
+            # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
+            vis = vis.to(device=dev, dtype=torch.int32).contiguous()
+            assert tuple(vis.shape) == (rows, 19)
+            tail = tail[:-1] + (C.c_void_p(vis.data_ptr()), s)
+            if image is not None:
+                check(lib.vitcap_engine_score_masked(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                                     C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score_masked')
+                self._encoded[slot] = (o, B)
+            else:
+                check(lib.vitcap_engine_score_masked_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
+                      'engine_score_masked_text')
+            return (lp, tok_lp, ids) if return_ids else (lp, tok_lp)
         if image is not None:
             check(lib.vitcap_engine_score(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
                                           C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score')
@@ -693,6 +708,113 @@ class ImageCaptioning(nn.Module):
         ids, lp, last = self.run(image, o, slot=slot, want_last=True)
         _, tok_lp, alts = self.alternatives_encoded(ids.view(image.shape[0], o.max_length), 1, k=k, slot=slot, last_tok=last, **over)
         return (ids, lp, alts, tok_lp) if want_token_logprobs else (ids, lp, alts)
+
+    # ---- occlusion: given captions scored with visual keys hidden from them (vitcap_engine_score_masked*)
+    def score_masked(self, image, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+        """score(one_pass=True) with visual keys hidden from the captions: `visible`, bool or uint8, one row per caption, either
+        (rows, 578) in the cache's order (0 tag cls, 1 encoder cls, 2..577 the 24 x 24 patches row-major) or a (rows, 24, 24) patch
+        grid (both cls columns then stay visible); nonzero = the caption's rows may attend that visual token, in all four decoder
+        layers -- the reference's attention_mask zeros on caption rows / visual columns (modeling_bert.py:1498-1501).  The mask hides
+        visual TOKENS from the CAPTION; the encoder and the prefill still see the whole image.  Inputs and refusals as
+        score(one_pass=True); a wrong shape or dtype of `visible` is a ValueError before the GPU is touched.  With everything visible
+        the results are score(one_pass=True)'s, bit for bit."""
+        from .occlusion import as_visible, pack_visible
+        K = int(seqs_per_image)
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
+        vis = pack_visible(as_visible(visible, image.shape[0] * K))
+        dev = self._check_image(image)
+        return self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, return_ids, vis=vis)
+
+    def score_masked_encoded(self, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+        """score_masked() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
+        (vitcap_engine_score_masked_text); the conditions of score_encoded()."""
+        from .occlusion import as_visible, pack_visible
+        K = int(seqs_per_image)
+        B, o, cap, lt = self._encoded_inputs('score_masked_encoded', slot, caption_ids, K, last_tok, over)
+        vis = pack_visible(as_visible(visible, B * K))
+        return self._score_one_pass(None, B, o, cap, lt, K, slot, self._packed[2], return_ids, vis=vis)
+
+    def _score_variants(self, image, B, o, cap, lt, masks, slot, dev):
+        """Every caption of cap (B * K, L) under every mask row of `masks` bool (V, 578), in passes of at most 32 variants per image
+        (K * variants <= 32 rows per image and pass); the first pass encodes when an image is given, the later ones read its prefill.
+        -> (logprobs (B * K, V), token_logprobs (B * K, V, L))."""
+        from .occlusion import MAX_ROWS, pack_visible
+        K, V, L = cap.shape[0] // B, masks.shape[0], cap.shape[1]
+        words = pack_visible(masks)                                    # (V, 19)
+        per = max(1, MAX_ROWS // K)
+        lps, toks = [], []
+        for v0 in range(0, V, per):
+            n = min(per, V - v0)
+            c = cap.repeat_interleave(n, 0)                            # caption-major: the n variants of a caption are adjacent
+            t = None if lt is None else lt.repeat_interleave(n, 0)
+            w = words[v0:v0 + n].repeat(B * K, 1)
+            lp, tok = self._score_one_pass(image if v0 == 0 else None, B, o, c, t, K * n, slot, dev, False, vis=w)
+            lps.append(lp.view(B * K, n))
+            toks.append(tok.view(B * K, n, L))
+        return torch.cat(lps, 1), torch.cat(toks, 1)
+
+    def _occlusion(self, image, B, o, cap, lt, window, stride, keep_cls, keep_only, slot, dev):
+        from .occlusion import check_window, window_masks
+        window, stride, g = check_window(window, stride)
+        masks = torch.cat([torch.ones((1, 578), dtype=torch.bool), window_masks(window, stride, keep_cls, keep_only)], 0)
+        lp, tok = self._score_variants(image, B, o, cap, lt, masks, slot, dev)
+        drop = tok[:, :1] - tok[:, 1:]                                 # (B, G, L)
+        return lp[:, 0], tok[:, 0], drop.permute(0, 2, 1).reshape(B, cap.shape[1], g, g)
+
+    def occlusion_maps(self, image, caption_ids, window=4, stride=None, keep_cls=True, keep_only=False, slot=0, last_tok=None, **over):
+        """How much less likely each word of a GIVEN caption becomes when the caption cannot see a region of the image: the caption
+        (one per image, caption_ids (B, L)) is scored unoccluded and once per window position -- a window x window block of the
+        24 x 24 patch grid hidden from it (with keep_only: everything BUT the block hidden), windows `stride` apart (default: window;
+        (24 - window) % stride must be 0).  keep_cls: the two cls tokens (columns 0, 1) stay visible in the occluded variants.  The
+        variants of an image share its encoder pass and visual K/V, 32 per scoring pass (score_masked).
+        -> (logprobs (B,), token_logprobs (B, L): the unoccluded scores, and drop (B, L, gh, gw)):
+        drop[b, t, i, j] = token_logprobs[b, t] - the same with window (i, j) hidden; gh = gw = (24 - window) / stride + 1; zero at
+        position 0 and behind the caption's end, where both terms are.  Occlusion hides visual tokens from the caption only: the
+        encoder has seen the whole image.  Inputs and refusals as score(one_pass=True)."""
+        from .occlusion import check_window
+        check_window(window, stride)
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, 1, last_tok, over)
+        dev = self._check_image(image)
+        return self._occlusion(image, image.shape[0], o, cap, lt, window, stride, keep_cls, keep_only, slot, dev)
+
+    def occlusion_maps_encoded(self, caption_ids, window=4, stride=None, keep_cls=True, keep_only=False, slot=0, last_tok=None, **over):
+        """occlusion_maps() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again;
+        the conditions of score_encoded()."""
+        from .occlusion import check_window
+        check_window(window, stride)
+        B, o, cap, lt = self._encoded_inputs('occlusion_maps_encoded', slot, caption_ids, 1, last_tok, over)
+        return self._occlusion(None, B, o, cap, lt, window, stride, keep_cls, keep_only, slot, self._packed[2])
+
+    def caption_with_occlusion(self, image, window=4, stride=None, keep_cls=True, keep_only=False, slot=0, **over):
+        """Greedy captions and the occlusion maps of their words: generate() through the staged path, then occlusion_maps_encoded()
+        on its own output (the token chosen at the last position handed over as last_tok).  -> (ids (B, 1, L), logprobs (B, 1),
+        drop (B, L, gh, gw))."""
+        from .occlusion import check_window
+        check_window(window, stride)
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
+            raise NotImplementedError('caption_with_occlusion runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): '
+                                      'occlusion maps under beam search, CBS or sampling are not built'
+                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
+        for n in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
+            over.pop(n, None)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        _, _, drop = self.occlusion_maps_encoded(ids.view(image.shape[0], o.max_length), window, stride, keep_cls, keep_only, slot=slot,
+                                                 last_tok=last, **over)
+        return ids, lp, drop
+
+    def visual_gain(self, image, caption_ids, seqs_per_image=1, slot=0, last_tok=None, **over):
+        """What the image added to each word of GIVEN captions: token_logprobs minus the token_logprobs with all 578 visual keys
+        hidden from the caption (it then attends its own tokens only), from two variants per caption.  Inputs and refusals as
+        score(one_pass=True).  -> fp32 (rows, L), zero at position 0 and behind a caption's end."""
+        K = int(seqs_per_image)
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
+        dev = self._check_image(image)
+        masks = torch.stack([torch.ones(578, dtype=torch.bool), torch.zeros(578, dtype=torch.bool)])
+        _, tok = self._score_variants(image, image.shape[0], o, cap, lt, masks, slot, dev)
+        return tok[:, 0] - tok[:, 1]
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like

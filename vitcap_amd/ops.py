@@ -207,6 +207,22 @@ def attn_text_grid(qkv_text, vis_qkv, n_images, caps_per_image, S_vis=578, max_l
     return out
 
 
+def attn_text_grid_masked(qkv_text, vis_qkv, vis_mask, n_images, caps_per_image, S_vis=578, max_len=20, scale=0.125, out=None):
+    """attn_text_grid with visual keys hidden per caption (vitcap_attn_text_grid_masked): vis_mask int32 (n_images * caps_per_image,
+    19) on the device, bit k & 31 of word k >> 5 set = visual key k visible (vitcap_amd.occlusion.pack_visible).  -> bf16 (rows, 768)."""
+    _dev_bf16(qkv_text)
+    _dev_bf16(vis_qkv)
+    assert vis_mask.is_cuda and vis_mask.is_contiguous() and vis_mask.dtype == torch.int32
+    assert tuple(vis_mask.shape) == (n_images * caps_per_image, 19)
+    vt = torch.empty((n_images, 12, 64, 608), device=qkv_text.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_beam_vt(_p(vis_qkv), _p(vt), n_images, min(S_vis, 608), _stream()), 'attn_beam_vt')
+    if out is None:
+        out = torch.empty((n_images * caps_per_image * (2 * max_len - 1), 768), device=qkv_text.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_text_grid_masked(_p(qkv_text), _p(vis_qkv), _p(vt), _p(vis_mask), _p(out), n_images, caps_per_image, S_vis,
+                                           max_len, scale, _stream()), 'attn_text_grid_masked')
+    return out
+
+
 def attn_probe_maps(qkv_text, vis_qkv, caption_ids, n_images, caps_per_image, S_vis=578, max_len=20, per_head=False, layer=0, out=None,
                     eos=102, eos_extra=(), scale=0.125):
     """Attention maps of the [MASK] probes of given captions, one decoder layer (vitcap_attn_probe_maps): qkv_text / vis_qkv as

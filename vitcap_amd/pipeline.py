@@ -273,6 +273,26 @@ class _PredictRun(object):
                     yield key, json.dumps(recs)
                 pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
 
+    def occlusion_rows(self, batches, dev, pred_rows, window):
+        """cfg.occlusion = window: the batches strictly one after the other through ImageCaptioning.caption_with_occlusion, as
+        attention_rows runs them (gemm_mode = TILES: the captions and confidences are the ordinary predict loop's, bit for bit).
+        Yields the rows of the occlusion TSV, one per image: the key and a JSON list with one record per live position of the
+        predicted caption -- the word and its gh x gw log-prob drops (vitcap_amd.occlusion.to_rows)."""
+        from .occlusion import to_rows
+        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        eos = model.test_extra_input.get('eos_token_ids') or [102]
+        with torch.no_grad():
+            for batch in batches:
+                batch = dict(batch)
+                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
+                if model.check_text_inputs(batch, L) != 0:
+                    raise NotImplementedError('occlusion: visible tag slots (tag_visible > 0) are not built for the occlusion maps')
+                ids, lp, drop = model.caption_with_occlusion(batch['image'], window=window, gemm_mode=1)
+                ids_h = ids.cpu()
+                for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
+                    yield key, json.dumps(recs)
+                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+
     def counted(self, rows):
         """images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
         workers running) to the last row -- the figure the reference's trainer logs as images/sec (trainer.py:155-170)."""
@@ -679,6 +699,18 @@ class CaptionUniPipeline(object):
                 self.merge_rank_files(predict_result_file)
                 self.merge_rank_files(alt_file)
             return predict_result_file
+        if self.cfg.occlusion:
+            # a second TSV next to the predictions, one row per image: per word of the caption its window drops
+            occ_file = self.get_occlusion_file(predict_result_file)
+            occ_sub = occ_file if self.world == 1 else '{}_{}_{}.tsv'.format(occ_file, self.rank, self.world)
+            pred_rows = []
+            tsv_writer(run.counted(run.occlusion_rows(batches, dev, pred_rows, int(self.cfg.occlusion))), occ_sub)
+            tsv_writer(iter(pred_rows), sub)
+            run.report()
+            if self.world > 1:
+                self.merge_rank_files(predict_result_file)
+                self.merge_rank_files(occ_file)
+            return predict_result_file
         tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)              # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
         run.report()
         if self.world > 1:
@@ -696,6 +728,37 @@ class CaptionUniPipeline(object):
         """<predict file minus .tsv>.alt.tsv: written by predict when the config sets `alternatives: k`."""
         assert predict_result_file.endswith('.tsv')
         return predict_result_file[:-len('.tsv')] + '.alt.tsv'
+
+    @staticmethod
+    def get_occlusion_file(predict_result_file):
+        """<predict file minus .tsv>.occ.tsv: written by predict when the config sets `occlusion: window`."""
+        assert predict_result_file.endswith('.tsv')
+        return predict_result_file[:-len('.tsv')] + '.occ.tsv'
+
+    def check_occlusion(self):
+        """`occlusion: window` is refused by name with what the occlusion maps are not built for, before a model is built."""
+        from .occlusion import check_window
+        cfg = self.cfg
+        if not cfg.occlusion:
+            return
+        check_window(cfg.occlusion)
+        if cfg.num_beams not in (None, 1):
+            raise NotImplementedError('occlusion: the maps are those of greedy captions; beam search (num_beams=%r) is not built for '
+                                      'them' % (cfg.num_beams,))
+        if cfg.use_cbs:
+            raise NotImplementedError('occlusion: the maps are those of greedy captions; CBS (use_cbs=%r) is not built for them'
+                                      % (cfg.use_cbs,))
+        if cfg.caption_prefix:
+            raise NotImplementedError('occlusion: caption_prefix=%r is not built together with the occlusion maps (they are those of '
+                                      'free greedy captions)' % (cfg.caption_prefix,))
+        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (occlusion_rows)
+            raise NotImplementedError('occlusion: visible tag slots (tag_visible=%r) are not built for the occlusion maps' % (cfg.tag_visible,))
+        if cfg.attention_maps:
+            raise NotImplementedError('occlusion together with attention_maps: one explaining pass per run is built; run the two '
+                                      'configurations one after the other')
+        if cfg.alternatives:
+            raise NotImplementedError('occlusion together with alternatives: one explaining pass per run is built; run the two '
+                                      'configurations one after the other')
 
     def check_alternatives(self):
         """`alternatives: k` is refused by name with what the alternatives are not built for, before a model is built."""
@@ -741,6 +804,7 @@ class CaptionUniPipeline(object):
             raise NotImplementedError('attention_maps: caption_prefix=%r is not built together with the attention maps (the maps are '
                                       'those of free greedy captions)' % (self.cfg.caption_prefix,))
         self.check_alternatives()
+        self.check_occlusion()
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -755,6 +819,8 @@ class CaptionUniPipeline(object):
         if have and self.cfg.attention_maps and not op.isfile(self.get_attention_file(predict_result_file)):
             have = False             # predictions from a run without the key: both files are written again
         if have and self.cfg.alternatives and not op.isfile(self.get_alternatives_file(predict_result_file)):
+            have = False
+        if have and self.cfg.occlusion and not op.isfile(self.get_occlusion_file(predict_result_file)):
             have = False
         if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
