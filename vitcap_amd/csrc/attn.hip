@@ -387,7 +387,22 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     const uint4 v = *(const uint4*)(qkv_step + ((size_t)b * 2) * QKV_LD + 768 * (1 + which) + h * HD + sub * 8);
     *(uint4*)(tkv + ((size_t)(t - 1) * 2 + which) * 768 + h * HD + sub * 8) = v;
   }
-  auto key_ptr = [&](int k, int which) -> const bf16_t* {   // which: 0 K, 1 V
+  // Key k belongs to thread group k % 32 in both passes, and every thread walks its keys in ascending k, 128 keys per sweep.
+  // The visual keys [0, S_vis) come first: 98 % of the bytes, read once per launch by this workgroup alone and too many (4 layers
+  // x 118 MB at B = 64) for any cache to hold until the next step.  The sweeps that hold visual keys only (4 of the 5 at
+  // S_vis = 578) stream them with the non-temporal policy through a descriptor over this image's visual rows: one 32-bit add
+  // per load in place of the selects and the 64-bit multiply-add of a generic key, nothing to test per key, and a row past S_vis
+  // would read as zeros, not from a neighbour's rows.  The whole byte offset sits in the per-lane operand: the hardware leaves
+  // the scalar offset operand out of its range check.  The sweep the visual rows end in, and any behind it, take each key from
+  // its own source with generic addressing and the default policy: the tag rows, the text cache and this step's two rows are
+  // few and are re-read by the next step, and folding them into that sweep costs them no round trip of their own.
+  const __amdgpu_buffer_rsrc_t vis_rc = vc_rsrc(vis_qkv + (size_t)img * S_vis * QKV_LD, (long long)S_vis * QKV_LD * 2);
+  const uint32_t vis_off = (uint32_t)(kslot * QKV_LD + 768 + h * HD + sub * 8) * 2u;   // K of key kslot; its V is 768 * 2 bytes on
+  auto vis_load = [&](int row0, int which) -> bf16x8 {   // visual key row0 + kslot, row0 a multiple of 32
+    const uint32_t off = vis_off + (uint32_t)row0 * (uint32_t)(QKV_LD * 2) + (uint32_t)which * (768u * 2u);
+    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(vis_rc, off, 0, /*nt*/ 2));
+  };
+  auto key_ptr = [&](int k, int which) -> const bf16_t* {   // any key; which: 0 K, 1 V
     if (k < S_vis) return vis_qkv + ((size_t)img * S_vis + k) * QKV_LD + 768 * (1 + which) + h * HD + sub * 8;
     if (k < S_pre) return tag_kv + ((size_t)img * n_tag + (k - S_vis)) * QKV_LD + 768 * (1 + which) + h * HD + sub * 8;
     const int tp = k - S_pre;
@@ -397,7 +412,40 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 
   // ---- pass 1: scores.  Four keys per thread per sweep (4 x 16 B loads in flight; the kernel is HBM-latency bound)
   float mx0 = -1e30f, mx1 = -1e30f;
-  for (int kb = kslot; kb < nkeys; kb += 128) {
+#define DECODE_SCORE(k_, kv_, valid_, text_)                                                \
+  do {                                                                                      \
+    float d0 = 0.f, d1 = 0.f;                                                               \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                         \
+      const float kf = (float)(kv_)[j];                                                     \
+      d0 = __builtin_fmaf(q0[j], kf, d0); /* fused by name: four keys side by side tempt hipcc to split some */ \
+      d1 = __builtin_fmaf(q1[j], kf, d1);                                                   \
+    }                                                                                       \
+    _Pragma("unroll") for (int o = 4; o > 0; o >>= 1) {                                     \
+      d0 += __shfl_xor(d0, o, 64);                                                          \
+      d1 += __shfl_xor(d1, o, 64);                                                          \
+    }                                                                                       \
+    if ((text_) && (k_) == nkeys - 1) d0 = -INFINITY; /* row 0 (position t-1) cannot see the [MASK] row */ \
+    if (valid_) {                                                                           \
+      if (sub == 0) { sc[0][k_] = d0; sc[1][k_] = d1; }                                     \
+      mx0 = fmaxf(mx0, d0);                                                                 \
+      mx1 = fmaxf(mx1, d1);                                                                 \
+    }                                                                                       \
+  } while (0)
+  const int vis_full = S_vis & ~127;                  // whole sweeps of visual keys: nothing to test per key
+  for (int k0 = 0; k0 < vis_full; k0 += 128) {
+    bf16x8 kv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) kv[u] = vis_load(k0 + u * 32, 0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + kslot + u * 32;
+      DECODE_SCORE(k, kv[u], true, false);
+      // one key at a time: the next key's row is not unpacked before this key is done.  Left alone, hipcc interleaves the four
+      // keys of a branch-free sweep, which costs 20 registers and with them the residency beside the 8-wave GEMM
+      if (u < 3) asm volatile("" : "+v"(mx0), "+v"(mx1), "+v"(kv[u + 1]));
+    }
+  }
+  for (int kb = vis_full + kslot; kb < nkeys; kb += 128) {
     bf16x8 kv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -407,26 +455,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = kb + u * 32;
-      float d0 = 0.f, d1 = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float kf = (float)kv[u][j];
-        d0 += q0[j] * kf;
-        d1 += q1[j] * kf;
-      }
-#pragma unroll
-      for (int o = 4; o > 0; o >>= 1) {
-        d0 += __shfl_xor(d0, o, 64);
-        d1 += __shfl_xor(d1, o, 64);
-      }
-      if (k == nkeys - 1) d0 = -INFINITY;   // row 0 (position t-1) cannot see the [MASK] row
-      if (k < nkeys) {
-        if (sub == 0) { sc[0][k] = d0; sc[1][k] = d1; }
-        mx0 = fmaxf(mx0, d0);
-        mx1 = fmaxf(mx1, d1);
-      }
+      DECODE_SCORE(k, kv[u], k < nkeys, true);
     }
   }
+#undef DECODE_SCORE
   mx0 = wave_max(mx0);
   mx1 = wave_max(mx1);
   if (lane == 0) { red[0][w] = mx0; red[1][w] = mx1; }
@@ -439,7 +471,32 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   float o0[8], o1[8], l0 = 0.f, l1 = 0.f;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { o0[j] = 0.f; o1[j] = 0.f; }
-  for (int kb = kslot; kb < nkeys; kb += 128) {
+#define DECODE_PV(k_, vv_, valid_)                                                                                  \
+  do {                                                                                                              \
+    if (valid_) {                                                                                                   \
+      const float p0 = fast_exp2(fmaf(sc[0][k_], c_log2, -m0)), p1 = fast_exp2(fmaf(sc[1][k_], c_log2, -m1));       \
+      l0 += p0;                                                                                                     \
+      l1 += p1;                                                                                                     \
+      const float p0b = (float)(__bf16)p0, p1b = (float)(__bf16)p1;                                                 \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                               \
+        const float vf = (float)(vv_)[j];                                                                           \
+        o0[j] = __builtin_fmaf(p0b, vf, o0[j]);                                                                     \
+        o1[j] = __builtin_fmaf(p1b, vf, o1[j]);                                                                     \
+      }                                                                                                             \
+    }                                                                                                               \
+  } while (0)
+  for (int k0 = 0; k0 < vis_full; k0 += 128) {
+    bf16x8 vv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) vv[u] = vis_load(k0 + u * 32, 1);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + kslot + u * 32;
+      DECODE_PV(k, vv[u], true);
+      if (u < 3) asm volatile("" : "+v"(o0[0]), "+v"(o1[7]), "+v"(vv[u + 1]) : : "memory");
+    }
+  }
+  for (int kb = vis_full + kslot; kb < nkeys; kb += 128) {
     bf16x8 vv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -449,20 +506,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = kb + u * 32;
-      if (k < nkeys) {
-        const float p0 = fast_exp2(fmaf(sc[0][k], c_log2, -m0)), p1 = fast_exp2(fmaf(sc[1][k], c_log2, -m1));
-        l0 += p0;
-        l1 += p1;
-        const float p0b = (float)(__bf16)p0, p1b = (float)(__bf16)p1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float vf = (float)vv[u][j];
-          o0[j] += p0b * vf;
-          o1[j] += p1b * vf;
-        }
-      }
+      DECODE_PV(k, vv[u], k < nkeys);
     }
   }
+#undef DECODE_PV
   // reduce over the 8 key slots of the wave (lanes with equal `sub`), then over waves through LDS
 #pragma unroll
   for (int o = 8; o < 64; o <<= 1) {
