@@ -44,14 +44,15 @@ extern "C" {
 #define VITCAP_OUT_F32 1
 
 const char* vitcap_last_error(void);
-/* ABI version of this header: bumped whenever a struct layout or a function signature changes (6: vitcap_gen_opts.cbs_no_repeat / cbs_bad_ending, vitcap_cbs_candidates' two
- * arguments; 5: vitcap_gemm_desc.ln_*; 4:
+/* ABI version of this header: bumped whenever a struct layout or a function signature changes (7: vitcap_score_req /
+ * vitcap_engine_score_req in place of the score_masked / explain / alternatives entry points; 6: vitcap_gen_opts.cbs_no_repeat /
+ * cbs_bad_ending, vitcap_cbs_candidates' two arguments; 5: vitcap_gemm_desc.ln_*; 4:
  * vitcap_gen_opts' constrained-beam-search block + the vitcap_cbs_* entry points; 3: `abi` heads vitcap_gemm_desc and
  * vitcap_gen_opts; 2 -> 3 also covers round 3's additions: gemm_desc.colsum, gen_opts.eos_extra / tag_pos0, vitcap_tag_embed's pos0,
  * vitcap_layernorm_bwd's extra pointer, zout / aux carrying gelu').  vitcap_version() returns the library's value: a binding checks
  * the two for equality at load time, and every call that takes one of the two option structs rejects a struct whose first field is
  * not VITCAP_ABI_VERSION (a caller built against an older header passes a shorter struct: its fields would be misread). */
-#define VITCAP_ABI_VERSION 6
+#define VITCAP_ABI_VERSION 7
 int vitcap_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -766,19 +767,92 @@ int vitcap_engine_generate_forced(vitcap_engine* e, const void* image, int image
  * per caption -- four decoder layers of full-size GEMMs, vitcap_attn_text_grid against the image's visual K/V, the LM head on the probe
  * rows (vocabulary GEMM in chunks of 2048 rows) and vitcap_score_rows.  Same rounding points as the step loop (fp32 residual stream,
  * bf16 GEMM operands and qkv); results agree with it within the bounds both meet against the reference, not bit for bit.
+ *
+ * One call is described by a vitcap_score_req, filled after vitcap_score_req_init and handed to vitcap_engine_score_req.  `kind` is a
+ * tag, not a bit set: it says which ONE of the extra field groups at the end of the struct is read; the fields of the other kinds
+ * are not looked at.  Fields every kind reads:
+ *   encode             1: encode + prefill `image` (image_is_bf16 as vitcap_engine_encode) into `workspace` first; 0: the call runs after
+ *                      vitcap_engine_encode + vitcap_engine_prefill on `workspace` and READS only the per-layer visual caches of it,
+ *                      so the same images can be scored again with other captions without re-encoding (`image` is not read)
+ *   B, opts, workspace, workspace_bytes   as the other engine calls take them
  *   caps_per_image     1..32 captions per image, image-major (vitcap_gen_opts.seqs_per_image is not read by these calls)
  *   caption_ids        device, int64 [B*caps_per_image][max_length]: [CLS] first, EOS-terminated, pad behind; copied by the call
  *   last_tok           device, int64 [B*caps_per_image] or NULL: vitcap_score_rows' last-column rule
  *   score_ws           device, 256-byte aligned, vitcap_engine_score_workspace_bytes(B, caps_per_image, opts) bytes: the text grid's
- *                      buffers (csrc/engine_layout.h: 0.66 GB at 64 images x 5 captions, 2.51 GB at 64 x 32, max_length 20)
+ *                      buffers (csrc/engine_layout.h: 0.66 GB at 64 images x 5 captions, 2.51 GB at 64 x 32, max_length 20).  Every
+ *                      kind uses this size: the extra results go straight to the caller's arrays
  *   out_logprobs       fp32 [B*caps];  out_ids int64 [B*caps][max_length];  out_token_logprobs fp32 [B*caps][max_length] or NULL;
- *                      out_last_tok int64 [B*caps] or NULL -- as vitcap_engine_decode_forced returns them
- * vitcap_engine_score_text runs after vitcap_engine_encode + vitcap_engine_prefill on `workspace` and READS only the per-layer visual
- * caches of it: the same images can be scored again with other captions without re-encoding.  vitcap_engine_score = encode + prefill
- * + score_text.  Refused with VITCAP_EINVAL before anything is enqueued, the option named in vitcap_last_error(): num_beams > 1,
- * use_cbs, tag_visible > 0, sampling.do_sample, repetition_penalty != 1 (the stepwise path scores the penalised row), caps_per_image
- * outside 1..32, null ids / outputs; a score workspace that is too small: VITCAP_EWORKSPACE.  eos_extra and max_length 2..40 work as
- * in the plain calls.  No hipGraph is captured for this path (use_graph is ignored). */
+ *                      out_last_tok int64 [B*caps] or NULL -- as vitcap_engine_decode_forced returns them.  Bit-identical in all
+ *                      four kinds (MASKED: with all 578 bits set)
+ * Refusals, before anything is enqueued and in this order: a null request or one of another ABI, a kind outside 0..3; the options,
+ * named in vitcap_last_error() -- num_beams > 1, use_cbs, tag_visible > 0, sampling.do_sample, repetition_penalty != 1 (the stepwise
+ * path scores the penalised row), caps_per_image outside 1..32; the batch; the kind's own fields (below); null ids / outputs; a score
+ * workspace that is too small: VITCAP_EWORKSPACE, everything before it VITCAP_EINVAL.  eos_extra and max_length 2..40 work as in the
+ * plain calls.  No hipGraph is captured for this path (use_graph is ignored).
+ *
+ * VITCAP_SCORE_PLAIN reads nothing more.  vitcap_engine_score_text / vitcap_engine_score are this kind with positional arguments
+ * (encode = 0 / 1).
+ *
+ * VITCAP_SCORE_MASKED -- "would this word survive without this region": visual keys hidden from the captions
+ * (vitcap_attn_text_grid_masked in place of vitcap_attn_text_grid in all four decoder layers, the same mask in each, as the
+ * reference applies its attention_mask).
+ *   vis_mask    device uint32 [B*caps_per_image][19], 4-byte aligned, laid out as vitcap_attn_text_grid_masked takes it.  It is READ
+ *               IN PLACE by the enqueued kernels, not copied: the caller keeps it alive and unchanged until the stream gets there.
+ * The mask hides visual TOKENS from the CAPTION's rows.  It does not hide patches from the encoder: vitcap_engine_encode, the prefill
+ * and the visual rows' own attention among themselves are untouched, so a hidden patch has still shaped its neighbours' tokens.
+ * A null or misaligned vis_mask is VITCAP_EINVAL.
+ *
+ * VITCAP_SCORE_MAPS -- "where did the model look for this word": the pass also writes the attention maps of the captions' [MASK]
+ * probes (vitcap_attn_probe_maps after the qkv GEMM of every selected decoder layer; the reference's attention_probs,
+ * modeling_bert.py:320-342, 484-510, mask 846-876).  vitcap_attn_probe_maps reads no mask, which is why this kind does not combine
+ * with MASKED.
+ *   maps        device fp32, per_head = 0: [B*caps][max_length][4][W] (head mean), per_head = 1: [B*caps][max_length][4][12][W],
+ *               W = 578 + max_length; rows, columns and zeros as vitcap_attn_probe_maps defines them
+ *   per_head    0 or 1
+ *   layer_mask  bit l selects decoder layer l (1..15).  The slices of unselected layers are left untouched.
+ * A null `maps`, a per_head other than 0 / 1 or a layer_mask outside 1..15 is VITCAP_EINVAL.
+ *
+ * VITCAP_SCORE_ALTS -- "what else could the model have said here": the pass also keeps what it saw in the vocabulary at every
+ * position (vitcap_score_rows_alts on every chunk of the vocabulary GEMM, in one kernel that does vitcap_score_rows' job for the chunk
+ * too).
+ *   k                  1..16 alternatives per position
+ *   alt_ids, alt_lp    device, int32 / fp32 [B*caps][max_length][k]
+ *   rank, entropy      device, int32 / fp32 [B*caps][max_length]
+ * as vitcap_score_rows_alts defines them; column 0 and the positions behind a caption's end hold alt_ids = rank = -1 and
+ * alt_lp = entropy = 0 (the call sets all four arrays to that pattern first).  k outside 1..16 or a null output array is
+ * VITCAP_EINVAL. */
+enum { VITCAP_SCORE_PLAIN = 0, VITCAP_SCORE_MASKED = 1, VITCAP_SCORE_MAPS = 2, VITCAP_SCORE_ALTS = 3 };
+typedef struct vitcap_score_req {
+  int32_t abi;                 /* VITCAP_ABI_VERSION, set by vitcap_score_req_init, checked first */
+  int32_t kind;                /* one of VITCAP_SCORE_*: which extra outputs / inputs below are read */
+  int32_t encode;              /* 1: encode + prefill `image` first; 0: the workspace holds the prefill */
+  const void* image;
+  int32_t image_is_bf16;
+  int32_t B;
+  const vitcap_gen_opts* opts;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t caps_per_image;
+  const int64_t* caption_ids;
+  const int64_t* last_tok;
+  void* score_ws;
+  size_t score_ws_bytes;
+  float* out_logprobs;
+  float* out_token_logprobs;
+  int64_t* out_ids;
+  int64_t* out_last_tok;
+  const uint32_t* vis_mask;    /* MASKED */
+  float* maps;                 /* MAPS */
+  int32_t per_head;
+  int32_t layer_mask;
+  int32_t k;                   /* ALTS */
+  int32_t* alt_ids;
+  float* alt_lp;
+  int32_t* rank;
+  float* entropy;
+} vitcap_score_req;
+void vitcap_score_req_init(vitcap_score_req* r);   /* zeros, abi, kind = VITCAP_SCORE_PLAIN */
+int vitcap_engine_score_req(vitcap_engine* e, const vitcap_score_req* r, void* stream);
 size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image, const vitcap_gen_opts* opts);
 int vitcap_engine_score_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                              int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
@@ -788,64 +862,6 @@ int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, 
                         size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
                         size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
                         void* stream);
-/* "Would this word survive without this region": the one-pass scoring pass with visual keys hidden from the captions
- * (vitcap_attn_text_grid_masked in place of vitcap_attn_text_grid in all four decoder layers, the same mask in each, as the
- * reference applies its attention_mask).  Arguments, refusals and results as vitcap_engine_score_text / vitcap_engine_score, plus
- *   vis_mask    device uint32 [B*caps_per_image][19], 4-byte aligned, laid out as vitcap_attn_text_grid_masked takes it.  It is READ
- *               IN PLACE by the enqueued kernels, not copied: the caller keeps it alive and unchanged until the stream gets there.
- * The mask hides visual TOKENS from the CAPTION's rows.  It does not hide patches from the encoder: vitcap_engine_encode, the prefill
- * and the visual rows' own attention among themselves are untouched, so a hidden patch has still shaped its neighbours' tokens.
- * With all 578 bits set the results are bit-identical to vitcap_engine_score_text / vitcap_engine_score.  A null vis_mask is
- * VITCAP_EINVAL, refused with the batch checks before anything is enqueued.  The score workspace is that of
- * vitcap_engine_score_workspace_bytes. */
-int vitcap_engine_score_masked_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
-                                    int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
-                                    size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
-                                    int64_t* out_last_tok, const uint32_t* vis_mask, void* stream);
-int vitcap_engine_score_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
-                               void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, const uint32_t* vis_mask,
-                               void* stream);
-/* "Where did the model look for this word": the one-pass scoring pass, which also writes the attention maps of the captions' [MASK]
- * probes (vitcap_attn_probe_maps after the qkv GEMM of every selected decoder layer; the reference's attention_probs,
- * modeling_bert.py:320-342, 484-510, mask 846-876).  Arguments, refusals and results as vitcap_engine_score_text /
- * vitcap_engine_score -- the scores are returned too and are bit-identical to those calls' -- plus
- *   maps        device fp32, per_head = 0: [B*caps][max_length][4][W] (head mean), per_head = 1: [B*caps][max_length][4][12][W],
- *               W = 578 + max_length; rows, columns and zeros as vitcap_attn_probe_maps defines them
- *   per_head    0 or 1
- *   layer_mask  bit l selects decoder layer l (1..15).  The slices of unselected layers are left untouched.
- * A null `maps`, a layer_mask outside 1..15 or a per_head other than 0 / 1 is VITCAP_EINVAL.  The score workspace is that of
- * vitcap_engine_score_workspace_bytes: the maps go straight to the caller's array. */
-int vitcap_engine_explain_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
-                               int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
-                               size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
-                               int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* stream);
-int vitcap_engine_explain(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts, void* workspace,
-                          size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok,
-                          void* score_ws, size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
-                          int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* stream);
-/* "What else could the model have said here": the one-pass scoring pass, which also keeps what it saw in the vocabulary at every
- * position (vitcap_score_rows_alts on every chunk of the vocabulary GEMM, in one kernel that does vitcap_score_rows' job for the chunk
- * too).  Arguments, refusals and results as vitcap_engine_score_text / vitcap_engine_score -- the scores, per-token log-probs and ids
- * are bit-identical to those calls' -- plus
- *   k                  1..16 alternatives per position
- *   alt_ids, alt_lp    device, int32 / fp32 [B*caps][max_length][k]
- *   rank, entropy      device, int32 / fp32 [B*caps][max_length]
- * as vitcap_score_rows_alts defines them; column 0 and the positions behind a caption's end hold alt_ids = rank = -1 and
- * alt_lp = entropy = 0 (the call sets all four arrays to that pattern first).  Refusals in this order: the options, the batch, k
- * outside 1..16 or a null output array (VITCAP_EINVAL), io, workspace.  The score workspace is that of
- * vitcap_engine_score_workspace_bytes: the results go straight to the caller's arrays. */
-int vitcap_engine_alternatives_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
-                                    int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
-                                    size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
-                                    int64_t* out_last_tok, int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy,
-                                    void* stream);
-int vitcap_engine_alternatives(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
-                               void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
-                               float* alt_lp, int32_t* rank, float* entropy, void* stream);
 /* copies the tag head's outputs of the last encode on this workspace (either pointer may be NULL) */
 int vitcap_engine_tags(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, float* tag_logits_out,
                        int64_t* tag_topk_out, void* stream);

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import alternatives_ref as R
+from score_request_calls import entry_points
 
 BOS, EOS, PAD = 101, 102, 0
 
@@ -203,16 +204,8 @@ def test_engine_alternatives_entry_points_refuse_without_a_device(L):
     assert lib.vitcap_engine_create(C.byref(h)) == 0 and h.value
     buf = (C.c_char * 1024)()
     a = C.c_void_p((C.addressof(buf) + 255) & ~255)
-    big = 1 << 40
-
-    def text(o, K=1, ids=a, sws=a, sws_bytes=big, lp=a, out_ids=a, k=5, ai=a, al=a, rk=a, en=a, B=1):
-        return lib.vitcap_engine_alternatives_text(h, B, C.byref(o) if o is not None else None, a, 512, K, ids, None, sws, sws_bytes, lp,
-                                                   None, out_ids, None, k, ai, al, rk, en, None)
-
-    def whole(o, K=1, ids=a, sws=a, sws_bytes=big, lp=a, out_ids=a, k=5, ai=a, al=a, rk=a, en=a, B=1):
-        return lib.vitcap_engine_alternatives(h, a, 0, B, C.byref(o) if o is not None else None, a, 512, K, ids, None, sws, sws_bytes, lp,
-                                              None, out_ids, None, k, ai, al, rk, en, None)
-
+    text, whole = entry_points(L, h, a, L.SCORE_ALTS, {'k': 'k', 'ai': 'alt_ids', 'al': 'alt_lp', 'rk': 'rank', 'en': 'entropy'},
+                               k=5, ai=a, al=a, rk=a, en=a)
     sp = L.SampleParams(1, 1.0, 0, 1.0, 0)
     refused = ((L.gen_opts(num_beams=2), b'num_beams'),
                (L.gen_opts(use_cbs=1, cbs_states=8, fsm=4096, num_constraints=4096), b'use_cbs'),
@@ -261,7 +254,7 @@ def test_score_rows_alts_launcher_refuses_bad_arguments(L):
 
 
 def test_new_symbols_are_exported(L):
-    for name in ('vitcap_score_rows_alts', 'vitcap_engine_alternatives', 'vitcap_engine_alternatives_text'):
+    for name in ('vitcap_score_rows_alts', 'vitcap_engine_score_req'):
         assert name in L.EXPORTS and getattr(L.lib, name) is not None
     from vitcap_amd import ops
     assert callable(ops.score_rows_alts)

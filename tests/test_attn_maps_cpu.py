@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import attn_maps_ref as R
+from score_request_calls import entry_points
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOS, EOS, PAD = 101, 102, 0
@@ -187,16 +188,8 @@ def test_engine_explain_entry_points_refuse_without_a_device(L):
     assert lib.vitcap_engine_create(C.byref(h)) == 0 and h.value
     buf = (C.c_char * 1024)()
     a = C.c_void_p((C.addressof(buf) + 255) & ~255)
-    big = 1 << 40
-
-    def text(o, K=1, ids=a, sws=a, sws_bytes=big, lp=a, out_ids=a, maps=a, per_head=0, mask=15):
-        return lib.vitcap_engine_explain_text(h, 1, C.byref(o) if o is not None else None, a, 512, K, ids, None, sws, sws_bytes, lp, None,
-                                              out_ids, None, maps, per_head, mask, None)
-
-    def whole(o, K=1, ids=a, sws=a, sws_bytes=big, lp=a, out_ids=a, maps=a, per_head=0, mask=15):
-        return lib.vitcap_engine_explain(h, a, 0, 1, C.byref(o) if o is not None else None, a, 512, K, ids, None, sws, sws_bytes, lp, None,
-                                         out_ids, None, maps, per_head, mask, None)
-
+    text, whole = entry_points(L, h, a, L.SCORE_MAPS, {'maps': 'maps', 'per_head': 'per_head', 'mask': 'layer_mask'},
+                               maps=a, per_head=0, mask=15)
     sp = L.SampleParams(1, 1.0, 0, 1.0, 0)
     refused = ((L.gen_opts(num_beams=2), b'num_beams'),
                (L.gen_opts(use_cbs=1, cbs_states=8, fsm=4096, num_constraints=4096), b'use_cbs'),

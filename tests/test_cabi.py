@@ -155,6 +155,41 @@ def test_struct_sizes_match_header(L):
     assert L.GenOpts.fsm.offset % 8 == 0 and C.sizeof(L.CbsState) == 8 * 8
 
 
+def test_score_request_struct(L):
+    """vitcap_score_req: vitcap_score_req_init sets abi and kind = PLAIN and zeros the rest; a null request, a request of another
+    ABI and a kind outside 0..3 are refused; and every field sits where the ctypes mirror puts it -- each value below is set through
+    the mirror and comes back in the message of the refusal it causes, so a shifted field fails here."""
+    from score_request_calls import aligned, entry_points
+    lib = L.lib
+    r = L.ScoreReq()
+    C.memset(C.byref(r), 0xff, C.sizeof(r))
+    lib.vitcap_score_req_init(C.byref(r))
+    assert r.abi == L.ABI_VERSION and r.kind == L.SCORE_PLAIN == 0
+    assert all(not getattr(r, n) for n, _ in L.ScoreReq._fields_ if n != 'abi')
+    # 3 ints, (pad), pointer, 2 ints, 2 pointers, size, int, (pad), 3 pointers, size, 4 pointers | pointer | pointer, 2 ints | int, (pad), 4 pointers
+    assert C.sizeof(L.ScoreReq) == 16 + 8 + 8 + 16 + 8 + 8 + 24 + 8 + 32 + 8 + 16 + 8 + 32
+    assert (L.SCORE_MASKED, L.SCORE_MAPS, L.SCORE_ALTS) == (1, 2, 3)
+    h = C.c_void_p()
+    assert lib.vitcap_engine_create(C.byref(h)) == 0 and h.value
+    buf = (C.c_char * 1024)()
+    a = aligned(buf)
+    assert lib.vitcap_engine_score_req(h, None, None) == -1 and b'null request' in lib.vitcap_last_error()
+    stale = L.score_req(abi=L.ABI_VERSION - 1)
+    assert lib.vitcap_engine_score_req(h, C.byref(stale), None) == -1 and b'ABI' in lib.vitcap_last_error()
+    for kind in (4, -1):
+        text, whole = entry_points(L, h, a, kind, {})
+        for fn in (text, whole):
+            assert fn(None) == -1 and b'kind' in lib.vitcap_last_error() and b'got %d' % kind in lib.vitcap_last_error()
+    need = lib.vitcap_engine_score_workspace_bytes(1, 1, None)
+    for kind, names, kw, echo in ((L.SCORE_ALTS, {'k': 'k'}, dict(k=17), b'got 17'),
+                                  (L.SCORE_MAPS, {'maps': 'maps', 'layer_mask': 'layer_mask'}, dict(maps=a, layer_mask=16), b'got 16'),
+                                  (L.SCORE_PLAIN, {}, dict(K=33), b'got 33'),
+                                  (L.SCORE_PLAIN, {}, dict(sws_bytes=need - 1), b'%d < required %d bytes' % (need - 1, need))):
+        for fn in entry_points(L, h, a, kind, names):
+            assert fn(None, **kw) == (-3 if 'sws_bytes' in kw else -1) and echo in lib.vitcap_last_error(), (kw, lib.vitcap_last_error())
+    lib.vitcap_engine_destroy(h)
+
+
 def test_model_surface(L, sd_np):
     from vitcap_amd.model import ImageCaptioning
     m = ImageCaptioning(tie_weights=True).load_recipe(0)

@@ -1,5 +1,5 @@
-"""Token alternatives of given captions on the device: vitcap_score_rows_alts (through ops.score_rows_alts), vitcap_engine_alternatives /
-vitcap_engine_alternatives_text (through vitcap_amd/model.py's alternatives / alternatives_encoded / caption_with_alternatives) and
+"""Token alternatives of given captions on the device: vitcap_score_rows_alts (through ops.score_rows_alts), vitcap_engine_score_req
+with kind VITCAP_SCORE_ALTS (through vitcap_amd/model.py's alternatives / alternatives_encoded / caption_with_alternatives) and
 the pipeline's `alternatives: k`.
 
 Bounds.  The op against the fp64 restatement of the row rule (tests/alternatives_ref.py): alt_ids and rank exact; alt_lp within 2e-5
@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import alternatives_ref as R
+from test_hip_score_onepass import _images, _variants
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +45,6 @@ def model():
     m = ImageCaptioning(tie_weights=True, tagemb='cls').load_recipe(0).eval()
     m.pack('cuda')
     return m
-
-
-def _images(n, seed=1234):
-    from vitcap_amd import weights as W
-    return torch.from_numpy(W.gen_image_batch(n, seed))
 
 
 # ------------------------------------------------------------------------------------------------ inputs, shared and never modified
@@ -210,16 +206,6 @@ def test_bit_identity_with_score_rows(ops, V, ldl):
 
 
 # ------------------------------------------------------------------------------------------------ engine helpers
-def _variants(c, K):
-    """K captions per image: its own, then its own with one word changed (another position and another word each)."""
-    caps = c.repeat_interleave(K, 0).clone()
-    L = c.shape[1]
-    for i in range(c.shape[0]):
-        for j in range(1, K):
-            caps[K * i + j, 1 + (2 * j) % (L - 2)] = 2023 + 40 * i + j
-    return caps
-
-
 def _identities(caps, tlp, alts, what, eos_ids=(EOS,)):
     """The identities of test 2 on an engine result -> the number of alternatives that are their position's scored token."""
     caps, tlp = caps.cpu(), tlp.cpu()

@@ -1,5 +1,5 @@
 """Attention maps of given captions on the device: vitcap_attn_probe_maps (through ops.attn_probe_maps and directly),
-vitcap_engine_explain / vitcap_engine_explain_text (through vitcap_amd/model.py's attention_maps / attention_maps_encoded /
+vitcap_engine_score_req with kind VITCAP_SCORE_MAPS (through vitcap_amd/model.py's attention_maps / attention_maps_encoded /
 caption_with_maps and directly).
 
 Bounds.  The op against the fp64 restatement of the row definition (tests/attn_maps_ref.py): |p - p_ref| <= 2e-4 p_ref + 1e-7,
@@ -15,6 +15,8 @@ import pytest
 import torch
 
 import attn_maps_ref as R
+from test_hip_score_onepass import _greedy_opts, _images
+from test_hip_score_request import MAPS, raw_request
 
 pytestmark = pytest.mark.gpu
 
@@ -54,11 +56,6 @@ def model():
 @pytest.fixture(scope='module')
 def fixture():
     return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_attn.npz')))
-
-
-def _images(n, seed=1234):
-    from vitcap_amd import weights as W
-    return torch.from_numpy(W.gen_image_batch(n, seed))
 
 
 _CASES = {}
@@ -210,33 +207,6 @@ def test_probe_maps_refusals_on_the_device(ops):
 
 
 # ------------------------------------------------------------------------------------------------ engine helpers
-def _greedy_opts(m, **over):
-    return m.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
-
-
-def _raw_explain(m, img, caps, K, o, per_head, mask, staged=False, maps=None):
-    """vitcap_engine_explain (img given) or vitcap_engine_explain_text (staged: the slot-0 workspace holds the prefill) called
-    directly -> (rc, logprob, token_logprobs, ids)."""
-    from vitcap_amd._lib import lib
-    dev = m._packed[2]
-    B = caps.shape[0] // K
-    ws, need = m._workspace(B, dev, 0, o)
-    sneed = lib.vitcap_engine_score_workspace_bytes(B, K, C.byref(o))
-    sws = torch.empty(max(sneed, 256), dtype=torch.uint8, device=dev)
-    rows, L = caps.shape
-    lp = torch.empty((rows,), dtype=torch.float32, device=dev)
-    tlp = torch.empty((rows, L), dtype=torch.float32, device=dev)
-    ids = torch.empty((rows, 1, L), dtype=torch.int64, device=dev)
-    capd = caps.to(dev).contiguous()
-    tail = (K, p(capd), None, p(sws), sneed, p(lp), p(tlp), p(ids), None, p(maps), per_head, mask, S())
-    if staged:
-        rc = lib.vitcap_engine_explain_text(m._engine, B, C.byref(o), p(ws), need, *tail)
-    else:
-        rc = lib.vitcap_engine_explain(m._engine, p(img), int(img.dtype == torch.bfloat16), B, C.byref(o), p(ws), need, *tail)
-    torch.cuda.synchronize()
-    return rc, lp, tlp, ids
-
-
 # ------------------------------------------------------------------------------------------------ 4
 def test_attention_maps_against_the_reference(model, fixture):
     """attention_maps() on the reference's own greedy captions of the two seeded images against the reference's attention_probs
@@ -300,7 +270,7 @@ def test_generate_is_unchanged_by_an_attention_maps_call(model, fixture):
 
 
 def test_unselected_layers_are_left_untouched(model, fixture):
-    """vitcap_engine_explain / vitcap_engine_explain_text directly, layer_mask 0b0101 into a sentinel-filled array: layers 1 and 3
+    """VITCAP_SCORE_MAPS requests (encode = 1 and 0) directly, layer_mask 0b0101 into a sentinel-filled array: layers 1 and 3
     and the canary around the array keep the sentinel, layers 0 and 2 are those of a full call; a zero mask, a null array and a bad
     per_head are refused with nothing written."""
     img = _images(2).cuda()
@@ -309,7 +279,7 @@ def test_unselected_layers_are_left_untouched(model, fixture):
     _, _, full = model.attention_maps(img, caps)
     for staged in (False, True):
         buf, maps = _framed((2, LMAX, 4, SV + LMAX))
-        rc, lp, tlp, ids = _raw_explain(model, img, caps, 1, o, 0, 0b0101, staged=staged, maps=maps)
+        rc, lp, tlp, ids, _ = raw_request(model, img, caps, 1, o, kind=MAPS, staged=staged, maps=maps, per_head=0, layer_mask=0b0101)
         assert rc == 0
         assert _canary_ok(buf, maps.shape) and bool((maps[:, :, [1, 3]] == SENT).all())
         assert torch.equal(maps[:, :, [0, 2]], full[:, :, [0, 2]])
@@ -317,8 +287,9 @@ def test_unselected_layers_are_left_untouched(model, fixture):
     from vitcap_amd._lib import lib
     buf, maps = _framed((2, LMAX, 4, SV + LMAX))
     for kw, name in ((dict(per_head=0, mask=0), b'layer_mask'), (dict(per_head=0, mask=16), b'layer_mask'), (dict(per_head=2, mask=15), b'per_head')):
-        assert _raw_explain(model, img, caps, 1, o, kw['per_head'], kw['mask'], maps=maps)[0] == -1 and name in lib.vitcap_last_error()
-    assert _raw_explain(model, img, caps, 1, o, 0, 15, maps=None)[0] == -1 and b'maps' in lib.vitcap_last_error()
+        assert raw_request(model, img, caps, 1, o, kind=MAPS, maps=maps, per_head=kw['per_head'], layer_mask=kw['mask'])[0] == -1
+        assert name in lib.vitcap_last_error()
+    assert raw_request(model, img, caps, 1, o, kind=MAPS, maps=None, per_head=0, layer_mask=15)[0] == -1 and b'maps' in lib.vitcap_last_error()
     assert bool((buf == SENT).all())
 
 

@@ -1,5 +1,5 @@
-"""Occlusion maps of given captions on the device: vitcap_attn_text_grid_masked, vitcap_engine_score_masked /
-vitcap_engine_score_masked_text (directly and through vitcap_amd/model.py's score_masked / score_masked_encoded / occlusion_maps /
+"""Occlusion maps of given captions on the device: vitcap_attn_text_grid_masked, vitcap_engine_score_req with kind
+VITCAP_SCORE_MASKED (directly and through vitcap_amd/model.py's score_masked / score_masked_encoded / occlusion_maps /
 visual_gain / caption_with_occlusion) and the pipeline's `occlusion: window`.
 
 Bounds.  Attention: |err| <= 2e-3 + 2^-7 |want| against the rounding emulation, the bound of tests/test_hip_score_onepass.py test 1.
@@ -16,6 +16,7 @@ import torch
 import occlusion_ref as R
 from test_hip_score_onepass import (BOS, EOS, LMAX, PAD, SEQ_TOL, SV, TOK_TOL, S, _bf, _close, _greedy_opts, _images, _rand, _raw_score,
                                     _variants, p)
+from test_hip_score_request import MASKED, raw_request
 
 pytestmark = pytest.mark.gpu
 
@@ -132,31 +133,6 @@ def test_attn_text_grid_masked_refusals(ops):
 
 
 # ------------------------------------------------------------------------------------------------ 5
-def _raw_masked(m, img, caps, K, o, mask, staged=False, sws_bytes=None, sentinel=None):
-    """vitcap_engine_score_masked (img given) or vitcap_engine_score_masked_text (staged) called directly, as
-    test_hip_score_onepass._raw_score calls the plain pair -> (rc, logprob, token_logprobs, ids, last_tok)."""
-    from vitcap_amd._lib import lib
-    dev = m._packed[2]
-    B = caps.shape[0] // K
-    ws, need = m._workspace(B, dev, 0, o)
-    sneed = lib.vitcap_engine_score_workspace_bytes(B, K, C.byref(o))
-    sws = torch.empty(max(sneed, 256), dtype=torch.uint8, device=dev)
-    rows, L = caps.shape
-    fill = (lambda *s, **k: torch.full(*s, fill_value=sentinel, **k)) if sentinel is not None else torch.empty
-    lp = fill((rows,), dtype=torch.float32, device=dev)
-    tlp = fill((rows, L), dtype=torch.float32, device=dev)
-    ids = fill((rows, 1, L), dtype=torch.int64, device=dev)
-    last = fill((rows,), dtype=torch.int64, device=dev)
-    capd = caps.to(dev).contiguous()
-    tail = (K, p(capd), None, p(sws), sneed if sws_bytes is None else sws_bytes, p(lp), p(tlp), p(ids), p(last), p(mask), S())
-    if staged:
-        rc = lib.vitcap_engine_score_masked_text(m._engine, B, C.byref(o), p(ws), need, *tail)
-    else:
-        rc = lib.vitcap_engine_score_masked(m._engine, p(img), int(img.dtype == torch.bfloat16), B, C.byref(o), p(ws), need, *tail)
-    torch.cuda.synchronize()
-    return rc, lp, tlp, ids, last
-
-
 def test_score_masked_all_ones_is_score_one_pass(model):
     """score_masked with everything visible equals score(one_pass=True) bit for bit -- logprob, token_logprobs and ids -- in both
     shapes of `visible`, and differs once keys are hidden."""
@@ -176,7 +152,7 @@ def test_score_masked_all_ones_is_score_one_pass(model):
 
 
 def test_engine_score_masked_staged_and_grouping(model):
-    """vitcap_engine_score_masked equals prefill + vitcap_engine_score_masked_text bit for bit; 12 variants per image equal three
+    """A VITCAP_SCORE_MASKED request with encode = 1 equals prefill + the same request with encode = 0 bit for bit; 12 variants per image equal three
     K = 4 calls bit for bit; generate() afterwards is unchanged and so are the K / V columns of dqkv0..3."""
     img = _images(2, 57).cuda()
     ids0, lp0 = model.generate(img)
@@ -187,16 +163,16 @@ def test_engine_score_masked_staged_and_grouping(model):
     visible[0] = True
     visible[13] = False
     mask = _pack(visible)
-    whole = _raw_masked(model, img, caps, 12, o, mask)
+    whole = raw_request(model, img, caps, 12, o, kind=MASKED, vis_mask=mask)
     assert whole[0] == 0 and bool(torch.isfinite(whole[1]).all())
     model.run(img, o, want_last=True)
     taps = [model.tap('dqkv%d' % l, 2, (2 * SV, 2304), dtype=torch.bfloat16, opts=o) for l in range(4)]
     assert float(taps[0][:, 768:].float().abs().max()) > 0
-    staged = _raw_masked(model, None, caps, 12, o, mask, staged=True)
+    staged = raw_request(model, None, caps, 12, o, kind=MASKED, vis_mask=mask, staged=True)
     assert staged[0] == 0 and all(torch.equal(x, y) for x, y in zip(staged[1:], whole[1:]))
     c3, m3 = caps.view(2, 3, 4, LMAX), mask.view(2, 3, 4, 19)
     for j in range(3):
-        part = _raw_masked(model, None, c3[:, j].reshape(8, LMAX), 4, o, m3[:, j].reshape(8, 19).contiguous(), staged=True)
+        part = raw_request(model, None, c3[:, j].reshape(8, LMAX), 4, o, kind=MASKED, vis_mask=m3[:, j].reshape(8, 19).contiguous(), staged=True)
         sel = (torch.arange(2)[:, None] * 12 + j * 4 + torch.arange(4)[None]).reshape(-1)
         assert part[0] == 0
         for x, y in zip(part[1:], whole[1:]):
@@ -232,16 +208,16 @@ def test_engine_score_masked_refusals_on_the_device(model):
 
     for staged in (False, True):
         for bad, name in refused:
-            r = _raw_masked(model, img, caps, 1, bad, mask, staged=staged, sentinel=-7)
+            r = raw_request(model, img, caps, 1, bad, kind=MASKED, vis_mask=mask, staged=staged, sentinel=-7)
             assert r[0] == -1 and name in lib.vitcap_last_error() and untouched(r), name
-        r = _raw_masked(model, img, caps.repeat(33, 1), 33, o, mask, staged=staged, sentinel=-7)
+        r = raw_request(model, img, caps.repeat(33, 1), 33, o, kind=MASKED, vis_mask=mask, staged=staged, sentinel=-7)
         assert r[0] == -1 and b'caps_per_image' in lib.vitcap_last_error() and untouched(r)
-        r = _raw_masked(model, img, caps, 1, o, None, staged=staged, sentinel=-7)
+        r = raw_request(model, img, caps, 1, o, kind=MASKED, vis_mask=None, staged=staged, sentinel=-7)
         assert r[0] == -1 and b'vis_mask is null' in lib.vitcap_last_error() and untouched(r)
         need = lib.vitcap_engine_score_workspace_bytes(1, 1, C.byref(o))
-        r = _raw_masked(model, img, caps, 1, o, mask, staged=staged, sws_bytes=need - 1, sentinel=-7)
+        r = raw_request(model, img, caps, 1, o, kind=MASKED, vis_mask=mask, staged=staged, sws_bytes=need - 1, sentinel=-7)
         assert r[0] == -3 and untouched(r)
-    r = _raw_masked(model, img, caps, 1, o, mask, sentinel=-7)       # and the accepted call writes every output
+    r = raw_request(model, img, caps, 1, o, kind=MASKED, vis_mask=mask, sentinel=-7)       # and the accepted call writes every output
     assert r[0] == 0 and not untouched(r) and bool(torch.isfinite(r[1]).all())
 
 

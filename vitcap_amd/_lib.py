@@ -23,7 +23,7 @@ OUT_BF16, OUT_F32 = 0, 1
 vp = C.c_void_p
 
 
-ABI_VERSION = 6          # include/vitcap_hip.h VITCAP_ABI_VERSION: checked against vitcap_version() when the library is loaded
+ABI_VERSION = 7          # include/vitcap_hip.h VITCAP_ABI_VERSION: checked against vitcap_version() when the library is loaded
 
 
 class GemmDesc(C.Structure):
@@ -76,6 +76,20 @@ class GenOpts(C.Structure):
                 # constrained beam search (ViTCAP.generate use_cbs / fsm / num_constraints / min_constraints_to_satisfy)
                 ('use_cbs', C.c_int32), ('cbs_states', C.c_int32), ('min_constraints_to_satisfy', C.c_int32),
                 ('cbs_no_repeat', C.c_int32), ('fsm', C.c_void_p), ('num_constraints', C.c_void_p), ('cbs_bad_ending', C.c_int32 * 16)]
+
+
+SCORE_PLAIN, SCORE_MASKED, SCORE_MAPS, SCORE_ALTS = 0, 1, 2, 3      # VITCAP_SCORE_*
+
+
+class ScoreReq(C.Structure):
+    """vitcap_score_req: one one-pass scoring call (vitcap_engine_score_req); `kind` says which of the trailing field groups is read."""
+    _fields_ = [('abi', C.c_int32), ('kind', C.c_int32), ('encode', C.c_int32), ('image', vp), ('image_is_bf16', C.c_int32),
+                ('B', C.c_int32), ('opts', C.POINTER(GenOpts)), ('workspace', vp), ('workspace_bytes', C.c_size_t),
+                ('caps_per_image', C.c_int32), ('caption_ids', vp), ('last_tok', vp), ('score_ws', vp), ('score_ws_bytes', C.c_size_t),
+                ('out_logprobs', vp), ('out_token_logprobs', vp), ('out_ids', vp), ('out_last_tok', vp),
+                ('vis_mask', vp),                                                               # SCORE_MASKED
+                ('maps', vp), ('per_head', C.c_int32), ('layer_mask', C.c_int32),               # SCORE_MAPS
+                ('k', C.c_int32), ('alt_ids', vp), ('alt_lp', vp), ('rank', vp), ('entropy', vp)]      # SCORE_ALTS
 
 
 class CbsState(C.Structure):
@@ -252,18 +266,8 @@ _SIGS = {
                                            vp, vp]),
     'vitcap_engine_score': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
                                       vp, vp, vp, vp, vp]),
-    'vitcap_engine_score_masked_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp,
-                                                  vp, vp, vp, vp]),
-    'vitcap_engine_score_masked': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
-                                             vp, vp, vp, vp, vp, vp]),
-    'vitcap_engine_explain_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp, vp,
-                                             vp, vp, C.c_int, C.c_int, vp]),
-    'vitcap_engine_explain': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
-                                        vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
-    'vitcap_engine_alternatives_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp,
-                                                  vp, vp, C.c_int, vp, vp, vp, vp, vp]),
-    'vitcap_engine_alternatives': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t,
-                                             vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    'vitcap_score_req_init': (None, [C.POINTER(ScoreReq)]),
+    'vitcap_engine_score_req': (C.c_int, [vp, C.POINTER(ScoreReq), vp]),
     'vitcap_engine_tags': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, vp, vp, vp]),
     'vitcap_engine_graph_count': (C.c_int, [vp]),
     'vitcap_engine_tap': (vp, [vp, C.c_char_p, vp, C.c_int, C.POINTER(GenOpts)]),
@@ -322,6 +326,25 @@ def gen_opts(**kw):
                 raise AttributeError('vitcap_gen_opts has no field %r' % k)
             setattr(o, k, v)
     return o
+
+
+def score_req(**kw):
+    """vitcap_score_req as vitcap_score_req_init leaves it (kind = SCORE_PLAIN), fields overridden by keyword: a tensor gives its
+    data pointer, `opts` a GenOpts (or None).  The request keeps the tensors and the options it points to alive."""
+    r = ScoreReq()
+    lib.vitcap_score_req_init(C.byref(r))
+    r._keep = []
+    for k, v in kw.items():
+        if not hasattr(r, k):
+            raise AttributeError('vitcap_score_req has no field %r' % k)
+        if k == 'opts':
+            r._keep.append(v)
+            v = C.pointer(v) if v is not None else None
+        elif hasattr(v, 'data_ptr'):
+            r._keep.append(v)
+            v = v.data_ptr()
+        setattr(r, k, v)
+    return r
 
 
 def check(rc, what=''):

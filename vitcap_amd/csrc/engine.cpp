@@ -1043,81 +1043,58 @@ int check_score(const vitcap_gen_opts& o, int caps_per_image) {
   return check_opts(o);
 }
 
-struct ScoreIO {
-  const int64_t* caption_ids;
-  const int64_t* last_tok;
-  float* out_logprobs;
-  float* out_tok_lp;
-  int64_t* out_ids;
-  int64_t* out_last_tok;
-};
+// prefix of the batch refusal, by vitcap_score_req.kind
+const char* const SCORE_WHO[4] = {"engine_score", "engine_score_masked", "engine_explain", "engine_alternatives"};
 
-int check_score_io(const ScoreIO& io, const ScoreLayout& sl, const void* sws, size_t sws_bytes) {
-  if (!io.caption_ids || !io.out_logprobs || !io.out_ids) { vitcap_set_error("engine_score: null caption_ids / outputs"); return VITCAP_EINVAL; }
-  if (!sws || ((uintptr_t)sws & 255) != 0) { vitcap_set_error("engine_score: score workspace null or not 256-byte aligned"); return VITCAP_EINVAL; }
-  if (sws_bytes < sl.off) {
-    vitcap_set_error("engine_score: score workspace %zu < required %zu bytes", sws_bytes, sl.off);
+int check_score_io(const vitcap_score_req& r, const ScoreLayout& sl) {
+  if (!r.caption_ids || !r.out_logprobs || !r.out_ids) { vitcap_set_error("engine_score: null caption_ids / outputs"); return VITCAP_EINVAL; }
+  if (!r.score_ws || ((uintptr_t)r.score_ws & 255) != 0) {
+    vitcap_set_error("engine_score: score workspace null or not 256-byte aligned");
+    return VITCAP_EINVAL;
+  }
+  if (r.score_ws_bytes < sl.off) {
+    vitcap_set_error("engine_score: score workspace %zu < required %zu bytes", r.score_ws_bytes, sl.off);
     return VITCAP_EWORKSPACE;
   }
   return VITCAP_OK;
 }
 
-// Attention maps of the probes (vitcap_engine_explain*): off for the scoring entry points, the way Forced is for decode_locked.
-struct Maps {
-  float* out = nullptr;      // the caller's [NC][L][4]([12])[W] array
-  int per_head = 0;
-  int layer_mask = 0;        // bit l: decoder layer l
-  bool on() const { return out != nullptr; }
-};
-
-int check_maps(const Maps& m) {
-  if (!m.out) { vitcap_set_error("engine_explain: maps is null"); return VITCAP_EINVAL; }
-  if (m.per_head != 0 && m.per_head != 1) { vitcap_set_error("engine_explain: per_head must be 0 or 1 (got %d)", m.per_head); return VITCAP_EINVAL; }
-  if (m.layer_mask < 1 || m.layer_mask > 15) {
-    vitcap_set_error("engine_explain: layer_mask must select at least one of the 4 decoder layers (1..15, got %d)", m.layer_mask);
+// VITCAP_SCORE_MAPS: attention maps of the probes, into the caller's [NC][L][4]([12])[W] array; layer_mask bit l: decoder layer l
+int check_maps(const vitcap_score_req& r) {
+  if (!r.maps) { vitcap_set_error("engine_explain: maps is null"); return VITCAP_EINVAL; }
+  if (r.per_head != 0 && r.per_head != 1) { vitcap_set_error("engine_explain: per_head must be 0 or 1 (got %d)", r.per_head); return VITCAP_EINVAL; }
+  if (r.layer_mask < 1 || r.layer_mask > 15) {
+    vitcap_set_error("engine_explain: layer_mask must select at least one of the 4 decoder layers (1..15, got %d)", r.layer_mask);
     return VITCAP_EINVAL;
   }
   return VITCAP_OK;
 }
 
-// Token alternatives of the probe rows (vitcap_engine_alternatives*): off for the scoring and the explain entry points.
-struct Alts {
-  int k = 0;
-  int32_t* ids = nullptr;    // the caller's [NC][L][k]
-  float* lp = nullptr;       // [NC][L][k]
-  int32_t* rank = nullptr;   // [NC][L]
-  float* entropy = nullptr;  // [NC][L]
-  bool on() const { return k > 0; }
-};
-
-int check_alts(const Alts& a) {
-  if (a.k < 1 || a.k > 16) { vitcap_set_error("engine_alternatives: k must be 1..16 (got %d)", a.k); return VITCAP_EINVAL; }
-  if (!a.ids || !a.lp || !a.rank || !a.entropy) {
+// VITCAP_SCORE_ALTS: token alternatives of the probe rows, into the caller's alt_ids / alt_lp [NC][L][k] and rank / entropy [NC][L]
+int check_alts(const vitcap_score_req& r) {
+  if (r.k < 1 || r.k > 16) { vitcap_set_error("engine_alternatives: k must be 1..16 (got %d)", r.k); return VITCAP_EINVAL; }
+  if (!r.alt_ids || !r.alt_lp || !r.rank || !r.entropy) {
     vitcap_set_error("engine_alternatives: null alt_ids / alt_lp / rank / entropy");
     return VITCAP_EINVAL;
   }
   return VITCAP_OK;
 }
 
-// Visual keys hidden from the captions (vitcap_engine_score_masked*): off for every other entry point.  The mask is the caller's
-// array, read in place by the attention launches of all four layers.
-struct Occl {
-  const uint32_t* vis_mask = nullptr;      // [NC][19], vitcap_attn_text_grid_masked's layout
-  bool on() const { return vis_mask != nullptr; }
-};
-
-// reads lo.dqkv[0..3] of `ws` (the visual caches of the prefill) and nothing else of it
-int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, const ScoreLayout& sl, char* sw,
-                 const ScoreIO& io, void* s, const Maps& mp = Maps(), const Alts& al = Alts(), const Occl& oc = Occl()) {
+// reads lo.dqkv[0..3] of the workspace (the visual caches of the prefill) and nothing else of it.  VITCAP_SCORE_MASKED: vis_mask
+// [NC][19] (vitcap_attn_text_grid_masked's layout) is the caller's array, read in place by the attention launches of all four layers.
+int score_locked(vitcap_engine* e, const vitcap_score_req& r, const vitcap_gen_opts& o, const Layout& lo, const ScoreLayout& sl, void* s) {
   hipStream_t st = (hipStream_t)s;
-  const int L = sl.L, R = sl.R, K = sl.K;
+  const int B = r.B, L = sl.L, R = sl.R, K = sl.K;
   const int NC = (int)sl.NC, M = (int)sl.M, P = (int)sl.P;
+  const bool masked = r.kind == VITCAP_SCORE_MASKED, maps = r.kind == VITCAP_SCORE_MAPS, alts = r.kind == VITCAP_SCORE_ALTS;
+  char* ws = (char*)r.workspace;
+  char* sw = (char*)r.score_ws;
   Enq q(e, B, o, lo, ws, s, Enq::ENCODE);
   const vitcap_weights& w = e->w;
   int64_t* ids = sl.ids.at<int64_t>(sw);
   int64_t* last = sl.last_tok.at<int64_t>(sw);
-  HIPCK(hipMemcpyAsync(ids, io.caption_ids, (size_t)NC * L * 8, hipMemcpyDeviceToDevice, st), "engine_score: caption ids copy");
-  if (io.last_tok) HIPCK(hipMemcpyAsync(last, io.last_tok, (size_t)NC * 8, hipMemcpyDeviceToDevice, st), "engine_score: last_tok copy");
+  HIPCK(hipMemcpyAsync(ids, r.caption_ids, (size_t)NC * L * 8, hipMemcpyDeviceToDevice, st), "engine_score: caption ids copy");
+  if (r.last_tok) HIPCK(hipMemcpyAsync(last, r.last_tok, (size_t)NC * 8, hipMemcpyDeviceToDevice, st), "engine_score: last_tok copy");
   else HIPCK(hipMemsetAsync(last, 0xff, (size_t)NC * 8, st), "engine_score: last_tok clear");
   float* x_f = sl.x_f.at<float>(sw);
   char* x_b = sw + sl.x_b;
@@ -1128,11 +1105,11 @@ int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout
     const vitcap_bert_layer_w& lw = w.dec[l];
     const char* vis = ws + lo.dqkv[l];
     CK(q.gemm(x_b, D, lw.qkv_w, lw.qkv_b, nullptr, 0, sw + sl.qkv, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
-    if (mp.on() && ((mp.layer_mask >> l) & 1))      // the caller's array, this layer's slice; reads qkv and the ids only
-      CK(vitcap_attn_probe_maps(sw + sl.qkv, vis, ids, mp.out + (size_t)l * (mp.per_head ? 12 : 1) * (SV + L), B, K, SV, L, mp.per_head,
+    if (maps && ((r.layer_mask >> l) & 1))      // the caller's array, this layer's slice; reads qkv and the ids only
+      CK(vitcap_attn_probe_maps(sw + sl.qkv, vis, ids, r.maps + (size_t)l * (r.per_head ? 12 : 1) * (SV + L), B, K, SV, L, r.per_head,
                                 o.eos_token_id, o.eos_extra, 0.125f, s));
     CK(vitcap_attn_beam_vt(vis, sw + sl.vt, B, SV, s));
-    if (oc.on()) CK(vitcap_attn_text_grid_masked(sw + sl.qkv, vis, sw + sl.vt, oc.vis_mask, sw + sl.ctx, B, K, SV, L, 0.125f, s));
+    if (masked) CK(vitcap_attn_text_grid_masked(sw + sl.qkv, vis, sw + sl.vt, r.vis_mask, sw + sl.ctx, B, K, SV, L, 0.125f, s));
     else CK(vitcap_attn_text_grid(sw + sl.qkv, vis, sw + sl.vt, sw + sl.ctx, B, K, SV, L, 0.125f, s));
     // BertSelfOutput / BertIntermediate / BertOutput: dense + residual, then LayerNorm (post-LN), as prefill_part
     CK(q.gemm_ln(sw + sl.ctx, D, lw.ao_w, lw.ao_b, x_f, sw + sl.tmp, M, D, lw.ao_g, lw.ao_beta, 1e-12f, sw + sl.sa_b, sl.sa_f.at<float>(sw)));
@@ -1143,26 +1120,61 @@ int score_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout
   CK(vitcap_copy_row_blocks(x_b, R, L, D, 0, sw + sl.hd_in, L - 1, 0, D, 0, L - 1, D, NC, s));
   CK(q.gemm(sw + sl.hd_in, D, w.cls.dense_w, w.cls.dense_b, nullptr, 0, sw + sl.hd_f, D, P, D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_F32));
   CK(vitcap_layernorm_fwd(sl.hd_f.at<float>(sw), D, w.cls.ln_g, w.cls.ln_b, 1e-12f, sw + sl.hd_b, nullptr, P, D, s));
-  float* tok_lp = io.out_tok_lp ? io.out_tok_lp : sl.tok_lp.at<float>(sw);
-  if (al.on()) {      // the dead pattern once: column 0 and whatever no launch covers; the chunks' launches write the rest
+  float* tok_lp = r.out_token_logprobs ? r.out_token_logprobs : sl.tok_lp.at<float>(sw);
+  if (alts) {      // the dead pattern once: column 0 and whatever no launch covers; the chunks' launches write the rest
     const size_t n = (size_t)NC * L;
-    HIPCK(hipMemsetAsync(al.ids, 0xff, n * al.k * 4, st), "engine_alternatives: alt_ids clear");
-    HIPCK(hipMemsetAsync(al.rank, 0xff, n * 4, st), "engine_alternatives: rank clear");
-    HIPCK(hipMemsetAsync(al.lp, 0, n * al.k * 4, st), "engine_alternatives: alt_lp clear");
-    HIPCK(hipMemsetAsync(al.entropy, 0, n * 4, st), "engine_alternatives: entropy clear");
+    HIPCK(hipMemsetAsync(r.alt_ids, 0xff, n * r.k * 4, st), "engine_alternatives: alt_ids clear");
+    HIPCK(hipMemsetAsync(r.rank, 0xff, n * 4, st), "engine_alternatives: rank clear");
+    HIPCK(hipMemsetAsync(r.alt_lp, 0, n * r.k * 4, st), "engine_alternatives: alt_lp clear");
+    HIPCK(hipMemsetAsync(r.entropy, 0, n * 4, st), "engine_alternatives: entropy clear");
   }
   for (int r0 = 0; r0 < P; r0 += (int)sl.CH) {
     const int n = P - r0 < (int)sl.CH ? P - r0 : (int)sl.CH;
     CK(q.gemm(sl.hd_b.at<char>(sw, (size_t)r0), D, w.cls.dec_w, w.cls.dec_b, nullptr, 0, sw + sl.logits, VP, n, VP, D, VITCAP_ACT_NONE,
               VITCAP_OUT_F32));
-    if (al.on())      // one kernel does vitcap_score_rows' job too: the 250 MB chunk is read once
+    if (alts)      // one kernel does vitcap_score_rows' job too: the 250 MB chunk is read once
       CK(vc_score_rows_alts(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
-                            tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, al.k, al.ids, al.lp, al.rank, al.entropy, s));
+                            tok_lp, r.out_ids, r.out_last_tok, r.out_logprobs, r.k, r.alt_ids, r.alt_lp, r.rank, r.entropy, s));
     else
       CK(vitcap_score_rows(sl.logits.at<float>(sw), VP, VITCAP_VOCAB, ids, last, r0, n, NC, L, o.eos_token_id, o.eos_extra, o.pad_token_id,
-                           nullptr, nullptr, tok_lp, io.out_ids, io.out_last_tok, io.out_logprobs, s));
+                           nullptr, nullptr, tok_lp, r.out_ids, r.out_last_tok, r.out_logprobs, s));
   }
   return VITCAP_OK;
+}
+
+// Every one-pass request, every refusal in one order: the request itself (null, ABI, kind), options, batch, the kind's own fields
+// (mask / maps / alternatives), io, workspace -- then, with `encode`, encode + prefill, then score_locked.
+int score_entry(vitcap_engine* e, const vitcap_score_req* rp, void* s) {
+  if (!rp) { vitcap_set_error("score_req: null request"); return VITCAP_EINVAL; }
+  const vitcap_score_req& r = *rp;
+  if (r.abi != VITCAP_ABI_VERSION) {
+    vitcap_set_error("score_req: built against ABI %d, this library is ABI %d (use vitcap_score_req_init)", r.abi, VITCAP_ABI_VERSION);
+    return VITCAP_EINVAL;
+  }
+  if (r.kind < VITCAP_SCORE_PLAIN || r.kind > VITCAP_SCORE_ALTS) {
+    vitcap_set_error("score_req: kind must be one of VITCAP_SCORE_* (0..3, got %d)", r.kind);
+    return VITCAP_EINVAL;
+  }
+  const vitcap_gen_opts o = opts_or_default(r.opts);
+  CK(check_score(o, r.caps_per_image));
+  if (r.B <= 0) { vitcap_set_error("%s: bad batch", SCORE_WHO[r.kind]); return VITCAP_EINVAL; }
+  if (r.kind == VITCAP_SCORE_MASKED) {
+    if (!r.vis_mask) { vitcap_set_error("engine_score_masked: vis_mask is null"); return VITCAP_EINVAL; }
+    if (((uintptr_t)r.vis_mask & 3) != 0) { vitcap_set_error("engine_score_masked: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
+  }
+  if (r.kind == VITCAP_SCORE_MAPS) CK(check_maps(r));
+  if (r.kind == VITCAP_SCORE_ALTS) CK(check_alts(r));
+  const ScoreLayout sl(r.B, r.caps_per_image, o.max_length);
+  CK(check_score_io(r, sl));
+  Layout lo;
+  CK(enter(e, r.B, o, r.workspace, r.workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (r.encode) {
+    char* ws = (char*)r.workspace;
+    CK(Enq(e, r.B, o, lo, ws, s, Enq::ENCODE).encode(r.image, r.image_is_bf16));
+    CK(Enq(e, r.B, o, lo, ws, s, Enq::ENCODE).prefill());
+  }
+  return score_locked(e, r, o, lo, sl, s);
 }
 
 }  // namespace
@@ -1173,132 +1185,47 @@ extern "C" size_t vitcap_engine_score_workspace_bytes(int B, int caps_per_image,
   return ScoreLayout(B, caps_per_image, o.max_length).off;
 }
 
+extern "C" void vitcap_score_req_init(vitcap_score_req* r) {
+  if (!r) return;
+  *r = vitcap_score_req();
+  r->abi = VITCAP_ABI_VERSION;
+  r->kind = VITCAP_SCORE_PLAIN;
+}
+
+extern "C" int vitcap_engine_score_req(vitcap_engine* e, const vitcap_score_req* r, void* s) { return score_entry(e, r, s); }
+
+// The plain request with positional arguments in place of the struct, as every integration starts.
 namespace {
-
-// The eight entry points of the one-pass pass: every refusal in one order -- options, batch (and, for the masked pair, the mask),
-// maps / alternatives (when asked for), io, workspace -- then, with an image, encode + prefill, then score_locked.  mp: the maps
-// description of the explain pair, al: the alternatives description of the alternatives pair, oc: the mask of the masked pair; all
-// null for the scoring pair.
-int score_entry(vitcap_engine* e, const void* image, int image_is_bf16, bool encode, int B, const vitcap_gen_opts* opts, void* workspace,
-                size_t workspace_bytes, int caps_per_image, const ScoreIO& io, void* score_ws, size_t score_ws_bytes, const Maps* mp,
-                void* s, const Alts* al = nullptr, const Occl* oc = nullptr) {
-  const vitcap_gen_opts o = opts_or_default(opts);
-  CK(check_score(o, caps_per_image));
-  if (B <= 0) {
-    vitcap_set_error("%s: bad batch", mp ? "engine_explain" : al ? "engine_alternatives" : oc ? "engine_score_masked" : "engine_score");
-    return VITCAP_EINVAL;
-  }
-  if (oc && !oc->vis_mask) { vitcap_set_error("engine_score_masked: vis_mask is null"); return VITCAP_EINVAL; }
-  if (oc && ((uintptr_t)oc->vis_mask & 3) != 0) { vitcap_set_error("engine_score_masked: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
-  if (mp) CK(check_maps(*mp));
-  if (al) CK(check_alts(*al));
-  const ScoreLayout sl(B, caps_per_image, o.max_length);
-  CK(check_score_io(io, sl, score_ws, score_ws_bytes));
-  Layout lo;
-  CK(enter(e, B, o, workspace, workspace_bytes, lo));
-  char* ws = (char*)workspace;
-  std::lock_guard<std::mutex> lk(e->mu);
-  if (encode) {
-    CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
-    CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
-  }
-  return score_locked(e, B, o, lo, ws, sl, (char*)score_ws, io, s, mp ? *mp : Maps(), al ? *al : Alts(), oc ? *oc : Occl());
+vitcap_score_req plain_req(int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes, int caps_per_image,
+                           const int64_t* caption_ids, const int64_t* last_tok, void* score_ws, size_t score_ws_bytes,
+                           float* out_logprobs, float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok) {
+  vitcap_score_req r;
+  vitcap_score_req_init(&r);
+  r.B = B; r.opts = opts; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.caps_per_image = caps_per_image; r.caption_ids = caption_ids; r.last_tok = last_tok;
+  r.score_ws = score_ws; r.score_ws_bytes = score_ws_bytes;
+  r.out_logprobs = out_logprobs; r.out_token_logprobs = out_token_logprobs; r.out_ids = out_ids; r.out_last_tok = out_last_tok;
+  return r;
 }
-
-Alts alts_of(int k, int32_t* alt_ids, float* alt_lp, int32_t* rank, float* entropy) {
-  Alts al;
-  al.k = k; al.ids = alt_ids; al.lp = alt_lp; al.rank = rank; al.entropy = entropy;
-  return al;
-}
-
-Maps maps_of(float* maps, int per_head, int layer_mask) {
-  Maps mp;
-  mp.out = maps; mp.per_head = per_head; mp.layer_mask = layer_mask;
-  return mp;
-}
-
 }  // namespace
 
 extern "C" int vitcap_engine_score_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                                         int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
                                         size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
                                         int64_t* out_last_tok, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s);
+  const vitcap_score_req r = plain_req(B, opts, workspace, workspace_bytes, caps_per_image, caption_ids, last_tok, score_ws, score_ws_bytes,
+                                       out_logprobs, out_token_logprobs, out_ids, out_last_tok);
+  return score_entry(e, &r, s);
 }
 
 extern "C" int vitcap_engine_score(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
                                    void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
                                    const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
                                    float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
-                     nullptr, s);
-}
-
-extern "C" int vitcap_engine_score_masked_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace,
-                                               size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok,
-                                               const uint32_t* vis_mask, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  Occl oc;
-  oc.vis_mask = vis_mask;
-  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s,
-                     nullptr, &oc);
-}
-
-extern "C" int vitcap_engine_score_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
-                                          void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                                          const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                                          float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, const uint32_t* vis_mask,
-                                          void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  Occl oc;
-  oc.vis_mask = vis_mask;
-  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
-                     nullptr, s, nullptr, &oc);
-}
-
-extern "C" int vitcap_engine_explain_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
-                                          int caps_per_image, const int64_t* caption_ids, const int64_t* last_tok, void* score_ws,
-                                          size_t score_ws_bytes, float* out_logprobs, float* out_token_logprobs, int64_t* out_ids,
-                                          int64_t* out_last_tok, float* maps, int per_head, int layer_mask, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  const Maps mp = maps_of(maps, per_head, layer_mask);
-  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, &mp, s);
-}
-
-extern "C" int vitcap_engine_explain(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
-                                     void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                                     const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                                     float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, float* maps, int per_head,
-                                     int layer_mask, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  const Maps mp = maps_of(maps, per_head, layer_mask);
-  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, &mp, s);
-}
-
-extern "C" int vitcap_engine_alternatives_text(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace,
-                                               size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                                               const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                                               float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
-                                               float* alt_lp, int32_t* rank, float* entropy, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  const Alts al = alts_of(k, alt_ids, alt_lp, rank, entropy);
-  return score_entry(e, nullptr, 0, false, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes, nullptr, s,
-                     &al);
-}
-
-extern "C" int vitcap_engine_alternatives(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
-                                          void* workspace, size_t workspace_bytes, int caps_per_image, const int64_t* caption_ids,
-                                          const int64_t* last_tok, void* score_ws, size_t score_ws_bytes, float* out_logprobs,
-                                          float* out_token_logprobs, int64_t* out_ids, int64_t* out_last_tok, int k, int32_t* alt_ids,
-                                          float* alt_lp, int32_t* rank, float* entropy, void* s) {
-  const ScoreIO io{caption_ids, last_tok, out_logprobs, out_token_logprobs, out_ids, out_last_tok};
-  const Alts al = alts_of(k, alt_ids, alt_lp, rank, entropy);
-  return score_entry(e, image, image_is_bf16, true, B, opts, workspace, workspace_bytes, caps_per_image, io, score_ws, score_ws_bytes,
-                     nullptr, s, &al);
+  vitcap_score_req r = plain_req(B, opts, workspace, workspace_bytes, caps_per_image, caption_ids, last_tok, score_ws, score_ws_bytes,
+                                 out_logprobs, out_token_logprobs, out_ids, out_last_tok);
+  r.encode = 1; r.image = image; r.image_is_bf16 = image_is_bf16;
+  return score_entry(e, &r, s);
 }
 
 extern "C" const void* vitcap_engine_tap(vitcap_engine* e, const char* name, void* workspace, int B, const vitcap_gen_opts* opts) {

@@ -475,9 +475,8 @@ class ImageCaptioning(nn.Module):
         from .forced import pack_forced
         K = int(seqs_per_image)
         if one_pass:
-            o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
-            dev = self._check_image(image)
-            return self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, return_ids)
+            image, B, o, cap, lt, dev = self._score_source('score', image, slot, caption_ids, K, last_tok, over)
+            return self._score_one_pass(image, B, o, cap, lt, K, slot, dev, return_ids)
         o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
         o.seqs_per_image = K
         check(lib.vitcap_gen_opts_check(C.byref(o)), 'gen_opts')
@@ -525,90 +524,90 @@ class ImageCaptioning(nn.Module):
         return sws, need
 
     def _score_one_pass(self, image, B, o, cap, lt, K, slot, dev, return_ids, maps=None, alts=None, vis=None):
-        """vitcap_engine_score (image given) or vitcap_engine_score_text (image None: the slot's workspace holds the prefill).
-        vis = packed visibility words int32 (rows, 19) (vitcap_amd.occlusion.pack_visible): vitcap_engine_score_masked /
-        vitcap_engine_score_masked_text instead; same results as the plain pair.
-        maps = (per_head, layer_mask): vitcap_engine_explain / vitcap_engine_explain_text instead, -> (lp, tok_lp, ids, maps).
-        alts = k: vitcap_engine_alternatives / vitcap_engine_alternatives_text instead, -> (lp, tok_lp, ids, Alternatives)."""
+        """One vitcap_engine_score_req call: `image` is encoded first, or with image None the slot's workspace holds the prefill.
+        At most one of the three (vitcap_score_req.kind is a tag):
+        vis = packed visibility words int32 (rows, 19) (vitcap_amd.occlusion.pack_visible): SCORE_MASKED; results as SCORE_PLAIN.
+        maps = (per_head, layer_mask): SCORE_MAPS, -> (lp, tok_lp, ids, maps).
+        alts = k: SCORE_ALTS, -> (lp, tok_lp, ids, Alternatives)."""
         rows = B * K
-        cap = cap.to(dev).contiguous()
-        lt = None if lt is None else lt.to(dev).contiguous()
         ws, need = self._workspace(B, dev, slot, o)
         sws, sneed = self._score_workspace(B, K, o, dev, slot)
         lp = torch.empty((rows,), dtype=torch.float32, device=dev)
         tok_lp = torch.empty((rows, o.max_length), dtype=torch.float32, device=dev)
         ids = torch.empty((rows, 1, o.max_length), dtype=torch.int64, device=dev)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        tail = (K, C.c_void_p(cap.data_ptr()), C.c_void_p(lt.data_ptr()) if lt is not None else None, C.c_void_p(sws.data_ptr()), sneed,
-                C.c_void_p(lp.data_ptr()), C.c_void_p(tok_lp.data_ptr()), C.c_void_p(ids.data_ptr()), None, s)
+        req = L.score_req(B=B, opts=o, workspace=ws, workspace_bytes=need, caps_per_image=K, caption_ids=cap.to(dev).contiguous(),
+                          last_tok=None if lt is None else lt.to(dev).contiguous(), score_ws=sws, score_ws_bytes=sneed,
+                          out_logprobs=lp, out_token_logprobs=tok_lp, out_ids=ids)
+        if image is not None:
+            req.encode, req.image, req.image_is_bf16 = 1, image.data_ptr(), int(image.dtype == torch.bfloat16)
+        extra = ()
         if maps is not None:
             per_head, layer_mask = maps
             W = 578 + o.max_length
             out = torch.zeros((rows, o.max_length, 4) + ((12, W) if per_head else (W,)), dtype=torch.float32, device=dev)
-            tail = tail[:-1] + (C.c_void_p(out.data_ptr()), int(per_head), int(layer_mask), s)
-            if image is not None:
-                check(lib.vitcap_engine_explain(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                                C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_explain')
-                self._encoded[slot] = (o, B)
-            else:
-                check(lib.vitcap_engine_explain_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
-                      'engine_explain_text')
-            return lp, tok_lp, ids, out
-        if alts is not None:
+            req.kind, req.maps, req.per_head, req.layer_mask = L.SCORE_MAPS, out.data_ptr(), int(per_head), int(layer_mask)
+            extra = (out,)
+        elif alts is not None:
             from .alternatives import Alternatives
             k = int(alts)
             res = Alternatives(torch.empty((rows, o.max_length, k), dtype=torch.int32, device=dev),
                                torch.empty((rows, o.max_length, k), dtype=torch.float32, device=dev),
                                torch.empty((rows, o.max_length), dtype=torch.int32, device=dev),
                                torch.empty((rows, o.max_length), dtype=torch.float32, device=dev))      # the engine fills all of them
-            tail = tail[:-1] + (k,) + tuple(C.c_void_p(x.data_ptr()) for x in res) + (s,)
-            if image is not None:
-                check(lib.vitcap_engine_alternatives(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                                     C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_alternatives')
-                self._encoded[slot] = (o, B)
-            else:
-                check(lib.vitcap_engine_alternatives_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
-                      'engine_alternatives_text')
-            return lp, tok_lp, ids, res
-        if vis is not None:
+            req.kind, req.k = L.SCORE_ALTS, k
+            req.alt_ids, req.alt_lp, req.rank, req.entropy = (x.data_ptr() for x in res)
+            extra = (res,)
+        elif vis is not None:
             # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
             vis = vis.to(device=dev, dtype=torch.int32).contiguous()
             assert tuple(vis.shape) == (rows, 19)
-            tail = tail[:-1] + (C.c_void_p(vis.data_ptr()), s)
-            if image is not None:
-                check(lib.vitcap_engine_score_masked(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                                     C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score_masked')
-                self._encoded[slot] = (o, B)
-            else:
-                check(lib.vitcap_engine_score_masked_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail),
-                      'engine_score_masked_text')
-            return (lp, tok_lp, ids) if return_ids else (lp, tok_lp)
+            req.kind, req.vis_mask = L.SCORE_MASKED, vis.data_ptr()
+        check(lib.vitcap_engine_score_req(self._engine, C.byref(req), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              'engine_score_req')
         if image is not None:
-            check(lib.vitcap_engine_score(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
-                                          C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score')
             self._encoded[slot] = (o, B)
+        return (lp, tok_lp, ids) + extra if extra or return_ids else (lp, tok_lp)
+
+    def _score_source(self, who, image, slot, caption_ids, K, last_tok, over, then=None):
+        """The opening of every X / X_encoded pair: the host-side checks (_score_inputs), then `then(B)` -- checks of the caller that
+        need the batch -- and only then the device.  image None: the images of the last run() / generate*() / score() call on
+        `slot`, with the options laid out as that call's.  -> (image or None, B, opts, caption ids, last_tok or None, device)."""
+        if image is not None:
+            B = image.shape[0]
+            o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
         else:
-            check(lib.vitcap_engine_score_text(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, *tail), 'engine_score_text')
-        return (lp, tok_lp, ids) if return_ids else (lp, tok_lp)
+            if slot not in self._encoded:
+                raise RuntimeError('%s: no encoded images on slot %r (call run / generate / score on it first)' % (who, slot))
+            o_last, B = self._encoded[slot]
+            o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
+            o.seqs_per_image = o_last.seqs_per_image      # the workspace of that call, as it was laid out
+            if o.max_length != o_last.max_length or o_last.tag_visible > 0 or o_last.num_beams > 1 or o_last.use_cbs:
+                raise ValueError('%s: the last call on slot %r ran other options (max_length / tags / beams)' % (who, slot))
+        if then is not None:
+            then(B)
+        return image, B, o, cap, lt, (self._check_image(image) if image is not None else self._packed[2])
+
+    def _greedy_caption(self, who, what, image, slot, over):
+        """The opening of the caption_with_* calls: greedy captions only, then generate() through the staged path.  Takes the search
+        options out of `over`.  -> (opts, ids, logprobs, last_tok)."""
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
+            raise NotImplementedError('%s runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): %s under beam search, '
+                                      'CBS or sampling are not built'
+                                      % (who, te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False)), what))
+        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
+            over.pop(k, None)
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        return (o,) + self.run(image, o, slot=slot, want_last=True)
 
     def score_encoded(self, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
         """score(one_pass=True) against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
-        (vitcap_engine_score_text reads the visual K/V that call left in the slot's workspace).  The options that size the
+        (a vitcap_score_req with encode = 0 reads the visual K/V that call left in the slot's workspace).  The options that size the
         workspace (max_length) must be those of that call."""
-        B, o, cap, lt = self._encoded_inputs('score_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
-        return self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], return_ids)
-
-    def _encoded_inputs(self, who, slot, caption_ids, K, last_tok, over):
-        """The checks of the calls that run against a slot's already encoded images (score_encoded, attention_maps_encoded):
-        -> (B, opts laid out as that call's, caption ids, last_tok or None)."""
-        if slot not in self._encoded:
-            raise RuntimeError('%s: no encoded images on slot %r (call run / generate / score on it first)' % (who, slot))
-        o_last, B = self._encoded[slot]
-        o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
-        o.seqs_per_image = o_last.seqs_per_image      # the workspace of that call, as it was laid out
-        if o.max_length != o_last.max_length or o_last.tag_visible > 0 or o_last.num_beams > 1 or o_last.use_cbs:
-            raise ValueError('%s: the last call on slot %r ran other options (max_length / tags / beams)' % (who, slot))
-        return B, o, cap, lt
+        K = int(seqs_per_image)
+        image, B, o, cap, lt, dev = self._score_source('score_encoded', None, slot, caption_ids, K, last_tok, over)
+        return self._score_one_pass(image, B, o, cap, lt, K, slot, dev, return_ids)
 
     @staticmethod
     def _layer_mask(layers):
@@ -621,71 +620,58 @@ class ImageCaptioning(nn.Module):
             mask |= 1 << l
         return mask
 
+    def _attention_maps(self, who, image, caption_ids, seqs_per_image, per_head, layers, slot, last_tok, over):
+        K, mask = int(seqs_per_image), self._layer_mask(layers)
+        image, B, o, cap, lt, dev = self._score_source(who, image, slot, caption_ids, K, last_tok, over)
+        lp, tok_lp, _, maps = self._score_one_pass(image, B, o, cap, lt, K, slot, dev, False, maps=(bool(per_head), mask))
+        return lp, tok_lp, maps
+
     def attention_maps(self, image, caption_ids, seqs_per_image=1, per_head=False, layers=(0, 1, 2, 3), slot=0, last_tok=None, **over):
         """Where the model looked for each word of GIVEN captions: the softmax row of the [MASK] probe at every position t >= 1, in
         every selected decoder layer -- the reference's attention_probs[b, h, cur_len = t] (modeling_bert.py:320-342, 484-510) --
-        from the one-pass scoring pass (vitcap_engine_explain).  Inputs and refusals as score(one_pass=True).
+        from the one-pass scoring pass (a vitcap_score_req of kind VITCAP_SCORE_MAPS).  Inputs and refusals as score(one_pass=True).
         -> (logprobs (rows,), token_logprobs (rows, L), maps): maps fp32 (rows, L, 4, W), the mean over the 12 heads, or with
         per_head (rows, L, 4, 12, W); W = 578 + L, columns as vitcap_amd.attnmaps names them (0 tag cls, 1 encoder cls, 2..577 the
         24 x 24 patches, 578 + k token k, 578 + t the probe itself).  Position 0 and the positions behind a caption's first [SEP]
         are zeros; so are the layers not in `layers` (the engine leaves their slices untouched, the array starts zeroed)."""
-        K = int(seqs_per_image)
-        mask = self._layer_mask(layers)
-        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
-        dev = self._check_image(image)
-        lp, tok_lp, _, maps = self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, False, maps=(bool(per_head), mask))
-        return lp, tok_lp, maps
+        return self._attention_maps('attention_maps', image, caption_ids, seqs_per_image, per_head, layers, slot, last_tok, over)
 
     def attention_maps_encoded(self, caption_ids, seqs_per_image=1, per_head=False, layers=(0, 1, 2, 3), slot=0, last_tok=None, **over):
         """attention_maps() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
-        (vitcap_engine_explain_text); the conditions of score_encoded()."""
-        mask = self._layer_mask(layers)
-        B, o, cap, lt = self._encoded_inputs('attention_maps_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
-        lp, tok_lp, _, maps = self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], False,
-                                                   maps=(bool(per_head), mask))
-        return lp, tok_lp, maps
+        (the request's encode = 0); the conditions of score_encoded()."""
+        return self._attention_maps('attention_maps_encoded', None, caption_ids, seqs_per_image, per_head, layers, slot, last_tok, over)
 
     def caption_with_maps(self, image, per_head=False, layers=(0, 1, 2, 3), slot=0, **over):
         """Greedy captions and where the model looked for each of their words: generate() through the staged path, then
         attention_maps_encoded() on its own output (the token chosen at the last position handed over as last_tok).
         -> (ids (B, 1, L), logprobs (B, 1), maps)."""
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
-            raise NotImplementedError('caption_with_maps runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): attention '
-                                      'maps under beam search, CBS or sampling are not built'
-                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
-        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
-            over.pop(k, None)
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
-        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        o, ids, lp, last = self._greedy_caption('caption_with_maps', 'attention maps', image, slot, over)
         _, _, maps = self.attention_maps_encoded(ids.view(image.shape[0], o.max_length), 1, per_head=per_head, layers=layers, slot=slot,
                                                  last_tok=last, **over)
         return ids, lp, maps
 
+    def _alternatives(self, who, image, caption_ids, seqs_per_image, k, slot, last_tok, over):
+        from .alternatives import check_k
+        K, k = int(seqs_per_image), check_k(k)
+        image, B, o, cap, lt, dev = self._score_source(who, image, slot, caption_ids, K, last_tok, over)
+        lp, tok_lp, _, alts = self._score_one_pass(image, B, o, cap, lt, K, slot, dev, False, alts=k)
+        return lp, tok_lp, alts
+
     def alternatives(self, image, caption_ids, seqs_per_image=1, k=5, slot=0, last_tok=None, **over):
         """What the model would have said instead, at every position of GIVEN captions: from the logits of the one-pass scoring pass
-        (vitcap_engine_alternatives) the k best vocabulary entries per position with their log-probs, the rank of the scored word
-        among all 30522 and the entropy of the position's distribution.  Inputs and refusals as score(one_pass=True); k is 1..16.
+        (a vitcap_score_req of kind VITCAP_SCORE_ALTS) the k best vocabulary entries per position with their log-probs, the rank of
+        the scored word among all 30522 and the entropy of the position's distribution.  Inputs and refusals as score(one_pass=True);
+        k is 1..16.
         -> (logprobs (rows,), token_logprobs (rows, L), alts): alts a vitcap_amd.alternatives.Alternatives of ids int32 (rows, L, k)
         best first (ties to the lower id), logprobs fp32 (rows, L, k), rank int32 (rows, L) (0 = the scored word is the first
         choice) and entropy fp32 (rows, L) in nats.  Position 0 and the positions behind a caption's first [SEP] hold ids = rank =
         -1 and logprobs = entropy = 0.  Where ids equals the scored word, logprobs equals token_logprobs bit for bit."""
-        from .alternatives import check_k
-        K, k = int(seqs_per_image), check_k(k)
-        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
-        dev = self._check_image(image)
-        lp, tok_lp, _, alts = self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, False, alts=k)
-        return lp, tok_lp, alts
+        return self._alternatives('alternatives', image, caption_ids, seqs_per_image, k, slot, last_tok, over)
 
     def alternatives_encoded(self, caption_ids, seqs_per_image=1, k=5, slot=0, last_tok=None, **over):
         """alternatives() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
-        (vitcap_engine_alternatives_text); the conditions of score_encoded()."""
-        from .alternatives import check_k
-        k = check_k(k)
-        B, o, cap, lt = self._encoded_inputs('alternatives_encoded', slot, caption_ids, int(seqs_per_image), last_tok, over)
-        lp, tok_lp, _, alts = self._score_one_pass(None, B, o, cap, lt, int(seqs_per_image), slot, self._packed[2], False, alts=k)
-        return lp, tok_lp, alts
+        (the request's encode = 0); the conditions of score_encoded()."""
+        return self._alternatives('alternatives_encoded', None, caption_ids, seqs_per_image, k, slot, last_tok, over)
 
     def caption_with_alternatives(self, image, k=5, slot=0, want_token_logprobs=False, **over):
         """Greedy captions and, for each of their words, what else the model could have said: generate() through the staged path,
@@ -696,20 +682,18 @@ class ImageCaptioning(nn.Module):
         log-probs of the caption's words (B, L) come last."""
         from .alternatives import check_k
         k = check_k(k)
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
-            raise NotImplementedError('caption_with_alternatives runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): '
-                                      'alternatives under beam search, CBS or sampling are not built'
-                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
-        for n in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
-            over.pop(n, None)
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
-        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        o, ids, lp, last = self._greedy_caption('caption_with_alternatives', 'alternatives', image, slot, over)
         _, tok_lp, alts = self.alternatives_encoded(ids.view(image.shape[0], o.max_length), 1, k=k, slot=slot, last_tok=last, **over)
         return (ids, lp, alts, tok_lp) if want_token_logprobs else (ids, lp, alts)
 
-    # ---- occlusion: given captions scored with visual keys hidden from them (vitcap_engine_score_masked*)
+    # ---- occlusion: given captions scored with visual keys hidden from them (vitcap_score_req of kind VITCAP_SCORE_MASKED)
+    def _score_masked(self, who, image, caption_ids, visible, seqs_per_image, slot, return_ids, last_tok, over):
+        from .occlusion import as_visible, pack_visible
+        K, vis = int(seqs_per_image), []
+        image, B, o, cap, lt, dev = self._score_source(who, image, slot, caption_ids, K, last_tok, over,
+                                                       then=lambda B: vis.append(pack_visible(as_visible(visible, B * K))))
+        return self._score_one_pass(image, B, o, cap, lt, K, slot, dev, return_ids, vis=vis[0])
+
     def score_masked(self, image, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
         """score(one_pass=True) with visual keys hidden from the captions: `visible`, bool or uint8, one row per caption, either
         (rows, 578) in the cache's order (0 tag cls, 1 encoder cls, 2..577 the 24 x 24 patches row-major) or a (rows, 24, 24) patch
@@ -718,21 +702,12 @@ class ImageCaptioning(nn.Module):
         visual TOKENS from the CAPTION; the encoder and the prefill still see the whole image.  Inputs and refusals as
         score(one_pass=True); a wrong shape or dtype of `visible` is a ValueError before the GPU is touched.  With everything visible
         the results are score(one_pass=True)'s, bit for bit."""
-        from .occlusion import as_visible, pack_visible
-        K = int(seqs_per_image)
-        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
-        vis = pack_visible(as_visible(visible, image.shape[0] * K))
-        dev = self._check_image(image)
-        return self._score_one_pass(image, image.shape[0], o, cap, lt, K, slot, dev, return_ids, vis=vis)
+        return self._score_masked('score_masked', image, caption_ids, visible, seqs_per_image, slot, return_ids, last_tok, over)
 
     def score_masked_encoded(self, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
         """score_masked() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again
-        (vitcap_engine_score_masked_text); the conditions of score_encoded()."""
-        from .occlusion import as_visible, pack_visible
-        K = int(seqs_per_image)
-        B, o, cap, lt = self._encoded_inputs('score_masked_encoded', slot, caption_ids, K, last_tok, over)
-        vis = pack_visible(as_visible(visible, B * K))
-        return self._score_one_pass(None, B, o, cap, lt, K, slot, self._packed[2], return_ids, vis=vis)
+        (the request's encode = 0); the conditions of score_encoded()."""
+        return self._score_masked('score_masked_encoded', None, caption_ids, visible, seqs_per_image, slot, return_ids, last_tok, over)
 
     def _score_variants(self, image, B, o, cap, lt, masks, slot, dev):
         """Every caption of cap (B * K, L) under every mask row of `masks` bool (V, 578), in passes of at most 32 variants per image
@@ -753,9 +728,10 @@ class ImageCaptioning(nn.Module):
             toks.append(tok.view(B * K, n, L))
         return torch.cat(lps, 1), torch.cat(toks, 1)
 
-    def _occlusion(self, image, B, o, cap, lt, window, stride, keep_cls, keep_only, slot, dev):
+    def _occlusion_maps(self, who, image, caption_ids, window, stride, keep_cls, keep_only, slot, last_tok, over):
         from .occlusion import check_window, window_masks
         window, stride, g = check_window(window, stride)
+        image, B, o, cap, lt, dev = self._score_source(who, image, slot, caption_ids, 1, last_tok, over)
         masks = torch.cat([torch.ones((1, 578), dtype=torch.bool), window_masks(window, stride, keep_cls, keep_only)], 0)
         lp, tok = self._score_variants(image, B, o, cap, lt, masks, slot, dev)
         drop = tok[:, :1] - tok[:, 1:]                                 # (B, G, L)
@@ -771,19 +747,12 @@ class ImageCaptioning(nn.Module):
         drop[b, t, i, j] = token_logprobs[b, t] - the same with window (i, j) hidden; gh = gw = (24 - window) / stride + 1; zero at
         position 0 and behind the caption's end, where both terms are.  Occlusion hides visual tokens from the caption only: the
         encoder has seen the whole image.  Inputs and refusals as score(one_pass=True)."""
-        from .occlusion import check_window
-        check_window(window, stride)
-        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, 1, last_tok, over)
-        dev = self._check_image(image)
-        return self._occlusion(image, image.shape[0], o, cap, lt, window, stride, keep_cls, keep_only, slot, dev)
+        return self._occlusion_maps('occlusion_maps', image, caption_ids, window, stride, keep_cls, keep_only, slot, last_tok, over)
 
     def occlusion_maps_encoded(self, caption_ids, window=4, stride=None, keep_cls=True, keep_only=False, slot=0, last_tok=None, **over):
         """occlusion_maps() against the images of the last run() / generate*() / score() call on `slot`, without encoding them again;
         the conditions of score_encoded()."""
-        from .occlusion import check_window
-        check_window(window, stride)
-        B, o, cap, lt = self._encoded_inputs('occlusion_maps_encoded', slot, caption_ids, 1, last_tok, over)
-        return self._occlusion(None, B, o, cap, lt, window, stride, keep_cls, keep_only, slot, self._packed[2])
+        return self._occlusion_maps('occlusion_maps_encoded', None, caption_ids, window, stride, keep_cls, keep_only, slot, last_tok, over)
 
     def caption_with_occlusion(self, image, window=4, stride=None, keep_cls=True, keep_only=False, slot=0, **over):
         """Greedy captions and the occlusion maps of their words: generate() through the staged path, then occlusion_maps_encoded()
@@ -791,16 +760,7 @@ class ImageCaptioning(nn.Module):
         drop (B, L, gh, gw))."""
         from .occlusion import check_window
         check_window(window, stride)
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
-            raise NotImplementedError('caption_with_occlusion runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): '
-                                      'occlusion maps under beam search, CBS or sampling are not built'
-                                      % (te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False))))
-        for n in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
-            over.pop(n, None)
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
-        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        o, ids, lp, last = self._greedy_caption('caption_with_occlusion', 'occlusion maps', image, slot, over)
         _, _, drop = self.occlusion_maps_encoded(ids.view(image.shape[0], o.max_length), window, stride, keep_cls, keep_only, slot=slot,
                                                  last_tok=last, **over)
         return ids, lp, drop
@@ -809,11 +769,9 @@ class ImageCaptioning(nn.Module):
         """What the image added to each word of GIVEN captions: token_logprobs minus the token_logprobs with all 578 visual keys
         hidden from the caption (it then attends its own tokens only), from two variants per caption.  Inputs and refusals as
         score(one_pass=True).  -> fp32 (rows, L), zero at position 0 and behind a caption's end."""
-        K = int(seqs_per_image)
-        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, over)
-        dev = self._check_image(image)
+        image, B, o, cap, lt, dev = self._score_source('visual_gain', image, slot, caption_ids, int(seqs_per_image), last_tok, over)
         masks = torch.stack([torch.ones(578, dtype=torch.bool), torch.zeros(578, dtype=torch.bool)])
-        _, tok = self._score_variants(image, image.shape[0], o, cap, lt, masks, slot, dev)
+        _, tok = self._score_variants(image, B, o, cap, lt, masks, slot, dev)
         return tok[:, 0] - tok[:, 1]
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):

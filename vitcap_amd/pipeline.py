@@ -218,80 +218,76 @@ class _PredictRun(object):
             for entry in self.pending:
                 yield from self.collect(entry)
 
+    def analysed(self, batches, dev, pred_rows, mode, what, caption_with):
+        """The batch loop of the three analysis modes (cfg.attention_maps / alternatives / occlusion): the batches strictly one after
+        the other through `caption_with(image)`, one of ImageCaptioning.caption_with_* (no two-slot overlap; throughput is not a target
+        of these modes).  The callers pass gemm_mode = TILES, the GEMM form of the ordinary predict loop, so that the captions and
+        their confidences are that loop's, bit for bit.  Yields (batch, ids on the host, logprobs, what caption_with returned behind
+        them) per batch; the (key, json) rows caption_rows would give (about 100 B each) are appended to `pred_rows` when the
+        consumer comes back for the next batch."""
+        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        with torch.no_grad():
+            for batch in batches:
+                batch = dict(batch)
+                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
+                if model.check_text_inputs(batch, L) != 0:
+                    raise NotImplementedError('%s: visible tag slots (tag_visible > 0) are not built for the %s' % (mode, what))
+                ids, lp, *extras = caption_with(batch['image'])
+                ids_h = ids.cpu()
+                yield batch, ids_h, lp, extras
+                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+
     def attention_rows(self, batches, dev, pred_rows):
-        """cfg.attention_maps: the batches strictly one after the other through ImageCaptioning.caption_with_maps (no two-slot
-        overlap; throughput is not a target of this mode), with the GEMM form of the ordinary predict loop (gemm_mode = TILES) so
-        that the captions and their confidences are that loop's, bit for bit.  Yields the rows of the attention TSV, one per image
-        (about 30 KB each: they are streamed to their file); the (key, json) rows caption_rows would give (about 100 B each) are
-        appended to `pred_rows`."""
+        """cfg.attention_maps: yields the rows of the attention TSV, one per image (about 30 KB each: they are streamed to their
+        file), from the last decoder layer's maps of ImageCaptioning.caption_with_maps."""
         import base64
         import numpy as np
         from .attnmaps import patch_grid
         model, L = self.model, int(self.pipe.cfg.max_gen_length)
         vocab = self.pipe.tokenizer.ids_to_tokens
         eos = set(int(e) for e in (model.test_extra_input.get('eos_token_ids') or [102]))
-        with torch.no_grad():
-            for batch in batches:
-                batch = dict(batch)
-                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
-                if model.check_text_inputs(batch, L) != 0:
-                    raise NotImplementedError('attention_maps: visible tag slots (tag_visible > 0) are not built for the attention maps')
-                ids, lp, maps = model.caption_with_maps(batch['image'], layers=(3,), gemm_mode=1)
-                ids_h, grids = ids.cpu(), patch_grid(maps[:, :, 3]).to(torch.float16).cpu().numpy()      # (B, L, 24, 24)
-                for b, key in enumerate(batch['key']):
-                    toks = ids_h[b, 0].tolist()
-                    ends = [t for t in range(1, L) if toks[t] in eos]
-                    n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
-                    data = np.ascontiguousarray(grids[b, 1:n + 1])
-                    yield key, json.dumps({'tokens': [vocab[i] for i in toks[1:n + 1]], 'layer': 3, 'shape': [n, 24, 24],
-                                           'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
-                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+        for batch, ids_h, lp, (maps,) in self.analysed(batches, dev, pred_rows, 'attention_maps', 'attention maps',
+                                                       lambda img: model.caption_with_maps(img, layers=(3,), gemm_mode=1)):
+            grids = patch_grid(maps[:, :, 3]).to(torch.float16).cpu().numpy()      # (B, L, 24, 24)
+            for b, key in enumerate(batch['key']):
+                toks = ids_h[b, 0].tolist()
+                ends = [t for t in range(1, L) if toks[t] in eos]
+                n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
+                data = np.ascontiguousarray(grids[b, 1:n + 1])
+                yield key, json.dumps({'tokens': [vocab[i] for i in toks[1:n + 1]], 'layer': 3, 'shape': [n, 24, 24],
+                                       'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
 
     def alternative_rows(self, batches, dev, pred_rows, k):
-        """cfg.alternatives = k: the batches strictly one after the other through ImageCaptioning.caption_with_alternatives, as
-        attention_rows runs them (gemm_mode = TILES: the captions and confidences are the ordinary predict loop's, bit for bit).
-        Yields the rows of the alternatives TSV, one per image: the key and a JSON list with one record per live position of the
-        predicted caption -- word, log-prob, rank, entropy and the k (word, log-prob) alternatives, all of the one-pass pass."""
+        """cfg.alternatives = k: yields the rows of the alternatives TSV, one per image: the key and a JSON list with one record per
+        live position of the predicted caption -- word, log-prob, rank, entropy and the k (word, log-prob) alternatives, all of the
+        one-pass pass (ImageCaptioning.caption_with_alternatives)."""
         from .alternatives import to_words
         model, L = self.model, int(self.pipe.cfg.max_gen_length)
         vocab = self.pipe.tokenizer.ids_to_tokens
-        with torch.no_grad():
-            for batch in batches:
-                batch = dict(batch)
-                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
-                if model.check_text_inputs(batch, L) != 0:
-                    raise NotImplementedError('alternatives: visible tag slots (tag_visible > 0) are not built for the alternatives')
-                ids, lp, alts, tok_lp = model.caption_with_alternatives(batch['image'], k=k, want_token_logprobs=True, gemm_mode=1)
-                ids_h, alts_h, tok_lp_h = ids.cpu(), type(alts)(*(x.cpu() for x in alts)), tok_lp.cpu()
-                for b, key in enumerate(batch['key']):
-                    toks, words = ids_h[b, 0].tolist(), to_words(self.pipe.tokenizer, alts_h, b)
-                    rank, ent, own = alts_h.rank[b].tolist(), alts_h.entropy[b].tolist(), tok_lp_h[b].tolist()
-                    # word: the caption's token as written (a [SEP] the max-length rule wrote into the last column is scored as the
-                    # loop's own choice there); logprob, rank: the scored word's in the one-pass pass
-                    recs = [{'word': vocab[toks[t]], 'logprob': own[t], 'rank': rank[t], 'entropy': ent[t],
-                             'alternatives': [[w, q] for w, q in words[t]]} for t in range(1, L) if rank[t] >= 0]
-                    yield key, json.dumps(recs)
-                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+        for batch, ids_h, lp, (alts, tok_lp) in self.analysed(
+                batches, dev, pred_rows, 'alternatives', 'alternatives',
+                lambda img: model.caption_with_alternatives(img, k=k, want_token_logprobs=True, gemm_mode=1)):
+            alts_h, tok_lp_h = type(alts)(*(x.cpu() for x in alts)), tok_lp.cpu()
+            for b, key in enumerate(batch['key']):
+                toks, words = ids_h[b, 0].tolist(), to_words(self.pipe.tokenizer, alts_h, b)
+                rank, ent, own = alts_h.rank[b].tolist(), alts_h.entropy[b].tolist(), tok_lp_h[b].tolist()
+                # word: the caption's token as written (a [SEP] the max-length rule wrote into the last column is scored as the
+                # loop's own choice there); logprob, rank: the scored word's in the one-pass pass
+                recs = [{'word': vocab[toks[t]], 'logprob': own[t], 'rank': rank[t], 'entropy': ent[t],
+                         'alternatives': [[w, q] for w, q in words[t]]} for t in range(1, L) if rank[t] >= 0]
+                yield key, json.dumps(recs)
 
     def occlusion_rows(self, batches, dev, pred_rows, window):
-        """cfg.occlusion = window: the batches strictly one after the other through ImageCaptioning.caption_with_occlusion, as
-        attention_rows runs them (gemm_mode = TILES: the captions and confidences are the ordinary predict loop's, bit for bit).
-        Yields the rows of the occlusion TSV, one per image: the key and a JSON list with one record per live position of the
-        predicted caption -- the word and its gh x gw log-prob drops (vitcap_amd.occlusion.to_rows)."""
+        """cfg.occlusion = window: yields the rows of the occlusion TSV, one per image: the key and a JSON list with one record per
+        live position of the predicted caption -- the word and its gh x gw log-prob drops (vitcap_amd.occlusion.to_rows) of
+        ImageCaptioning.caption_with_occlusion."""
         from .occlusion import to_rows
-        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        model = self.model
         eos = model.test_extra_input.get('eos_token_ids') or [102]
-        with torch.no_grad():
-            for batch in batches:
-                batch = dict(batch)
-                batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
-                if model.check_text_inputs(batch, L) != 0:
-                    raise NotImplementedError('occlusion: visible tag slots (tag_visible > 0) are not built for the occlusion maps')
-                ids, lp, drop = model.caption_with_occlusion(batch['image'], window=window, gemm_mode=1)
-                ids_h = ids.cpu()
-                for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
-                    yield key, json.dumps(recs)
-                pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+        for batch, ids_h, lp, (drop,) in self.analysed(batches, dev, pred_rows, 'occlusion', 'occlusion maps',
+                                                       lambda img: model.caption_with_occlusion(img, window=window, gemm_mode=1)):
+            for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
+                yield key, json.dumps(recs)
 
     def counted(self, rows):
         """images/s of the steady state: from the moment the first two batches' captions have come back (model warm, loader
