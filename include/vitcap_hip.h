@@ -266,6 +266,16 @@ int vitcap_attn_dense_bwd_rows(const void* qkv, const void* out, const void* dou
 int vitcap_attn_decode_step(const void* qkv_step, const void* vis_qkv, void* text_kv, void* out,
                             int B, int S_vis, int t, int max_len, int seq_per_image, float scale,
                             void* stream);
+/* The same with visual keys hidden from single sequences (region captions).  vis_mask: device, uint32 [B][mask_words] with
+ * mask_words >= ceil(S_vis / 32), one row per SEQUENCE (not per image: the sequences of an image may see different regions); bit
+ * k & 31 of word k >> 5 set = visual key k is visible, bits from S_vis on are ignored -- at S_vis = 578 the [rows][19] layout of
+ * vitcap_attn_text_grid_masked.  A hidden key's score is -inf for both query rows of the step before the row maximum is taken;
+ * the text cache, the step's own two rows and the published cache row are untouched, so no softmax row is empty.  With every bit
+ * set the output is bit-identical to vitcap_attn_decode_step.  Argument checks as vitcap_attn_decode_step, plus VITCAP_EINVAL for
+ * a null or 4-byte-misaligned mask and for mask_words < ceil(S_vis / 32). */
+int vitcap_attn_decode_step_masked(const void* qkv_step, const void* vis_qkv, void* text_kv, void* out,
+                                   int B, int S_vis, int t, int max_len, int seq_per_image, float scale,
+                                   const uint32_t* vis_mask, int mask_words, void* stream);
 /* The same with the predicted tag tokens visible to the caption rows (the mask CaptionTensorizer builds when
  * a text_b of n_tag tag tokens is attached, dataset.py:240-252, 387-390): n_tag more keys per image between the visual and the
  * text keys.  tag_qkv_a / tag_qkv_b: bf16 [B/seq_per_image][n_tag][2304] packed like vis_qkv, the tag rows' K/V under the two
@@ -762,6 +772,23 @@ int vitcap_engine_generate_forced(vitcap_engine* e, const void* image, int image
                                   void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
                                   int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
                                   int64_t* tag_topk_out, void* stream);
+/* The `_forced` calls with visual tokens hidden from single sequences: captions the model writes about a part of the image, up to
+ * 8 parts per image on one encoder pass (seqs_per_image), and -- with forced_ids and score_forced = 1 -- the stepwise counterpart
+ * of VITCAP_SCORE_MASKED.
+ *   vis_mask  device, uint32 [B*seqs_per_image][19], image-major, the layout of vitcap_attn_decode_step_masked at S_vis = 578.
+ *             Read in place by every step's attention launches: it must stay valid and unchanged until `stream` has run them.
+ * forced_ids may be NULL (free decoding).  seqs_per_image 1..8, sampling, repetition_penalty, eos_extra, decode_streams and
+ * encode_parts work as in the `_forced` calls.  Refused with VITCAP_EINVAL and the option's name in vitcap_last_error(), before
+ * anything is enqueued: num_beams > 1, use_cbs, tag_visible > 0, use_graph = 1 (a captured loop would freeze this call's mask
+ * pointer; the mask is not staged in the workspace), a null or 4-byte-misaligned vis_mask.  The mask hides visual TOKENS from the
+ * caption: a hidden patch has still shaped its neighbours and the cls tokens inside the encoder. */
+int vitcap_engine_decode_masked(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                float* out_token_logprobs, int64_t* out_last_tok, const uint32_t* vis_mask, void* stream);
+int vitcap_engine_generate_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                  void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
+                                  int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
+                                  int64_t* tag_topk_out, const uint32_t* vis_mask, void* stream);
 /* One-pass scoring of GIVEN captions: every token is known in advance, so the max_length - 1 sequential steps of
  * vitcap_engine_decode_forced(score_forced = 1) become one pass over a [token rows | [MASK] probe rows] grid of 2 * max_length - 1 rows
  * per caption -- four decoder layers of full-size GEMMs, vitcap_attn_text_grid against the image's visual K/V, the LM head on the probe

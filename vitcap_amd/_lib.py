@@ -194,6 +194,8 @@ _SIGS = {
                                              C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'vitcap_attn_decode_step': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_float, vp]),
+    'vitcap_attn_decode_step_masked': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_float, vp, C.c_int, vp]),
     'vitcap_attn_decode_step_tags': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp,
                                                C.c_int, vp, vp]),
     'vitcap_tag_embed': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp,
@@ -261,6 +263,9 @@ _SIGS = {
     'vitcap_engine_decode_forced': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp]),
     'vitcap_engine_generate_forced': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,
                                                 vp, vp, vp, vp, vp, vp]),
+    'vitcap_engine_decode_masked': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    'vitcap_engine_generate_masked': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,
+                                                vp, vp, vp, vp, vp, vp, vp]),
     'vitcap_engine_score_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.POINTER(GenOpts)]),
     'vitcap_engine_score_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp, vp,
                                            vp, vp]),

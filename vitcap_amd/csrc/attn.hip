@@ -344,15 +344,29 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
 // Two passes over the scores: they are staged in LDS (<= 640 keys x 2 rows fp32) so the softmax uses
 // the exact row max like the oracle.
 // ------------------------------------------------------------------------------------------------
+//
+// MASKED (vitcap_attn_decode_step_masked): sequence b reads row b of vis_mask ([sequences][mask_words] words, the layout of
+// vitcap_attn_text_grid_masked): bit k & 31 of word k >> 5 set = visual key k is visible to this sequence; bits from S_vis on are
+// ignored.  A hidden visual key is hidden from both query rows of the step: its two scores become -inf before they are staged and
+// before the row maximum, and everything behind that point is the code of the plain instance.  The tag / text / step rows never
+// consult the mask, so no softmax row is empty even with every bit clear.  A whole visual sweep whose four mask words are zero is
+// skipped in both passes (no loads, no sc[] writes, no P.V).  That changes no bit of the result: a hidden key that is not skipped
+// contributes p = exp2(fma(-inf, c, -m)) = 0 to the row sum, its bf16 rounding is 0, and fma(0, v, o) = o for every finite v
+// (+0 + -0 = +0 in round-to-nearest), so the sums with and without the sweep are the same chain of additions of the same values.
+// The mask is not MASKED = false's business: that instance has no use of the two arguments and is the kernel as shipped.
+// ------------------------------------------------------------------------------------------------
 constexpr int MAXKEYS = 704;     // 578 visual + 50 tag + 41 text + pad
+constexpr bool DECODE_MASK_SKIP = true;   // docs/LAB_regions.md section 3 measures the masked instance with and without the skip
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ qkv_step,
                                                           const bf16_t* __restrict__ vis_qkv,
                                                           bf16_t* __restrict__ text_kv, bf16_t* __restrict__ out,
                                                           int S_vis, int t, int max_len, int seq_per_image,
                                                           float c_log2, const int32_t* __restrict__ live,
                                                           const bf16_t* __restrict__ tag_a, const bf16_t* __restrict__ tag_b,
-                                                          int n_tag, const int64_t* __restrict__ tag_len) {
+                                                          int n_tag, const int64_t* __restrict__ tag_len,
+                                                          const uint32_t* __restrict__ vis_mask, int mask_words) {
   VC_LIVE_EXIT(live);
   __shared__ float sc[2][MAXKEYS];
   __shared__ float red[2][4];
@@ -370,6 +384,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   if (n_tag > 0) tag_kv = ((int)tag_len[0] + 20 <= t + 51) ? tag_a : tag_b;
   const int S_pre = S_vis + n_tag;   // keys before the text rows
   const int nkeys = S_pre + t + 1;   // visual | tags | text 0..t-1 | mask row
+  const uint32_t* mrow = MASKED ? vis_mask + (size_t)b * mask_words : nullptr;   // this sequence's visibility bits
 
   const bf16_t* q0p = qkv_step + ((size_t)b * 2) * QKV_LD + h * HD + sub * 8;
   const bf16_t* q1p = q0p + QKV_LD;
@@ -412,7 +427,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 
   // ---- pass 1: scores.  Four keys per thread per sweep (4 x 16 B loads in flight; the kernel is HBM-latency bound)
   float mx0 = -1e30f, mx1 = -1e30f;
-#define DECODE_SCORE(k_, kv_, valid_, text_)                                                \
+#define DECODE_SCORE(k_, kv_, valid_, text_, hid_)                                          \
   do {                                                                                      \
     float d0 = 0.f, d1 = 0.f;                                                               \
     _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                         \
@@ -425,6 +440,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
       d1 += __shfl_xor(d1, o, 64);                                                          \
     }                                                                                       \
     if ((text_) && (k_) == nkeys - 1) d0 = -INFINITY; /* row 0 (position t-1) cannot see the [MASK] row */ \
+    if (MASKED) { d0 = (hid_) ? -INFINITY : d0; d1 = (hid_) ? -INFINITY : d1; } /* a hidden visual key: both rows */ \
     if (valid_) {                                                                           \
       if (sub == 0) { sc[0][k_] = d0; sc[1][k_] = d1; }                                     \
       mx0 = fmaxf(mx0, d0);                                                                 \
@@ -433,13 +449,20 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   } while (0)
   const int vis_full = S_vis & ~127;                  // whole sweeps of visual keys: nothing to test per key
   for (int k0 = 0; k0 < vis_full; k0 += 128) {
+    // the four keys of a thread sit at bit kslot of the words (k0 >> 5) + u, which are the same for the whole workgroup
+    uint32_t mw[4] = {0u, 0u, 0u, 0u};
+    if (MASKED) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) mw[u] = mrow[(k0 >> 5) + u];
+      if (DECODE_MASK_SKIP && (mw[0] | mw[1] | mw[2] | mw[3]) == 0u) continue;
+    }
     bf16x8 kv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) kv[u] = vis_load(k0 + u * 32, 0);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = k0 + kslot + u * 32;
-      DECODE_SCORE(k, kv[u], true, false);
+      DECODE_SCORE(k, kv[u], true, false, ((mw[u] >> kslot) & 1u) == 0u);
       // one key at a time: the next key's row is not unpacked before this key is done.  Left alone, hipcc interleaves the four
       // keys of a branch-free sweep, which costs 20 registers and with them the residency beside the 8-wave GEMM
       if (u < 3) asm volatile("" : "+v"(mx0), "+v"(mx1), "+v"(kv[u + 1]));
@@ -455,7 +478,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int k = kb + u * 32;
-      DECODE_SCORE(k, kv[u], k < nkeys, true);
+      bool hid = false;      // the visual keys behind the last whole sweep; k < S_vis keeps the word inside the row
+      if (MASKED && k < S_vis) hid = ((mrow[k >> 5] >> (k & 31)) & 1u) == 0u;
+      DECODE_SCORE(k, kv[u], k < nkeys, true, hid);
     }
   }
 #undef DECODE_SCORE
@@ -486,6 +511,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     }                                                                                                               \
   } while (0)
   for (int k0 = 0; k0 < vis_full; k0 += 128) {
+    if (MASKED && DECODE_MASK_SKIP) {      // the sweeps pass 1 skipped: their sc[] entries were never written
+      const uint32_t* mp = mrow + (k0 >> 5);
+      if ((mp[0] | mp[1] | mp[2] | mp[3]) == 0u) continue;
+    }
     bf16x8 vv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) vv[u] = vis_load(k0 + u * 32, 1);
@@ -936,9 +965,9 @@ extern "C" int vitcap_attn_decode_step_tags(const void* qkv_step, const void* vi
   VC_REQUIRE(t >= 1 && t < max_len && S_vis + n_tag + t + 1 <= MAXKEYS, "attn_decode: t=%d S_vis=%d out of range", t, S_vis);
   VC_REQUIRE(seq_per_image >= 1 && B % seq_per_image == 0, "attn_decode: bad seq_per_image");
   const float c = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3(NH, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv_step,
+  hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(NH, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv_step,
                      (const bf16_t*)vis_qkv, (bf16_t*)text_kv, (bf16_t*)out, S_vis, t, max_len, seq_per_image, c, vc_tls_live,
-                     (const bf16_t*)tag_qkv_a, (const bf16_t*)tag_qkv_b, n_tag, tag_len);
+                     (const bf16_t*)tag_qkv_a, (const bf16_t*)tag_qkv_b, n_tag, tag_len, (const uint32_t*)nullptr, 0);
   VC_LAUNCH_CHECK("attn_decode");
   return VITCAP_OK;
 }
@@ -947,4 +976,21 @@ extern "C" int vitcap_attn_decode_step(const void* qkv_step, const void* vis_qkv
                                        int S_vis, int t, int max_len, int seq_per_image, float scale, void* stream) {
   return vitcap_attn_decode_step_tags(qkv_step, vis_qkv, text_kv, out, B, S_vis, t, max_len, seq_per_image, scale, nullptr, nullptr,
                                       0, nullptr, stream);
+}
+
+extern "C" int vitcap_attn_decode_step_masked(const void* qkv_step, const void* vis_qkv, void* text_kv, void* out, int B,
+                                              int S_vis, int t, int max_len, int seq_per_image, float scale,
+                                              const uint32_t* vis_mask, int mask_words, void* stream) {
+  VC_REQUIRE(qkv_step && vis_qkv && text_kv && out && B > 0, "attn_decode_masked: bad arguments");
+  VC_REQUIRE(S_vis > 0 && t >= 1 && t < max_len && S_vis + t + 1 <= MAXKEYS, "attn_decode_masked: t=%d S_vis=%d out of range", t, S_vis);
+  VC_REQUIRE(seq_per_image >= 1 && B % seq_per_image == 0, "attn_decode_masked: bad seq_per_image");
+  VC_REQUIRE(vis_mask != nullptr, "attn_decode_masked: vis_mask is null");
+  VC_REQUIRE(((uintptr_t)vis_mask & 3) == 0, "attn_decode_masked: vis_mask is not 4-byte aligned");
+  VC_REQUIRE(mask_words >= (S_vis + 31) / 32, "attn_decode_masked: mask_words=%d < ceil(S_vis / 32) = %d", mask_words, (S_vis + 31) / 32);
+  const float c = scale * 1.4426950408889634f;
+  hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(NH, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv_step,
+                     (const bf16_t*)vis_qkv, (bf16_t*)text_kv, (bf16_t*)out, S_vis, t, max_len, seq_per_image, c, vc_tls_live,
+                     (const bf16_t*)nullptr, (const bf16_t*)nullptr, 0, (const int64_t*)nullptr, vis_mask, mask_words);
+  VC_LAUNCH_CHECK("attn_decode_masked");
+  return VITCAP_OK;
 }

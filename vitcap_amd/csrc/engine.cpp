@@ -208,6 +208,8 @@ struct Enq {
   // forced decoding (vitcap_engine_decode_forced): -1 = a plain call; 0 / 1 = score_forced, and the greedy loop reads lo.forced
   // (staged by the caller of decode_loop) and writes lo.tok_lp
   int forced = -1;
+  // region captions (vitcap_engine_decode_masked): the caller's device array [NS][MASK_WORDS], read in place by the attention launches
+  const uint32_t* vis_mask = nullptr;
 
   Enq(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, void* s, Phase ph)
       : e(e), w(e->w), o(o), lo(lo), ws(ws), B(B), s(s),
@@ -585,7 +587,9 @@ struct Enq {
       char* tc = tcache + lo.tcache_at(l, s0);
       const char* vis = p(lo.dqkv[l], i0);
       CK(proj(xs_b, lw.qkv_w, lw.qkv_b, sqkv, 3 * D, VITCAP_ACT_NONE));
-      if (lo.NT > 0)
+      if (vis_mask)      // a slice starts at its first sequence's row
+        CK(vitcap_attn_decode_step_masked(sqkv, vis, tc, sctx, ns, SV, t, L, K, 0.125f, vis_mask + s0 * MASK_WORDS, MASK_WORDS, s));
+      else if (lo.NT > 0)
         CK(vitcap_attn_decode_step_tags(sqkv, vis, tc, sctx, ns, SV, t, L, K, 0.125f, p(lo.tqkv_c(0, l), i0), p(lo.tqkv_c(1, l), i0), lo.NT,
                                         p<int64_t>(lo.tag_len), s));
       else if (lo.vt[l] && K >= 2 && K <= 8)
@@ -779,7 +783,7 @@ struct Enq {
 
  private:
   Enq(const Enq& q, const Layout& lv, int Bv, void* sv)
-      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced) {}
+      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced), vis_mask(q.vis_mask) {}
 };
 
 vitcap_gen_opts opts_or_default(const vitcap_gen_opts* opts) { return opts ? *opts : default_opts(); }
@@ -804,8 +808,23 @@ struct Forced {
   const int64_t* ids = nullptr;     // device [NS][L] or null
   int score = 0;
   float* out_tok_lp = nullptr;      // device [NS][L] or null
+  const uint32_t* vis_mask = nullptr;      // the `_masked` entry points: device [NS][MASK_WORDS], read in place
+  bool masked = false;
   bool on() const { return ids || out_tok_lp; }
 };
+// what a visibility mask is not built for: refused by the option's name before anything is enqueued
+int check_masked(const vitcap_gen_opts& o, const Forced& f) {
+  if (check_opts(o) != VITCAP_OK) return VITCAP_EINVAL;
+  const char* bad = nullptr;
+  if (o.num_beams > 1) bad = "num_beams > 1";
+  else if (o.use_cbs) bad = "use_cbs";
+  else if (o.tag_visible > 0) bad = "tag_visible > 0";
+  else if (o.use_graph) bad = "use_graph = 1 (a captured loop would freeze this call's mask pointer)";
+  if (bad) { vitcap_set_error("masked decoding: a visibility mask is not built for %s", bad); return VITCAP_EINVAL; }
+  if (!f.vis_mask) { vitcap_set_error("masked decoding: vis_mask is null"); return VITCAP_EINVAL; }
+  if (((uintptr_t)f.vis_mask & 3) != 0) { vitcap_set_error("masked decoding: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
+  return VITCAP_OK;
+}
 // forced tokens are built for the greedy / sampling loop only: refused by name before anything is enqueued
 int check_forced(const vitcap_gen_opts& o, const Forced& f) {
   if (!f.on()) return VITCAP_OK;
@@ -823,7 +842,7 @@ int decode_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layou
                   int64_t* out_last_tok, void* s, const Forced& f = Forced()) {
   if (!out_ids || !out_logprobs) { vitcap_set_error("decode: null outputs"); return VITCAP_EINVAL; }
   hipStream_t st = (hipStream_t)s;
-  const bool graph = o.use_graph && !o.sampling.do_sample;
+  const bool graph = o.use_graph && !o.sampling.do_sample && !f.masked;      // check_masked has refused use_graph with a mask
   const int fmode = f.on() ? f.score : -1;
   // The loop -- eager or replayed -- reads the forced ids from the workspace, never from the caller's array: a captured loop holds
   // no pointer of the call it was captured in.  No ids given (only the per-token log-probs are wanted): every entry -1.
@@ -835,6 +854,7 @@ int decode_locked(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layou
   if (!graph) {
     Enq q(e, B, o, lo, ws, s, Enq::DECODE);
     q.forced = fmode;
+    q.vis_mask = f.vis_mask;
     CK(q.decode_loop());
   } else {
     GraphEntry* hit = nullptr;
@@ -1010,6 +1030,39 @@ extern "C" int vitcap_engine_generate_forced(vitcap_engine* e, const void* image
   const vitcap_gen_opts o = opts_or_default(opts);
   Forced f;
   f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs;
+  CK(check_forced(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  char* ws = (char*)workspace;
+  std::lock_guard<std::mutex> lk(e->mu);
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
+  CK(decode_locked(e, B, o, lo, ws, out_ids, out_logprobs, nullptr, s, f));
+  return tags_copy(lo, B, ws, tag_logits_out, tag_topk_out, s);
+}
+
+extern "C" int vitcap_engine_decode_masked(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                           const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                           float* out_token_logprobs, int64_t* out_last_tok, const uint32_t* vis_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs; f.vis_mask = vis_mask; f.masked = true;
+  CK(check_masked(o, f));
+  CK(check_forced(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  return decode_locked(e, B, o, lo, (char*)workspace, out_ids, out_logprobs, out_last_tok, s, f);
+}
+
+extern "C" int vitcap_engine_generate_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                             void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
+                                             int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
+                                             int64_t* tag_topk_out, const uint32_t* vis_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs; f.vis_mask = vis_mask; f.masked = true;
+  CK(check_masked(o, f));
   CK(check_forced(o, f));
   Layout lo;
   CK(enter(e, B, o, workspace, workspace_bytes, lo));

@@ -7,6 +7,7 @@ namespace vc __attribute__((visibility("hidden"))) {      // nothing of it is ex
 constexpr int D = VITCAP_HID;
 constexpr int NV = VITCAP_NVIS;        // 577
 constexpr int SV = VITCAP_NVIS + 1;    // 578 decoder visual rows (tag CLS first)
+constexpr int MASK_WORDS = (SV + 31) / 32;   // 19: uint32 words of one visibility row (vitcap_attn_decode_step_masked)
 constexpr int VP = VITCAP_VOCAB_PAD;
 constexpr int TOPK = 50;
 constexpr int JROWS = 640;           // rows per image of the joint [visual | tag] buffer (578 + 50, padded to 5 x 128)

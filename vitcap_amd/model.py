@@ -193,10 +193,11 @@ class ImageCaptioning(nn.Module):
             pass
 
     # ---------------------------------------------------------------- forward
-    def _workspace(self, B, dev, slot=0, opts=None, wait=None):
+    def _workspace(self, B, dev, slot=0, opts=None, wait=None, keep=False):
         """One workspace per slot: concurrent generate() calls on different HIP streams use different slots.  `wait`: event of
         the slot's in-flight work, waited for before a larger buffer replaces the old one (the caching allocator may hand the
-        old block to another stream at once)."""
+        old block to another stream at once).  keep: a larger buffer starts as a copy of the old one (a decode on the slot's prefill
+        with more sequences per image than the call that encoded)."""
         need = lib.vitcap_engine_workspace_bytes(B, C.byref(opts) if opts is not None else None)
         if need == 0:
             check(lib.vitcap_gen_opts_check(C.byref(opts)), 'gen_opts')
@@ -204,7 +205,9 @@ class ImageCaptioning(nn.Module):
         if ws is None or ws.numel() < need or ws.device != dev:
             if ws is not None and wait is not None:
                 wait.synchronize()
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            old, ws = ws, torch.empty(need, dtype=torch.uint8, device=dev)
+            if keep and old is not None and old.device == dev:
+                ws[:old.numel()].copy_(old)      # the per-image buffers come first in the layout: the prefill stays where it was
             self._ws[slot] = ws
         return ws, need
 
@@ -377,13 +380,35 @@ class ImageCaptioning(nn.Module):
             raise NotImplementedError('prefix_ids / forced tokens need num_beams == 1 and use_cbs off: forced tokens under beam search '
                                       'are not built (got num_beams=%s, use_cbs=%s)' % (num_beams, bool(use_cbs)))
 
-    def run(self, image, opts, want_tags=False, slot=0, want_last=False, forced=None, score_forced=0, want_token_logprobs=False):
+    def refuse_visible(self, who, over=None):
+        """A visibility mask (`visible` / regions) exists for the greedy / sampling loop without visible tags: anything else is
+        refused by the option's name, before the GPU is touched."""
+        te = dict(self.test_extra_input)
+        te.update(over or {})
+        if int(te.get('num_beams', 1) or 1) > 1:
+            raise NotImplementedError('%s: a visibility mask is not built for num_beams > 1 (got %s)' % (who, te['num_beams']))
+        if te.get('use_cbs', False):
+            raise NotImplementedError('%s: a visibility mask is not built for use_cbs' % who)
+        if int(te.get('tag_visible', 0) or 0) > 0:
+            raise NotImplementedError('%s: a visibility mask is not built for tag_visible > 0 (got %s)' % (who, te['tag_visible']))
+
+    def run(self, image, opts, want_tags=False, slot=0, want_last=False, forced=None, score_forced=0, want_token_logprobs=False,
+            vis=None):
         """One vitcap_engine_generate call on the current stream under `opts` (a vitcap_gen_opts from gen_options()).
         forced (rows, max_length) int64 / score_forced: vitcap_amd.forced.pack_forced; with want_token_logprobs the per-token
-        log-probs (rows, max_length) are returned last.  Either one makes it a vitcap_engine_generate_forced call."""
+        log-probs (rows, max_length) are returned last.  Either one makes it a vitcap_engine_generate_forced call.
+        vis int32 (rows, 19), vitcap_amd.occlusion.pack_visible: visual keys hidden per sequence, a vitcap_engine_generate_masked
+        call (no hipGraph: the call sets use_graph = 0).  With vis, image None decodes on the prefill the last call left on `slot`
+        (vitcap_engine_decode_masked)."""
         use_forced = forced is not None or want_token_logprobs
         if use_forced:
             self.refuse_forced_search(opts.num_beams, opts.use_cbs)
+        if vis is not None:
+            if opts.num_beams > 1 or opts.use_cbs or opts.tag_visible > 0:
+                raise NotImplementedError('a visibility mask is not built for num_beams > 1 / use_cbs / tag_visible > 0 (got %d, %d, %d)'
+                                          % (opts.num_beams, opts.use_cbs, opts.tag_visible))
+            opts.use_graph = 0
+            return self._run_masked(image, opts, vis, want_tags, slot, want_last, forced, score_forced, want_token_logprobs)
         dev = self._check_image(image)
         B = image.shape[0]
         rows = B * opts.seqs_per_image
@@ -432,6 +457,69 @@ class ImageCaptioning(nn.Module):
         self._last = (slot, opts, B)
         return (ids, lp) + extra
 
+    def _run_masked(self, image, opts, vis, want_tags, slot, want_last, forced, score_forced, want_token_logprobs):
+        """run() with a visibility mask: vitcap_engine_generate_masked, or with image None / want_last the staged calls ending in
+        vitcap_engine_decode_masked."""
+        if image is not None:
+            dev, B = self._check_image(image), image.shape[0]
+        else:
+            if slot not in self._encoded:
+                raise RuntimeError('no encoded images on slot %r (call run / generate / score on it first)' % (slot,))
+            o_last, B = self._encoded[slot]
+            if opts.max_length != o_last.max_length or o_last.tag_visible > 0:
+                raise ValueError('the last call on slot %r ran other options (max_length / tags)' % (slot,))
+            dev = self._packed[2]
+        rows = B * opts.seqs_per_image
+        if tuple(vis.shape) != (rows, 19):
+            raise ValueError('the packed visibility mask must be (%d, 19), got %s' % (rows, tuple(vis.shape)))
+        # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
+        vis = vis.to(device=dev, dtype=torch.int32).contiguous()
+        fp = tp = tok_lp = None
+        if forced is not None:
+            if tuple(forced.shape) != (rows, opts.max_length):
+                raise ValueError('forced ids must be (%d, %d), got %s' % (rows, opts.max_length, tuple(forced.shape)))
+            forced = forced.to(device=dev, dtype=torch.int64).contiguous()
+            fp = C.c_void_p(forced.data_ptr())
+        if want_token_logprobs:
+            tok_lp = torch.empty((rows, opts.max_length), dtype=torch.float32, device=dev)
+            tp = C.c_void_p(tok_lp.data_ptr())
+        ws, need = self._workspace(B, dev, slot, opts, keep=image is None)
+        ids, lp = self._out_buffers(B, opts, dev)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        wp, vp = C.c_void_p(ws.data_ptr()), C.c_void_p(vis.data_ptr())
+        extra = (tok_lp,) if want_token_logprobs else ()
+        if image is None or want_last:
+            last = torch.empty((rows,), dtype=torch.int64, device=dev) if want_last else None
+            if image is not None:
+                check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                               C.byref(opts), wp, need, s), 'engine_encode')
+                check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
+            check(lib.vitcap_engine_decode_masked(self._engine, B, C.byref(opts), wp, need, fp, int(score_forced),
+                                                  C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tp,
+                                                  C.c_void_p(last.data_ptr()) if want_last else None, vp, s), 'engine_decode_masked')
+            self._encoded[slot] = (opts, B)
+            return ((ids, lp, last) if want_last else (ids, lp)) + extra
+        tag_logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev) if want_tags else None
+        tag_topk = torch.empty((B, 50), dtype=torch.int64, device=dev) if want_tags else None
+        tl = C.c_void_p(tag_logits.data_ptr()) if want_tags else None
+        tk = C.c_void_p(tag_topk.data_ptr()) if want_tags else None
+        check(lib.vitcap_engine_generate_masked(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
+                                                C.byref(opts), wp, need, fp, int(score_forced), C.c_void_p(ids.data_ptr()),
+                                                C.c_void_p(lp.data_ptr()), tp, tl, tk, vp, s), 'engine_generate_masked')
+        if want_tags:
+            self.last_tags = (tag_logits, tag_topk)
+        self._encoded[slot] = (opts, B)
+        self._last = (slot, opts, B)
+        return (ids, lp) + extra
+
+    def _visible_words(self, who, visible, rows, keep_cls, over):
+        """`visible` of generate / generate_multi -> (packed words or None, `over` with use_graph off); the refusals come first."""
+        if visible is None:
+            return None, over
+        from .occlusion import as_visible, pack_visible
+        self.refuse_visible(who, over)
+        return pack_visible(as_visible(visible, rows, keep_cls)), dict(over, use_graph=False)
+
     @staticmethod
     def _prefix_forced(prefix_ids, B, K, max_length):
         """prefix_ids (B, P) -- one prefix per image, shared by its K sequences -- or (B*K, P) -> pack_forced's (forced, 0)."""
@@ -443,23 +531,35 @@ class ImageCaptioning(nn.Module):
             p = p.repeat_interleave(K, 0)
         return pack_forced(prefix_ids=p, rows=B * K, max_length=max_length)
 
-    def generate(self, image, want_tags=False, slot=0, prefix_ids=None, want_token_logprobs=False, **over):
+    def generate(self, image, want_tags=False, slot=0, prefix_ids=None, want_token_logprobs=False, visible=None, keep_cls=True, **over):
         """Greedy captions.  image: (B,3,384,384) fp32 or bf16 on the GPU, normalised with mean=.5/std=.5.
         prefix_ids (B, P), -1-padded: the captions start with these tokens (positions 1..P; they do not enter the score, like a
-        reference loop started at cur_len = P).  want_token_logprobs: returns (ids, logprobs, token_logprobs (B, L))."""
+        reference loop started at cur_len = P).  want_token_logprobs: returns (ids, logprobs, token_logprobs (B, L)).
+        visible: as score_masked takes it, one row per image -- (B, 578) in cache order or a (B, 24, 24) patch grid (the two cls
+        columns then visible iff keep_cls): the caption is written with the other visual tokens hidden from it in all four decoder
+        layers, the reference's attention_mask zeros on caption rows / visual columns (modeling_bert.py:1498-1501).  The mask hides
+        visual TOKENS from the CAPTION; the encoder has seen the whole image.  Not built with beams, CBS or visible tags
+        (NotImplementedError); no hipGraph is used (the call sets use_graph = 0)."""
+        vis, over = self._visible_words('generate', visible, image.shape[0], keep_cls, over)
         o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
         forced, sf = self._prefix_forced(prefix_ids, image.shape[0], 1, o.max_length)
-        return self.run(image, o, want_tags=want_tags, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs)
+        return self.run(image, o, want_tags=want_tags, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs,
+                        vis=vis)
 
-    def generate_multi(self, image, seqs_per_image, slot=0, want_last=False, prefix_ids=None, want_token_logprobs=False, **over):
+    def generate_multi(self, image, seqs_per_image, slot=0, want_last=False, prefix_ids=None, want_token_logprobs=False, visible=None,
+                       keep_cls=True, **over):
         """`seqs_per_image` sampled sequences per image (num_return_sequences of ViTCAP.generate): the encoder and the
         visual prefill run once per image, the sequences of an image share its visual K/V.  Returns (ids (B*n,1,L),
         logprobs (B*n,1)) image-major -- the same sequences generate() gives on the n-times repeated batch -- and, with
         want_last, the token chosen at the last position (before the forced [SEP]) of every sequence.
-        prefix_ids (B, P) or (B*n, P) / want_token_logprobs: as generate(); the per-token log-probs come last."""
+        prefix_ids (B, P) or (B*n, P) / want_token_logprobs: as generate(); the per-token log-probs come last.
+        visible: as generate(), one row per SEQUENCE ((B*n, 578) or (B*n, 24, 24)): the sequences of an image may see different parts."""
+        n = min(int(seqs_per_image), 8) if int(seqs_per_image) > 1 else 1      # gen_options' sequences per image
+        vis, over = self._visible_words('generate_multi', visible, image.shape[0] * n, keep_cls, over)
         o = self.gen_options(num_beams=1, num_keep_best=1, num_return_sequences=int(seqs_per_image), do_sample=True, **over)
         forced, sf = self._prefix_forced(prefix_ids, image.shape[0], o.seqs_per_image, o.max_length)
-        return self.run(image, o, slot=slot, want_last=want_last, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs)
+        return self.run(image, o, slot=slot, want_last=want_last, forced=forced, score_forced=sf, want_token_logprobs=want_token_logprobs,
+                        vis=vis)
 
     def score(self, image, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, one_pass=False, **over):
         """Log-probability of GIVEN captions under the procedure generate() uses: one [MASK] probe per position on the tokens so
@@ -694,14 +794,29 @@ class ImageCaptioning(nn.Module):
                                                        then=lambda B: vis.append(pack_visible(as_visible(visible, B * K))))
         return self._score_one_pass(image, B, o, cap, lt, K, slot, dev, return_ids, vis=vis[0])
 
-    def score_masked(self, image, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+    def score_masked(self, image, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, one_pass=True, **over):
         """score(one_pass=True) with visual keys hidden from the captions: `visible`, bool or uint8, one row per caption, either
         (rows, 578) in the cache's order (0 tag cls, 1 encoder cls, 2..577 the 24 x 24 patches row-major) or a (rows, 24, 24) patch
         grid (both cls columns then stay visible); nonzero = the caption's rows may attend that visual token, in all four decoder
         layers -- the reference's attention_mask zeros on caption rows / visual columns (modeling_bert.py:1498-1501).  The mask hides
         visual TOKENS from the CAPTION; the encoder and the prefill still see the whole image.  Inputs and refusals as
         score(one_pass=True); a wrong shape or dtype of `visible` is a ValueError before the GPU is touched.  With everything visible
-        the results are score(one_pass=True)'s, bit for bit."""
+        the results are score(one_pass=True)'s, bit for bit.
+        one_pass=False: the same captions and masks through the masked step loop (vitcap_engine_generate_masked with forced tokens),
+        the stepwise counterpart score() has; seqs_per_image 1..8; with everything visible the results are score()'s, bit for bit."""
+        if not one_pass:
+            from .forced import pack_forced
+            from .occlusion import as_visible, pack_visible
+            self.refuse_visible('score_masked', over)
+            K = int(seqs_per_image)
+            o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **dict(over, use_graph=False))
+            o.seqs_per_image = K
+            check(lib.vitcap_gen_opts_check(C.byref(o)), 'gen_opts')
+            rows = image.shape[0] * K
+            vis = pack_visible(as_visible(visible, rows))
+            forced, sf = pack_forced(caption_ids=caption_ids, rows=rows, max_length=o.max_length, last_tok=last_tok)
+            ids, lp, tok_lp = self.run(image, o, slot=slot, forced=forced, score_forced=sf, want_token_logprobs=True, vis=vis)
+            return (lp.view(-1), tok_lp, ids) if return_ids else (lp.view(-1), tok_lp)
         return self._score_masked('score_masked', image, caption_ids, visible, seqs_per_image, slot, return_ids, last_tok, over)
 
     def score_masked_encoded(self, caption_ids, visible, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
@@ -773,6 +888,65 @@ class ImageCaptioning(nn.Module):
         masks = torch.stack([torch.ones(578, dtype=torch.bool), torch.zeros(578, dtype=torch.bool)])
         _, tok = self._score_variants(image, B, o, cap, lt, masks, slot, dev)
         return tok[:, 0] - tok[:, 1]
+
+    # ---- region captions: captions the model writes with everything outside a region hidden from them (vitcap_engine_*_masked)
+    def _caption_regions(self, who, image, regions, keep_cls, slot, over):
+        from .occlusion import pack_visible
+        from .regions import MAX_REGIONS, region_masks
+        te = dict(self.test_extra_input)
+        te.update(over)
+        if te.get('do_sample', False):
+            raise NotImplementedError('%s writes greedy captions; do_sample is not built for it' % who)
+        self.refuse_visible(who, over)
+        if image is not None:
+            B = image.shape[0]
+        else:
+            if slot not in self._encoded:
+                raise RuntimeError('%s: no encoded images on slot %r (call run / generate / score on it first)' % (who, slot))
+            B = self._encoded[slot][1]
+        masks, _ = region_masks(regions, B, keep_cls)                  # (B, R, 578)
+        R = masks.shape[1]
+        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
+        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+        all_ids, all_lp = [], []
+        for r0 in range(0, R, MAX_REGIONS):
+            n = min(MAX_REGIONS, R - r0)
+            ok = type(o).from_buffer_copy(o)
+            ok.seqs_per_image = n
+            check(lib.vitcap_gen_opts_check(C.byref(ok)), 'gen_opts')
+            vis = pack_visible(masks[:, r0:r0 + n].reshape(B * n, -1))
+            # the first pass encodes; the later ones decode on its prefill
+            ids, lp = self.run(image if r0 == 0 else None, ok, slot=slot, vis=vis)
+            all_ids.append(ids.view(B, n, ok.max_length))
+            all_lp.append(lp.view(B, n))
+        return torch.cat(all_ids, 1), torch.cat(all_lp, 1)
+
+    def caption_regions(self, image, regions, keep_cls=True, slot=0, **over):
+        """One greedy caption per region of every image, everything outside the region hidden from that caption (generate(visible=)
+        with the region's mask).  regions: integer boxes (B, R, 4) or (R, 4) -- the same for every image -- as [row0, col0, row1,
+        col1), half-open, on the 24 x 24 patch grid, or bool grids (B, R, 24, 24) (vitcap_amd.regions; grid_regions(g) gives the
+        g x g tiling).  keep_cls: the two cls tokens stay visible to every caption.  Any R: the image is encoded once, its regions are
+        decoded in passes of up to 8 sequences per image that share its visual K/V.  The mask hides visual TOKENS from the caption; a
+        hidden patch has still shaped its neighbours and the cls tokens inside the encoder.  Bad boxes are a ValueError, beams / CBS /
+        visible tags / sampling a NotImplementedError, before the GPU is touched.
+        -> (ids (B, R, L), logprobs (B, R)); each equal to generate(image, visible=region mask)'s, bit for bit, while the decode
+        step takes the same GEMM forms (B * 8 <= 128 sequences)."""
+        return self._caption_regions('caption_regions', image, regions, keep_cls, slot, over)
+
+    def caption_regions_encoded(self, regions, keep_cls=True, slot=0, **over):
+        """caption_regions() against the images of the last run() / generate*() / score() call on `slot`, without encoding them
+        again (vitcap_engine_decode_masked on that call's prefill); max_length must be that call's, and it ran without visible tags."""
+        return self._caption_regions('caption_regions_encoded', None, regions, keep_cls, slot, over)
+
+    def caption_with_regions(self, image, regions, keep_cls=True, slot=0, **over):
+        """Greedy captions of the whole images and of their regions on one encoder pass: generate() through the staged path, then
+        caption_regions_encoded().  -> (ids (B, 1, L), logprobs (B, 1), region ids (B, R, L), region logprobs (B, R))."""
+        from .regions import region_masks
+        self.refuse_visible('caption_with_regions', over)
+        region_masks(regions, image.shape[0], keep_cls)      # the refusals, before the GPU is touched
+        o, ids, lp, _ = self._greedy_caption('caption_with_regions', 'region captions', image, slot, over)
+        rids, rlp = self.caption_regions_encoded(regions, keep_cls=keep_cls, slot=slot, **over)
+        return ids, lp, rids, rlp
 
     def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like

@@ -43,14 +43,14 @@ def window_masks(window, stride=None, keep_cls=True, keep_only=False):
     return out
 
 
-def as_visible(visible, rows):
-    """The `visible` argument of score_masked -> bool (rows, 578): bool or uint8, (rows, 578) in cache order or a (rows, 24, 24) patch
-    grid (then both cls columns are visible).  A wrong shape or dtype is a ValueError."""
+def as_visible(visible, rows, keep_cls=True):
+    """The `visible` argument of score_masked / generate -> bool (rows, 578): bool or uint8, (rows, 578) in cache order or a
+    (rows, 24, 24) patch grid (then both cls columns are visible iff keep_cls).  A wrong shape or dtype is a ValueError."""
     v = torch.as_tensor(visible)
     if v.dtype not in (torch.bool, torch.uint8):
         raise ValueError('visible must be bool or uint8 (got %s)' % (v.dtype,))
     if tuple(v.shape) == (rows, GRID, GRID):
-        full = torch.ones((rows, N_VIS), dtype=torch.bool)
+        full = torch.full((rows, N_VIS), bool(keep_cls), dtype=torch.bool)
         full[:, COL_PATCH0:] = v.reshape(rows, N_PATCH).cpu() != 0
         return full
     if tuple(v.shape) != (rows, N_VIS):

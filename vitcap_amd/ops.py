@@ -180,6 +180,21 @@ def attn_decode_step(qkv_step, vis_qkv, text_kv, B, S_vis, t, max_len=20, seq_pe
     return out
 
 
+def attn_decode_step_masked(qkv_step, vis_qkv, text_kv, vis_mask, B, S_vis, t, max_len=20, seq_per_image=1, scale=0.125):
+    """attn_decode_step with visual keys hidden per sequence (vitcap_attn_decode_step_masked): vis_mask int32 (B, mask_words >=
+    ceil(S_vis / 32)) on the device, bit k & 31 of word k >> 5 set = visual key k visible (vitcap_amd.occlusion.pack_visible at
+    S_vis = 578)."""
+    _dev_bf16(qkv_step)
+    _dev_bf16(vis_qkv)
+    _dev_bf16(text_kv)
+    assert vis_mask.is_cuda and vis_mask.is_contiguous() and vis_mask.dtype == torch.int32
+    assert vis_mask.dim() == 2 and vis_mask.shape[0] == B
+    out = torch.empty((B * 2, 768), device=qkv_step.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_decode_step_masked(_p(qkv_step), _p(vis_qkv), _p(text_kv), _p(out), B, S_vis, t, max_len,
+                                             seq_per_image, scale, _p(vis_mask), int(vis_mask.shape[1]), _stream()), 'attn_decode_masked')
+    return out
+
+
 def attn_decode_beams(qkv_step, vis_qkv, text_kv, n_images, K, S_vis, t, max_len=20, scale=0.125):
     """Decode-step attention for K sequences per image on the matrix pipe (vitcap_attn_decode_beams); builds V^T first."""
     _dev_bf16(qkv_step)

@@ -219,7 +219,7 @@ class _PredictRun(object):
                 yield from self.collect(entry)
 
     def analysed(self, batches, dev, pred_rows, mode, what, caption_with):
-        """The batch loop of the three analysis modes (cfg.attention_maps / alternatives / occlusion): the batches strictly one after
+        """The batch loop of the analysis modes (cfg.attention_maps / alternatives / occlusion / regions): the batches strictly one after
         the other through `caption_with(image)`, one of ImageCaptioning.caption_with_* (no two-slot overlap; throughput is not a target
         of these modes).  The callers pass gemm_mode = TILES, the GEMM form of the ordinary predict loop, so that the captions and
         their confidences are that loop's, bit for bit.  Yields (batch, ids on the host, logprobs, what caption_with returned behind
@@ -287,6 +287,17 @@ class _PredictRun(object):
         for batch, ids_h, lp, (drop,) in self.analysed(batches, dev, pred_rows, 'occlusion', 'occlusion maps',
                                                        lambda img: model.caption_with_occlusion(img, window=window, gemm_mode=1)):
             for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
+                yield key, json.dumps(recs)
+
+    def region_rows(self, batches, dev, pred_rows, g):
+        """cfg.regions = g: yields the rows of the regions TSV, one per image: the key and a JSON list with one record per tile of the
+        g x g tiling -- its pixel rectangle, caption and confidence (vitcap_amd.regions.to_rows) of
+        ImageCaptioning.caption_with_regions."""
+        from .regions import grid_regions, to_rows
+        model, boxes = self.model, grid_regions(g)
+        for batch, ids_h, lp, (rids, rlp) in self.analysed(batches, dev, pred_rows, 'regions', 'region captions',
+                                                           lambda img: model.caption_with_regions(img, boxes, gemm_mode=1)):
+            for key, recs in zip(batch['key'], to_rows(rids.cpu(), rlp.cpu(), boxes, self.pipe.tokenizer)):
                 yield key, json.dumps(recs)
 
     def counted(self, rows):
@@ -707,6 +718,18 @@ class CaptionUniPipeline(object):
                 self.merge_rank_files(predict_result_file)
                 self.merge_rank_files(occ_file)
             return predict_result_file
+        if self.cfg.regions:
+            # a second TSV next to the predictions, one row per image: a caption per tile of the g x g tiling
+            reg_file = self.get_regions_file(predict_result_file)
+            reg_sub = reg_file if self.world == 1 else '{}_{}_{}.tsv'.format(reg_file, self.rank, self.world)
+            pred_rows = []
+            tsv_writer(run.counted(run.region_rows(batches, dev, pred_rows, int(self.cfg.regions))), reg_sub)
+            tsv_writer(iter(pred_rows), sub)
+            run.report()
+            if self.world > 1:
+                self.merge_rank_files(predict_result_file)
+                self.merge_rank_files(reg_file)
+            return predict_result_file
         tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)              # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
         run.report()
         if self.world > 1:
@@ -730,6 +753,34 @@ class CaptionUniPipeline(object):
         """<predict file minus .tsv>.occ.tsv: written by predict when the config sets `occlusion: window`."""
         assert predict_result_file.endswith('.tsv')
         return predict_result_file[:-len('.tsv')] + '.occ.tsv'
+
+    @staticmethod
+    def get_regions_file(predict_result_file):
+        """<predict file minus .tsv>.regions.tsv: written by predict when the config sets `regions: g`."""
+        assert predict_result_file.endswith('.tsv')
+        return predict_result_file[:-len('.tsv')] + '.regions.tsv'
+
+    def check_regions(self):
+        """`regions: g` is refused by name with what the region captions are not built for, before a model is built."""
+        from .regions import grid_regions
+        cfg = self.cfg
+        if not cfg.regions:
+            return
+        grid_regions(cfg.regions)
+        if cfg.num_beams not in (None, 1):
+            raise NotImplementedError('regions: the region captions are greedy; beam search (num_beams=%r) is not built for them'
+                                      % (cfg.num_beams,))
+        if cfg.use_cbs:
+            raise NotImplementedError('regions: the region captions are greedy; CBS (use_cbs=%r) is not built for them' % (cfg.use_cbs,))
+        if cfg.caption_prefix:
+            raise NotImplementedError('regions: caption_prefix=%r is not built together with the region captions (they are free greedy '
+                                      'captions)' % (cfg.caption_prefix,))
+        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (region_rows)
+            raise NotImplementedError('regions: visible tag slots (tag_visible=%r) are not built for the region captions' % (cfg.tag_visible,))
+        for other in ('attention_maps', 'alternatives', 'occlusion'):
+            if getattr(cfg, other):
+                raise NotImplementedError('regions together with %s: one explaining pass per run is built; run the two configurations '
+                                          'one after the other' % other)
 
     def check_occlusion(self):
         """`occlusion: window` is refused by name with what the occlusion maps are not built for, before a model is built."""
@@ -801,6 +852,7 @@ class CaptionUniPipeline(object):
                                       'those of free greedy captions)' % (self.cfg.caption_prefix,))
         self.check_alternatives()
         self.check_occlusion()
+        self.check_regions()
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -817,6 +869,8 @@ class CaptionUniPipeline(object):
         if have and self.cfg.alternatives and not op.isfile(self.get_alternatives_file(predict_result_file)):
             have = False
         if have and self.cfg.occlusion and not op.isfile(self.get_occlusion_file(predict_result_file)):
+            have = False
+        if have and self.cfg.regions and not op.isfile(self.get_regions_file(predict_result_file)):
             have = False
         if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
