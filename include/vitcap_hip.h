@@ -550,6 +550,19 @@ int vitcap_attn_decode_beams(const void* qkv_step, const void* vis_qkv, const vo
 int vitcap_attn_decode_beam_groups(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
                                    int n_images, int seq_per_group, int groups_per_image, int S_vis, int t, int max_len, float scale,
                                    void* stream);
+/* vitcap_attn_decode_beam_groups with visual keys hidden from whole groups (region captions under beam search); with
+ * groups_per_image = 1 the masked form of vitcap_attn_decode_beams.  vis_mask: device, uint32 [n_images * groups_per_image][mask_words]
+ * with mask_words >= ceil(S_vis / 32), one row per GROUP in launch order: bit k & 31 of word k >> 5 set = visual key k is visible to
+ * all 2 * seq_per_group query rows of the group; bits from S_vis on are ignored, whatever they hold -- at S_vis = 578 the [rows][19]
+ * layout of vitcap_attn_decode_step_masked.  A hidden key's scores are -inf before the row maximum is taken; the text keys (cache
+ * rows, the step's row 0, the [MASK] row) never consult the mask, so no softmax row is empty even with every bit clear, and the
+ * published cache rows are the step's row 0 as ever.  16-key blocks and 32-key blocks without a visible key are not loaded or
+ * multiplied, which changes no bit: with every bit set `out` and the cache are bit-identical to vitcap_attn_decode_beam_groups'.
+ * Argument checks as vitcap_attn_decode_beam_groups, plus VITCAP_EINVAL -- before anything is enqueued, message prefix
+ * "attn_decode_beams_masked" -- for a null or 4-byte-misaligned mask and for mask_words < ceil(S_vis / 32). */
+int vitcap_attn_decode_beam_groups_masked(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
+                                          int n_images, int seq_per_group, int groups_per_image, int S_vis, int t, int max_len,
+                                          float scale, const uint32_t* vis_mask, int mask_words, void* stream);
 /* Text-grid attention of the one-pass caption scorer: all steps of a GIVEN caption at once, the captions of an image sharing its
  * visual K/V (csrc/attn_grid.hip).
  *   qkv_text  bf16 [n_images * caps_per_image][R][2304], R = 2 * max_len - 1 rows per caption, image-major: rows 0..L-1 the caption's
@@ -789,6 +802,24 @@ int vitcap_engine_generate_masked(vitcap_engine* e, const void* image, int image
                                   void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
                                   int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
                                   int64_t* tag_topk_out, const uint32_t* vis_mask, void* stream);
+/* The beam-search counterparts of the two `_masked` calls: region captions by beam search, and the n-best captions of a region.
+ *   vis_mask  device, uint32 [B][19], ONE ROW PER IMAGE -- all beams of an image see the same part of it -- in the layout of
+ *             vitcap_attn_decode_beam_groups_masked at S_vis = 578.  Read in place by every step's attention launches: it must stay
+ *             valid and unchanged until `stream` has run them.
+ * Accepted: num_beams 2..8 with length_penalty, num_keep_best and repetition_penalty; outputs as vitcap_engine_decode under those
+ * options ([B][num_keep_best][max_length] ids, [B][num_keep_best] scores).  vitcap_engine_decode_beam_masked runs on the prefill that a
+ * call with the SAME beam options left on the workspace (vitcap_engine_encode + vitcap_engine_prefill, or a whole generate call), so
+ * several masks can be decoded against one encoder pass.  Refused with VITCAP_EINVAL and the option's name in vitcap_last_error(),
+ * before anything else is looked at: num_beams == 1 (that is vitcap_engine_decode_masked), use_cbs, tag_visible > 0, do_sample,
+ * use_graph = 1, forced tokens (forced_ids or out_token_logprobs not NULL; the two arguments exist so that the four `_masked` calls
+ * share a signature); then a null or 4-byte-misaligned vis_mask.  out_last_tok is not written under beam search. */
+int vitcap_engine_decode_beam_masked(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                     const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                     float* out_token_logprobs, int64_t* out_last_tok, const uint32_t* vis_mask, void* stream);
+int vitcap_engine_generate_beam_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                       void* workspace, size_t workspace_bytes, const int64_t* forced_ids, int score_forced,
+                                       int64_t* out_ids, float* out_logprobs, float* out_token_logprobs, float* tag_logits_out,
+                                       int64_t* tag_topk_out, const uint32_t* vis_mask, void* stream);
 /* One-pass scoring of GIVEN captions: every token is known in advance, so the max_length - 1 sequential steps of
  * vitcap_engine_decode_forced(score_forced = 1) become one pass over a [token rows | [MASK] probe rows] grid of 2 * max_length - 1 rows
  * per caption -- four decoder layers of full-size GEMMs, vitcap_attn_text_grid against the image's visual K/V, the LM head on the probe

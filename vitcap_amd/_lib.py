@@ -225,6 +225,8 @@ _SIGS = {
     'vitcap_attn_beam_vt': (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     'vitcap_attn_decode_beams': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_decode_beam_groups': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    'vitcap_attn_decode_beam_groups_masked': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                        vp, C.c_int, vp]),
     'vitcap_attn_text_grid': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_text_grid_masked': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_probe_maps': (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp]),
@@ -266,6 +268,9 @@ _SIGS = {
     'vitcap_engine_decode_masked': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     'vitcap_engine_generate_masked': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,
                                                 vp, vp, vp, vp, vp, vp, vp]),
+    'vitcap_engine_decode_beam_masked': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
+    'vitcap_engine_generate_beam_masked': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,
+                                                     vp, vp, vp, vp, vp, vp, vp]),
     'vitcap_engine_score_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.POINTER(GenOpts)]),
     'vitcap_engine_score_text': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp, vp, vp,
                                            vp, vp]),

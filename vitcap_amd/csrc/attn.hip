@@ -598,13 +598,28 @@ __global__ __launch_bounds__(256) void vt_build_kernel(const bf16_t* __restrict_
 
 // MAXP: (sequence, text key) pairs per 8-lane group in phase 1b (K * (t+1) <= 32 * MAXP); MAXT: text keys per group and sequence
 // in phase 2b (t + 1 <= 8 * MAXT).  Two instantiations: <4, 3> (5 beams x 20 tokens: fits two workgroups per CU), <11, 6> (any).
-template <int MAXP, int MAXT>
+//
+// MASKED (vitcap_attn_decode_beam_groups_masked): group blockIdx.y reads row blockIdx.y of vis_mask ([groups][mask_words] words): bit
+// k & 31 of word k >> 5 set = visual key k is visible to ALL 2 * K query rows of the group; bits from S_vis on are cleared here before
+// any use (mword).  A hidden key's scores become -inf before they are staged in sc[][] and before the row maximum; everything behind
+// that point is the plain instance's code.  The text keys (phases 1b / 2b) never consult the mask, so no softmax row is empty even with
+// every bit clear.  Blocks without a visible key are skipped: a 16-key block of phase 1a whose 16 bits are clear loads no K rows and
+// issues no MFMA (if another bit of its 32-bit word is set, phase 2a will read its scores: it writes their -inf), and a 32-key block
+// of phase 2a whose word is zero loads no V^T, computes no exp2 and issues no MFMA -- none of its sc[] entries was written and none is
+// read.  That changes no bit of the result, by the argument above attn_decode_kernel restated for the matrix pipe: a hidden key that
+// is not skipped gives p = exp2(fma(-inf, c, -m)) = +0, which adds +0 to the row sum (lsum >= +0 stays as it is) and rounds to bf16
+// +0; the MFMA then adds the products +0 * v = +-0 (V^T finite) to an accumulator that started at +0 and is never -0 (x + y = -0 only
+// for x = y = -0 in round-to-nearest), and a sum with exact zeros added is the same number in whatever order the pipe adds it.  So the
+// accumulators with and without the block hold the same bits.  The mask is wave-uniform (block index = wave + 4 i), read through
+// scalar loads.  MASKED = false has no use of the two arguments and is the kernel as shipped.
+template <int MAXP, int MAXT, bool MASKED>
 __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __restrict__ qkv_step,
                                                                const bf16_t* __restrict__ vis_qkv,
                                                                const bf16_t* __restrict__ vis_vt,
                                                                bf16_t* __restrict__ text_kv, bf16_t* __restrict__ out,
                                                                int S_vis, int t, int max_len, int K, float c_log2,
-                                                               const int32_t* __restrict__ live, int groups_per_image) {
+                                                               const int32_t* __restrict__ live, int groups_per_image,
+                                                               const uint32_t* __restrict__ vis_mask, int mask_words) {
   VC_LIVE_EXIT(live);
   // dynamic LDS sized by the image's 2*K query rows (5 beams: 47 KB -> three workgroups per CU): scores [NQ][BEAM_SC_LD], the
   // four waves' partial contexts [4][NQ][64], the text part [NQ][64]
@@ -625,6 +640,16 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
   const int NQ = 2 * K;                       // query rows of this group: row n = sequence n / 2, step row n % 2
   const int b0 = blockIdx.y * K;
   const int ntext = t + 1;                    // text keys per sequence: cache rows 0..t-2, this step's row 0, the [MASK] row
+  // the block index of the matrix-pipe phases is wk + 4 i; MASKED tells the compiler that it is the same for the whole wave
+  const int wk = MASKED ? __builtin_amdgcn_readfirstlane(w) : w;
+  const uint32_t* mk = MASKED ? vis_mask + (size_t)blockIdx.y * mask_words : nullptr;   // this group's visibility bits
+  const int nw = (S_vis + 31) >> 5;           // mask words that hold a key
+  auto mword = [&](int kb32) -> uint32_t {    // the 32 bits of keys kb32 * 32 ..; no bit from S_vis on, no word behind them is read
+    if (kb32 >= nw) return 0u;
+    const uint32_t m = mk[kb32];
+    return (kb32 == nw - 1 && (S_vis & 31) != 0) ? m & ((1u << (S_vis & 31)) - 1u) : m;
+  };
+  auto mhalf = [&](int kb16) -> uint32_t { return (mword(kb16 >> 1) >> ((kb16 & 1) * 16)) & 0xffffu; };   // of keys kb16 * 16 ..
 
   // publish this step's real-token K/V (row 0) of every sequence into its cache at position t-1
   if (tid < 16 * K) {
@@ -679,8 +704,9 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
   bf16x8 kf[MAXB][2];
 #pragma unroll
   for (int i = 0; i < MAXB; ++i) {
-    const int kb = w + 4 * i;
+    const int kb = wk + 4 * i;
     if (kb < nkb) {
+      if (MASKED && mhalf(kb) == 0u) continue;            // no visible key: phase 1a does not use the block
       int key = kb * 16 + frow;
       key = key < S_vis ? key : S_vis - 1;
       const bf16_t* kp = vis_qkv + ((size_t)img * S_vis + key) * QKV_LD + 768 + h * HD + fk * 8;
@@ -691,8 +717,17 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
   float mx = -1e30f;                          // this lane's query (frow) over its keys
 #pragma unroll
   for (int i = 0; i < MAXB; ++i) {
-    const int kb = w + 4 * i;
+    const int kb = wk + 4 * i;
     if (kb < nkb) {
+      const uint32_t mb = MASKED ? mhalf(kb) : 0xffffu;
+      if (MASKED && mb == 0u) {
+        // skipped.  Phase 2a reads the scores of every key of a 32-key block whose word is not zero: this half's are -inf
+        if (mword(kb >> 1) != 0u && frow < NQ) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sc[frow][kb * 16 + fk * 4 + e] = -INFINITY;
+        }
+        continue;
+      }
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i][0], qf[0], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i][1], qf[1], acc, 0, 0, 0);
@@ -700,7 +735,8 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int key = kb * 16 + fk * 4 + e;
-        const float v = key < S_vis ? acc[e] : -INFINITY;
+        float v = key < S_vis ? acc[e] : -INFINITY;
+        if (MASKED) v = ((mb >> (fk * 4 + e)) & 1u) != 0u ? v : -INFINITY;      // a hidden key: every query row of the group
         if (frow < NQ) sc[frow][key] = v;
         mx = fmaxf(mx, v);
       }
@@ -713,15 +749,16 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
   const bf16_t* vtb = vis_vt + ((size_t)img * NH + h) * HD * VT_KP;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
-    const int kb = w + 4 * i;
+    const int kb = wk + 4 * i;
     if (kb < VT_KP / 32) {
+      if (MASKED && mword(kb) == 0u) continue;              // no visible key: phase 2a does not use the block
 #pragma unroll
       for (int db = 0; db < 4; ++db) vf[i][db] = *(const bf16x8*)(vtb + (size_t)(db * 16 + frow) * VT_KP + kb * 32 + fk * 8);
     }
   }
   if (w == 0 && fk == 0) {                    // keys S_vis .. VT_KP-1 of the padded blocks: no weight
     if (frow < NQ)
-      for (int key = nkb * 16; key < VT_KP; ++key) sc[frow][key] = -INFINITY;
+      for (int key = nkb * 16; key < (MASKED ? nw * 32 : VT_KP); ++key) sc[frow][key] = -INFINITY;   // MASKED: blocks from nw on are skipped
   }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -776,8 +813,9 @@ __global__ __launch_bounds__(256) void attn_decode_beam_kernel(const bf16_t* __r
   float lsum = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
-    const int kb = w + 4 * i;
+    const int kb = wk + 4 * i;
     if (kb < VT_KP / 32) {
+      if (MASKED && mword(kb) == 0u) continue;              // p = +0 for all 32 keys: nothing to add (see above the kernel)
       bf16x8 pf;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -865,43 +903,66 @@ extern "C" int vitcap_attn_beam_vt(const void* vis_qkv, void* vis_vt, int n_imag
   return VITCAP_OK;
 }
 
-static int attn_decode_groups(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out, int n_images,
-                              int seq_per_image, int groups_per_image, int S_vis, int t, int max_len, float scale, void* stream);
+// who: the message prefix of the entry point.  vis_mask null: the plain instances (the mask arguments unused).
+static int attn_decode_groups(const char* who, const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
+                              int n_images, int seq_per_image, int groups_per_image, int S_vis, int t, int max_len, float scale,
+                              const uint32_t* vis_mask, int mask_words, void* stream);
 
 extern "C" int vitcap_attn_decode_beams(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
                                         int n_images, int seq_per_image, int S_vis, int t, int max_len, float scale, void* stream) {
-  return attn_decode_groups(qkv_step, vis_qkv, vis_vt, text_kv, out, n_images, seq_per_image, 1, S_vis, t, max_len, scale, stream);
+  return attn_decode_groups("attn_decode_beams", qkv_step, vis_qkv, vis_vt, text_kv, out, n_images, seq_per_image, 1, S_vis, t, max_len,
+                            scale, nullptr, 0, stream);
 }
 
 extern "C" int vitcap_attn_decode_beam_groups(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
                                               int n_images, int seq_per_group, int groups_per_image, int S_vis, int t, int max_len,
                                               float scale, void* stream) {
-  return attn_decode_groups(qkv_step, vis_qkv, vis_vt, text_kv, out, n_images, seq_per_group, groups_per_image, S_vis, t, max_len, scale,
-                            stream);
+  return attn_decode_groups("attn_decode_beams", qkv_step, vis_qkv, vis_vt, text_kv, out, n_images, seq_per_group, groups_per_image, S_vis,
+                            t, max_len, scale, nullptr, 0, stream);
 }
 
-static int attn_decode_groups(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out, int n_images,
-                              int seq_per_image, int groups_per_image, int S_vis, int t, int max_len, float scale, void* stream) {
-  VC_REQUIRE(qkv_step && vis_qkv && vis_vt && text_kv && out && n_images > 0 && groups_per_image >= 1, "attn_decode_beams: bad arguments");
-  VC_REQUIRE(seq_per_image >= 1 && seq_per_image <= 8, "attn_decode_beams: 1..8 sequences per group (got %d)", seq_per_image);
+extern "C" int vitcap_attn_decode_beam_groups_masked(const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv,
+                                                     void* out, int n_images, int seq_per_group, int groups_per_image, int S_vis, int t,
+                                                     int max_len, float scale, const uint32_t* vis_mask, int mask_words, void* stream) {
+  VC_REQUIRE(vis_mask != nullptr, "attn_decode_beams_masked: vis_mask is null");
+  VC_REQUIRE(((uintptr_t)vis_mask & 3) == 0, "attn_decode_beams_masked: vis_mask is not 4-byte aligned");
+  VC_REQUIRE(S_vis > 0 && mask_words >= (S_vis + 31) / 32, "attn_decode_beams_masked: mask_words=%d < ceil(S_vis / 32) = %d", mask_words,
+             (S_vis + 31) / 32);
+  return attn_decode_groups("attn_decode_beams_masked", qkv_step, vis_qkv, vis_vt, text_kv, out, n_images, seq_per_group, groups_per_image,
+                            S_vis, t, max_len, scale, vis_mask, mask_words, stream);
+}
+
+#define VC_LAUNCH_BEAM(MAXP_, MAXT_, MASKED_)                                                                                          \
+  hipLaunchKernelGGL((attn_decode_beam_kernel<MAXP_, MAXT_, MASKED_>), dim3(NH, n_images * groups_per_image), dim3(256), smem,         \
+                     (hipStream_t)stream, (const bf16_t*)qkv_step, (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)text_kv,    \
+                     (bf16_t*)out, S_vis, t, max_len, seq_per_image, c, vc_tls_live, groups_per_image, vis_mask, mask_words)
+
+static int attn_decode_groups(const char* who, const void* qkv_step, const void* vis_qkv, const void* vis_vt, void* text_kv, void* out,
+                              int n_images, int seq_per_image, int groups_per_image, int S_vis, int t, int max_len, float scale,
+                              const uint32_t* vis_mask, int mask_words, void* stream) {
+  VC_REQUIRE(qkv_step && vis_qkv && vis_vt && text_kv && out && n_images > 0 && groups_per_image >= 1, "%s: bad arguments", who);
+  VC_REQUIRE(seq_per_image >= 1 && seq_per_image <= 8, "%s: 1..8 sequences per group (got %d)", who, seq_per_image);
   VC_REQUIRE(t >= 1 && t < max_len && max_len <= 41 && S_vis > 16 && S_vis <= VT_KP && (S_vis + 15) / 16 <= 40,
-             "attn_decode_beams: t=%d max_len=%d S_vis=%d out of range", t, max_len, S_vis);
+             "%s: t=%d max_len=%d S_vis=%d out of range", who, t, max_len, S_vis);
   const float c = scale * 1.4426950408889634f;
   const int nq = 2 * seq_per_image;
   const size_t smem = (size_t)nq * BEAM_SC_LD * 4 + (size_t)5 * nq * HD * 4;      // <= 62.5 KB at 8 sequences per image
-  VC_FUNC_SMEM((attn_decode_beam_kernel<4, 3>), 64 * 1024);
-  VC_FUNC_SMEM((attn_decode_beam_kernel<11, 6>), 64 * 1024);
-  if (seq_per_image * (t + 1) <= 32 * 4 && t + 1 <= 8 * 3)
-    hipLaunchKernelGGL((attn_decode_beam_kernel<4, 3>), dim3(NH, n_images * groups_per_image), dim3(256), smem, (hipStream_t)stream, (const bf16_t*)qkv_step,
-                       (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)text_kv, (bf16_t*)out, S_vis, t, max_len,
-                       seq_per_image, c, vc_tls_live, groups_per_image);
-  else
-    hipLaunchKernelGGL((attn_decode_beam_kernel<11, 6>), dim3(NH, n_images * groups_per_image), dim3(256), smem, (hipStream_t)stream, (const bf16_t*)qkv_step,
-                       (const bf16_t*)vis_qkv, (const bf16_t*)vis_vt, (bf16_t*)text_kv, (bf16_t*)out, S_vis, t, max_len,
-                       seq_per_image, c, vc_tls_live, groups_per_image);
-  VC_LAUNCH_CHECK("attn_decode_beams");
+  const bool small = seq_per_image * (t + 1) <= 32 * 4 && t + 1 <= 8 * 3;
+  if (vis_mask) {
+    VC_FUNC_SMEM((attn_decode_beam_kernel<4, 3, true>), 64 * 1024);
+    VC_FUNC_SMEM((attn_decode_beam_kernel<11, 6, true>), 64 * 1024);
+    if (small) VC_LAUNCH_BEAM(4, 3, true);
+    else VC_LAUNCH_BEAM(11, 6, true);
+  } else {
+    VC_FUNC_SMEM((attn_decode_beam_kernel<4, 3, false>), 64 * 1024);
+    VC_FUNC_SMEM((attn_decode_beam_kernel<11, 6, false>), 64 * 1024);
+    if (small) VC_LAUNCH_BEAM(4, 3, false);
+    else VC_LAUNCH_BEAM(11, 6, false);
+  }
+  VC_LAUNCH_CHECK(who);
   return VITCAP_OK;
 }
+#undef VC_LAUNCH_BEAM
 
 
 #define VC_LAUNCH_DENSE(DROP_, grid_, stream_, ...)                                                             \

@@ -587,7 +587,11 @@ struct Enq {
       char* tc = tcache + lo.tcache_at(l, s0);
       const char* vis = p(lo.dqkv[l], i0);
       CK(proj(xs_b, lw.qkv_w, lw.qkv_b, sqkv, 3 * D, VITCAP_ACT_NONE));
-      if (vis_mask)      // a slice starts at its first sequence's row
+      if (vis_mask && lo.vt[l] && K >= 2 && K <= 8)
+        // beam search with a mask (vitcap_engine_decode_beam_masked): one row per IMAGE, a slice starts at its first image's row
+        CK(vitcap_attn_decode_beam_groups_masked(sqkv, vis, p(lo.vt[l], i0), tc, sctx, ns / K, K, 1, SV, t, L, 0.125f,
+                                                 vis_mask + (size_t)i0 * MASK_WORDS, MASK_WORDS, s));
+      else if (vis_mask)      // a slice starts at its first sequence's row
         CK(vitcap_attn_decode_step_masked(sqkv, vis, tc, sctx, ns, SV, t, L, K, 0.125f, vis_mask + s0 * MASK_WORDS, MASK_WORDS, s));
       else if (lo.NT > 0)
         CK(vitcap_attn_decode_step_tags(sqkv, vis, tc, sctx, ns, SV, t, L, K, 0.125f, p(lo.tqkv_c(0, l), i0), p(lo.tqkv_c(1, l), i0), lo.NT,
@@ -823,6 +827,21 @@ int check_masked(const vitcap_gen_opts& o, const Forced& f) {
   if (bad) { vitcap_set_error("masked decoding: a visibility mask is not built for %s", bad); return VITCAP_EINVAL; }
   if (!f.vis_mask) { vitcap_set_error("masked decoding: vis_mask is null"); return VITCAP_EINVAL; }
   if (((uintptr_t)f.vis_mask & 3) != 0) { vitcap_set_error("masked decoding: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
+  return VITCAP_OK;
+}
+// the beam counterpart (vitcap_engine_decode_beam_masked): one mask row per image, 2..8 beams; refused by name before anything else
+int check_beam_masked(const vitcap_gen_opts& o, const Forced& f) {
+  if (check_opts(o) != VITCAP_OK) return VITCAP_EINVAL;
+  const char* bad = nullptr;
+  if (o.num_beams < 2 || o.num_beams > 8) bad = "num_beams outside 2..8 (num_beams == 1 is vitcap_engine_decode_masked)";
+  else if (o.use_cbs) bad = "use_cbs";
+  else if (o.tag_visible > 0) bad = "tag_visible > 0";
+  else if (o.sampling.do_sample) bad = "do_sample (beam sampling)";
+  else if (o.use_graph) bad = "use_graph = 1 (a captured loop would freeze this call's mask pointer)";
+  else if (f.on()) bad = "forced_ids / token_logprobs (forced tokens under beam search)";
+  if (bad) { vitcap_set_error("masked beam decoding: a visibility mask under beam search is not built for %s", bad); return VITCAP_EINVAL; }
+  if (!f.vis_mask) { vitcap_set_error("masked beam decoding: vis_mask is null"); return VITCAP_EINVAL; }
+  if (((uintptr_t)f.vis_mask & 3) != 0) { vitcap_set_error("masked beam decoding: vis_mask is not 4-byte aligned"); return VITCAP_EINVAL; }
   return VITCAP_OK;
 }
 // forced tokens are built for the greedy / sampling loop only: refused by name before anything is enqueued
@@ -1064,6 +1083,39 @@ extern "C" int vitcap_engine_generate_masked(vitcap_engine* e, const void* image
   f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs; f.vis_mask = vis_mask; f.masked = true;
   CK(check_masked(o, f));
   CK(check_forced(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  char* ws = (char*)workspace;
+  std::lock_guard<std::mutex> lk(e->mu);
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).encode(image, image_is_bf16));
+  CK(Enq(e, B, o, lo, ws, s, Enq::ENCODE).prefill());
+  CK(decode_locked(e, B, o, lo, ws, out_ids, out_logprobs, nullptr, s, f));
+  return tags_copy(lo, B, ws, tag_logits_out, tag_topk_out, s);
+}
+
+extern "C" int vitcap_engine_decode_beam_masked(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace,
+                                                size_t workspace_bytes, const int64_t* forced_ids, int score_forced, int64_t* out_ids,
+                                                float* out_logprobs, float* out_token_logprobs, int64_t* out_last_tok,
+                                                const uint32_t* vis_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs; f.vis_mask = vis_mask; f.masked = true;
+  CK(check_beam_masked(o, f));
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  return decode_locked(e, B, o, lo, (char*)workspace, out_ids, out_logprobs, out_last_tok, s, f);
+}
+
+extern "C" int vitcap_engine_generate_beam_masked(vitcap_engine* e, const void* image, int image_is_bf16, int B,
+                                                  const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                                  const int64_t* forced_ids, int score_forced, int64_t* out_ids, float* out_logprobs,
+                                                  float* out_token_logprobs, float* tag_logits_out, int64_t* tag_topk_out,
+                                                  const uint32_t* vis_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Forced f;
+  f.ids = forced_ids; f.score = score_forced; f.out_tok_lp = out_token_logprobs; f.vis_mask = vis_mask; f.masked = true;
+  CK(check_beam_masked(o, f));
   Layout lo;
   CK(enter(e, B, o, workspace, workspace_bytes, lo));
   char* ws = (char*)workspace;

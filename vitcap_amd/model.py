@@ -948,13 +948,117 @@ class ImageCaptioning(nn.Module):
         rids, rlp = self.caption_regions_encoded(regions, keep_cls=keep_cls, slot=slot, **over)
         return ids, lp, rids, rlp
 
-    def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, **over):
+    def generate_beam(self, image, num_beams, length_penalty=1.0, slot=0, num_keep_best=1, visible=None, keep_cls=True, **over):
         """Beam search -> (ids (B,num_keep_best,L), logprobs (B,num_keep_best)), best hypothesis first, like
-        ViTCAP._generate_beam_search (modeling_utils.py:888-1100)."""
+        ViTCAP._generate_beam_search (modeling_utils.py:888-1100).
+        visible: as generate() takes it, one row per image -- (B, 578) in cache order or a (B, 24, 24) patch grid (the two cls columns
+        then visible iff keep_cls): all beams of an image are searched with the other visual tokens hidden from them
+        (vitcap_engine_generate_beam_masked).  Then num_beams 2..8; num_beams == 1, CBS, visible tags, beam sampling, hipGraph replay
+        and forced tokens are a NotImplementedError naming the option, a bad mask a ValueError, before the GPU is touched."""
+        if visible is not None:
+            from .occlusion import as_visible, pack_visible
+            self.refuse_visible_beam('generate_beam', num_beams, over)
+            vis = pack_visible(as_visible(visible, image.shape[0], keep_cls))
+            o = self._beam_masked_options(num_beams, length_penalty, num_keep_best, over)
+            return self._run_beam_masked(image, o, [vis], slot)[0]
         over.setdefault('do_sample', False)      # do_sample=True: beam sampling (modeling_utils.py:966-985), temperature / top_k / top_p / seed
         o = self.gen_options(num_beams=int(num_beams), length_penalty=float(length_penalty), num_keep_best=int(num_keep_best),
                              num_return_sequences=1, **over)
         return self.run(image, o, slot=slot)
+
+    # ---- region captions under beam search (vitcap_engine_*_beam_masked): one mask row per image, all its beams see the same part
+    def refuse_visible_beam(self, who, num_beams, over=None):
+        """What a visibility mask under beam search is not built for, refused by the option's name before the GPU is touched."""
+        te = dict(self.test_extra_input)
+        te.update(over or {})
+        if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 2 <= int(num_beams) <= 8:
+            raise NotImplementedError('%s: a visibility mask under beam search needs num_beams 2..8 (got num_beams=%r; one beam is '
+                                      'generate(visible=) / caption_regions)' % (who, num_beams))
+        if te.get('use_cbs', False):
+            raise NotImplementedError('%s: a visibility mask under beam search is not built for use_cbs' % who)
+        if int(te.get('tag_visible', 0) or 0) > 0:
+            raise NotImplementedError('%s: a visibility mask under beam search is not built for tag_visible > 0 (got %s)'
+                                      % (who, te['tag_visible']))
+        if te.get('do_sample', False):
+            raise NotImplementedError('%s: a visibility mask under beam search is not built for do_sample (beam sampling)' % who)
+        if te.get('use_graph', False):
+            raise NotImplementedError('%s: a visibility mask is not built for use_graph (a captured loop would freeze the mask pointer)' % who)
+        for k in ('prefix_ids', 'forced_ids', 'want_token_logprobs'):
+            if te.get(k) is not None and te.get(k) is not False:
+                raise NotImplementedError('%s: %s -- forced tokens under beam search are not built' % (who, k))
+
+    def _beam_masked_options(self, num_beams, length_penalty, num_keep_best, over):
+        over = {k: v for k, v in over.items() if k not in ('num_beams', 'length_penalty', 'num_keep_best', 'num_return_sequences',
+                                                           'do_sample', 'use_graph', 'prefix_ids', 'forced_ids', 'want_token_logprobs')}
+        return self.gen_options(num_beams=int(num_beams), length_penalty=float(length_penalty), num_keep_best=int(num_keep_best),
+                                num_return_sequences=1, do_sample=False, use_graph=False, **over)
+
+    def _run_beam_masked(self, image, opts, vis_list, slot, whole=False):
+        """The images are encoded and prefilled once under the beam options `opts`; then, with `whole`, one plain beam decode, and one
+        vitcap_engine_decode_beam_masked pass per packed mask (B, 19) of vis_list on that prefill.  A single mask without `whole` is
+        one vitcap_engine_generate_beam_masked call.  -> [(ids (B, keep, L), logprobs (B, keep)), ...], the whole-image result first."""
+        dev, B = self._check_image(image), image.shape[0]
+        for v in vis_list:
+            if tuple(v.shape) != (B, 19):
+                raise ValueError('the packed visibility mask must be (%d, 19), got %s' % (B, tuple(v.shape)))
+        # read in place by the enqueued kernels: allocated and released on this stream, so the blocks are not reused before them
+        vis_list = [v.to(device=dev, dtype=torch.int32).contiguous() for v in vis_list]
+        ws, need = self._workspace(B, dev, slot, opts)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        wp, ip, bf = C.c_void_p(ws.data_ptr()), C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16)
+        self._encoded[slot] = (opts, B)
+        self._last = (slot, opts, B)
+        out = []
+        if len(vis_list) == 1 and not whole:
+            ids, lp = self._out_buffers(B, opts, dev)
+            check(lib.vitcap_engine_generate_beam_masked(self._engine, ip, bf, B, C.byref(opts), wp, need, None, 0, C.c_void_p(ids.data_ptr()),
+                                                         C.c_void_p(lp.data_ptr()), None, None, None, C.c_void_p(vis_list[0].data_ptr()), s),
+                  'engine_generate_beam_masked')
+            return [(ids, lp)]
+        check(lib.vitcap_engine_encode(self._engine, ip, bf, B, C.byref(opts), wp, need, s), 'engine_encode')
+        check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
+        if whole:
+            ids, lp = self._out_buffers(B, opts, dev)
+            check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()),
+                                           None, s), 'engine_decode')
+            out.append((ids, lp))
+        for v in vis_list:
+            ids, lp = self._out_buffers(B, opts, dev)
+            check(lib.vitcap_engine_decode_beam_masked(self._engine, B, C.byref(opts), wp, need, None, 0, C.c_void_p(ids.data_ptr()),
+                                                       C.c_void_p(lp.data_ptr()), None, None, C.c_void_p(v.data_ptr()), s),
+                  'engine_decode_beam_masked')
+            out.append((ids, lp))
+        return out
+
+    def _caption_regions_beam(self, who, image, regions, num_beams, num_keep_best, length_penalty, keep_cls, slot, over, whole):
+        from .occlusion import pack_visible
+        from .regions import region_masks
+        self.refuse_visible_beam(who, num_beams, over)
+        B = image.shape[0]
+        masks, _ = region_masks(regions, B, keep_cls)                  # (B, R, 578)
+        R = masks.shape[1]
+        o = self._beam_masked_options(num_beams, length_penalty, num_keep_best, over)
+        res = self._run_beam_masked(image, o, [pack_visible(masks[:, r]) for r in range(R)], slot, whole=whole)
+        reg = res[1:] if whole else res
+        rids, rlp = torch.stack([x[0] for x in reg], 1), torch.stack([x[1] for x in reg], 1)
+        return (res[0][0], res[0][1], rids, rlp) if whole else (rids, rlp)
+
+    def caption_regions_beam(self, image, regions, num_beams, num_keep_best=1, length_penalty=1.0, keep_cls=True, slot=0, **over):
+        """caption_regions() by beam search: per region of every image its num_keep_best best captions under num_beams beams (2..8),
+        everything outside the region hidden from all beams (generate_beam(visible=) with the region's mask).  regions / keep_cls: as
+        caption_regions().  The images are encoded and prefilled once under the beam options; every region index is one
+        vitcap_engine_decode_beam_masked pass on that prefill.  Bad boxes are a ValueError; num_beams == 1, CBS, visible tags, sampling,
+        use_graph and forced tokens a NotImplementedError naming the option, before the GPU is touched.
+        -> (ids (B, R, num_keep_best, L), logprobs (B, R, num_keep_best)), best first."""
+        return self._caption_regions_beam('caption_regions_beam', image, regions, num_beams, num_keep_best, length_penalty, keep_cls, slot,
+                                          over, False)
+
+    def caption_with_regions_beam(self, image, regions, num_beams, num_keep_best=1, length_penalty=1.0, keep_cls=True, slot=0, **over):
+        """The whole-image beam captions and the region captions of caption_regions_beam() on one encoder pass: generate_beam(image,
+        num_beams, ...) through the staged path, then the region passes on its prefill.
+        -> (ids (B, keep, L), logprobs (B, keep), region ids (B, R, keep, L), region logprobs (B, R, keep))."""
+        return self._caption_regions_beam('caption_with_regions_beam', image, regions, num_beams, num_keep_best, length_penalty, keep_cls,
+                                          slot, over, True)
 
     def generate_cbs(self, image, fsm, num_constraints, num_beams=1, min_constraints_to_satisfy=2, slot=0, **over):
         """Constrained beam search: ViTCAP.generate(use_cbs=True, fsm=fsm, num_constraints=..., min_constraints_to_satisfy=...)

@@ -208,6 +208,26 @@ def attn_decode_beams(qkv_step, vis_qkv, text_kv, n_images, K, S_vis, t, max_len
     return out
 
 
+def attn_decode_beams_masked(qkv_step, vis_qkv, text_kv, vis_mask, n_images, K, S_vis, t, max_len=20, scale=0.125, groups_per_image=1,
+                             out=None):
+    """attn_decode_beams with visual keys hidden per group of K sequences (vitcap_attn_decode_beam_groups_masked); builds V^T first.
+    vis_mask int32 (n_images * groups_per_image, mask_words >= ceil(S_vis / 32)) on the device, bit k & 31 of word k >> 5 set = visual
+    key k visible (vitcap_amd.occlusion.pack_visible at S_vis = 578).  -> bf16 (n_images * groups_per_image * K * 2, 768)."""
+    _dev_bf16(qkv_step)
+    _dev_bf16(vis_qkv)
+    _dev_bf16(text_kv)
+    assert vis_mask.is_cuda and vis_mask.is_contiguous() and vis_mask.dtype == torch.int32
+    assert vis_mask.dim() == 2 and vis_mask.shape[0] == n_images * groups_per_image
+    vt = torch.empty((n_images, 12, 64, 608), device=qkv_step.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_beam_vt(_p(vis_qkv), _p(vt), n_images, S_vis, _stream()), 'attn_beam_vt')
+    if out is None:
+        out = torch.empty((n_images * groups_per_image * K * 2, 768), device=qkv_step.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_decode_beam_groups_masked(_p(qkv_step), _p(vis_qkv), _p(vt), _p(text_kv), _p(out), n_images, K, groups_per_image,
+                                                    S_vis, t, max_len, scale, _p(vis_mask), int(vis_mask.shape[1]), _stream()),
+          'attn_decode_beams_masked')
+    return out
+
+
 def attn_text_grid(qkv_text, vis_qkv, n_images, caps_per_image, S_vis=578, max_len=20, scale=0.125, out=None):
     """Text-grid attention of the one-pass caption scorer (vitcap_attn_text_grid): qkv_text bf16 (n_images * caps_per_image *
     (2 * max_len - 1), 2304) against the images' visual q|k|v rows; builds V^T first.  -> bf16 (rows, 768)."""

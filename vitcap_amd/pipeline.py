@@ -289,13 +289,20 @@ class _PredictRun(object):
             for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
                 yield key, json.dumps(recs)
 
-    def region_rows(self, batches, dev, pred_rows, g):
+    def region_rows(self, batches, dev, pred_rows, g, beams=None):
         """cfg.regions = g: yields the rows of the regions TSV, one per image: the key and a JSON list with one record per tile of the
         g x g tiling -- its pixel rectangle, caption and confidence (vitcap_amd.regions.to_rows) of
-        ImageCaptioning.caption_with_regions."""
+        ImageCaptioning.caption_with_regions.  cfg.regions_beams = k: the tiles' captions are caption_regions_beam's under k beams
+        (a second encoder pass under the beam options); the main caption stays the greedy one of generate()."""
         from .regions import grid_regions, to_rows
         model, boxes = self.model, grid_regions(g)
+
+        def with_beams(img):
+            ids, lp = model.generate(img, gemm_mode=1)
+            rids, rlp = model.caption_regions_beam(img, boxes, beams, gemm_mode=1)
+            return ids, lp, rids[:, :, 0], rlp[:, :, 0]
         for batch, ids_h, lp, (rids, rlp) in self.analysed(batches, dev, pred_rows, 'regions', 'region captions',
+                                                           with_beams if beams else
                                                            lambda img: model.caption_with_regions(img, boxes, gemm_mode=1)):
             for key, recs in zip(batch['key'], to_rows(rids.cpu(), rlp.cpu(), boxes, self.pipe.tokenizer)):
                 yield key, json.dumps(recs)
@@ -723,7 +730,8 @@ class CaptionUniPipeline(object):
             reg_file = self.get_regions_file(predict_result_file)
             reg_sub = reg_file if self.world == 1 else '{}_{}_{}.tsv'.format(reg_file, self.rank, self.world)
             pred_rows = []
-            tsv_writer(run.counted(run.region_rows(batches, dev, pred_rows, int(self.cfg.regions))), reg_sub)
+            tsv_writer(run.counted(run.region_rows(batches, dev, pred_rows, int(self.cfg.regions),
+                                                   int(self.cfg.regions_beams) if self.cfg.regions_beams else None)), reg_sub)
             tsv_writer(iter(pred_rows), sub)
             run.report()
             if self.world > 1:
@@ -764,6 +772,15 @@ class CaptionUniPipeline(object):
         """`regions: g` is refused by name with what the region captions are not built for, before a model is built."""
         from .regions import grid_regions
         cfg = self.cfg
+        k = cfg.regions_beams
+        if k is not None and k is not False:
+            # the tiles' captions by k-beam search (ImageCaptioning.caption_regions_beam); the main caption stays as configured
+            if not cfg.regions:
+                raise ValueError('regions_beams: %r is only valid next to `regions: g` (it sets how the tiles of the g x g tiling are '
+                                 'captioned)' % (k,))
+            if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= 8:
+                raise ValueError('regions_beams: the region captions under beam search take 2..8 beams (got %r); leave the key out for '
+                                 'greedy region captions' % (k,))
         if not cfg.regions:
             return
         grid_regions(cfg.regions)

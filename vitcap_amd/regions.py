@@ -77,8 +77,26 @@ def region_masks(regions, B, keep_cls=True):
 
 def to_rows(ids, logprobs, boxes, tokenizer):
     """One list per image for the regions TSV: per region its pixel rectangle [x0, y0, x1, y1) in the 384 x 384 input, the caption
-    and its confidence exp(logprob).  ids (B, R, L), logprobs (B, R), boxes (R, 4) or (B, R, 4)."""
+    and its confidence exp(logprob).  ids (B, R, L), logprobs (B, R), boxes (R, 4) or (B, R, 4).
+    The n-best shape of caption_regions_beam -- ids (B, R, keep, L), logprobs (B, R, keep), best first: 'caption' and 'conf' are the
+    best hypothesis', and with keep > 1 'nbest' lists all of them as {'caption', 'conf'}; a slot the search left empty (fewer than
+    keep finished hypotheses: score -1e5) is left out."""
     ids = torch.as_tensor(ids).cpu()
+    if ids.dim() == 4:
+        keep = ids.shape[2]
+        lpk = torch.as_tensor(logprobs).cpu()
+        if tuple(lpk.shape) != tuple(ids.shape[:3]):
+            raise ValueError('regions: to_rows needs logprobs %s next to n-best ids %s (got %s)'
+                             % (tuple(ids.shape[:3]), tuple(ids.shape), tuple(lpk.shape)))
+        out = to_rows(ids[:, :, 0], lpk[:, :, 0], boxes, tokenizer)
+        if keep > 1:
+            for i, recs in enumerate(out):
+                for r, rec in enumerate(recs):
+                    rec['nbest'] = [{'caption': tokenizer.decode(ids[i, r, k].tolist(), skip_special_tokens=True),
+                                     'conf': math.exp(float(lpk[i, r, k]))} for k in range(keep) if float(lpk[i, r, k]) > -1e4]
+        return out
+    if ids.dim() != 3:
+        raise ValueError('regions: to_rows needs ids (B, R, L) or (B, R, keep, L) (got %s)' % (tuple(ids.shape),))
     B, R = ids.shape[0], ids.shape[1]
     lp = torch.as_tensor(logprobs).cpu().reshape(B, R).tolist()
     b = check_boxes(boxes)
