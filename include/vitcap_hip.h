@@ -1001,7 +1001,13 @@ int vitcap_adamw_multi(float* p, const float* g, float* m, float* v, const float
  * vision_transformer.py:147-150), straight from the row-major backward operands: Y = dY bf16 [M][ldy] (N columns),
  * X = saved input bf16 [M][ldx] (K columns), reduction over the M = batch x tokens rows.  The M range is cut into
  * `splits` pieces, piece s writes the fp32 slab C_slabs[s][N][K] (deterministic; sum them with vitcap_reduce_slabs).
- * N and K multiples of 256. */
+ * N and K multiples of 256.
+ * The unit of the cut is a 64-row step: with steps = ceil(M / 64) and sps = ceil(steps / splits), piece s covers the rows
+ * [s * sps * 64, min((s + 1) * sps * 64, M)).  A piece that begins at or behind M is empty and writes a slab of zeros, so the sum
+ * over all `splits` slabs is the product whatever the counts; splits > steps is accepted.  Every element of every slab is written
+ * exactly once and nothing else is.  Checked (an error otherwise, nothing written): non-null pointers, M > 0, splits >= 1, N and K
+ * multiples of 256, ldy and ldx multiples of 8, Y and X 16-byte aligned.  NOT checked: ldy >= N, ldx >= K, the size of C_slabs.  Rows
+ * at or behind M are never read. */
 int vitcap_gemm_tn(const void* Y, int ldy, const void* X, int ldx, float* C_slabs, int M, int N, int K, int splits,
                    void* stream);
 /* The same with the sum over the splits done by the launch itself: out[N][K] (+)= sum_s C_slabs[s] in slab order (the result of
@@ -1014,7 +1020,8 @@ int vitcap_gemm_tn_sum(const void* Y, int ldy, const void* X, int ldx, float* C_
                        int K, int splits, void* stream);
 /* bias gradient: out[n] += sum_m y[m][n]  (bf16 [M][ldy] -> fp32 [N], atomic accumulation into `out`) */
 int vitcap_colsum_bf16(const void* y, int ldy, int M, int N, float* out, void* stream);
-/* fp32 master W[N][K] -> bf16 W and bf16 W^T[K][N] (the operands of the forward and the dgrad GEMMs) */
+/* fp32 master W[N][K] -> bf16 W and bf16 W^T[K][N] (the operands of the forward and the dgrad GEMMs), round to nearest even.
+ * Either output may be NULL (not both).  K a multiple of 64, ldt >= N and a multiple of 8; columns N..ldt of W^T are not written. */
 int vitcap_cast_transpose(const float* w, void* w_bf16, void* wt_bf16, int N, int K, int ldt, void* stream);
 /* The same for a table of matrices in one launch (all GEMM weights after an optimizer step).  `items` lives in DEVICE memory,
  * sorted by tile0 = the running sum of ceil(N/64) * (K/64) over the preceding items (item 0: 0); total_tiles = that sum over all
