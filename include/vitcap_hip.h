@@ -218,6 +218,17 @@ int vitcap_attn_dense_fwd(const void* qkv, void* out, int B, int S, float scale,
  * Used for the LAST tag block of TIMMVitSplitEncoder: of its output only the CLS row is ever read
  * (modeling_bert.py:1424 pooler(tag_hidden), 1493 tag_hidden[:, 0] as the first visual token). */
 int vitcap_attn_dense_fwd_rows(const void* qkv, void* out, int B, int S, int q_rows, float scale, void* stream);
+/* vitcap_attn_dense_fwd_rows with keys removed per image: the reference's additive mask of TIMMVitSplitEncoder.forward
+ * (modeling_bert.py:458-478 -> vision_transformer.py:174-182) with -10000 in the removed keys' columns for every query row, and
+ * the zero columns of extended_attention_mask (1498-1501) for the decoder's visual rows.
+ *   key_mask: device uint32 [B][mask_words]; key k of image b is visible iff bit (k + bit0) & 31 of word (k + bit0) >> 5 of
+ *   row b is set.  bit0 is 0 or 1: the encoder's key k is the decoder cache's key k + 1, so one mask in cache order serves both
+ *   (encoder 1, decoder 0).  mask_words >= ceil((S + bit0) / 32), S + bit0 <= 2048; bits past the last key are ignored.
+ * A hidden key's score is -inf before the row maximum; 64-key tiles (keys 64 i .. 64 i + 63) without a visible key and hidden
+ * left-over keys are not read at all, which changes no bit of the result.  Hidden QUERY rows are computed like the others.  An
+ * image with no visible key gets all-zero output rows.  With every bit set the output is vitcap_attn_dense_fwd_rows' bit for bit. */
+int vitcap_attn_dense_fwd_keys(const void* qkv, void* out, int B, int S, int q_rows, float scale, const uint32_t* key_mask,
+                               int mask_words, int bit0, void* stream);
 
 /* Training forms of the dense attention (ViT blocks and the visual rows of the decoder in
  * ViTCAP.encode_forward(is_training=True), modeling_bert.py:751-807): the forward additionally stores the log2-domain
@@ -768,6 +779,23 @@ int vitcap_engine_prefill(vitcap_engine* e, int B, const vitcap_gen_opts* opts, 
                           void* stream);
 int vitcap_engine_decode(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                          int64_t* out_ids, float* out_logprobs, int64_t* out_last_tok, void* stream);
+/* Patch removal: vitcap_engine_encode / vitcap_engine_prefill on an image with patches taken out -- the reference with the removed
+ * keys' columns set to -10000 in the additive mask TIMMVitSplitEncoder.forward hands every block (modeling_bert.py:458-478; ViTCAP.forward
+ * fills it with zeros, 1415) and to 0 in the visual rows' columns of extended_attention_mask (1498-1501).
+ *   patch_mask: device uint32 [B][19] in cache order, read in place: bit 0 the tag-branch CLS, bit 1 the CLS, bit 2 + p patch p
+ *   (row-major on the 24 x 24 grid); a clear bit removes that key from every query row.
+ * encode_patches runs all 12 + 4 ViT blocks through vitcap_attn_dense_fwd_keys with bit0 = 1 (the encoder's key k is cache key k + 1;
+ * both CLS rows read bit 1), prefill_patches the three visual-row attention launches with bit0 = 0.  Every part of
+ * vitcap_gen_opts.encode_parts and the forked tag branch read their own images' rows.  No workspace buffer is added.  The removed
+ * patches' rows are still computed (nothing reads them).  Everything downstream -- vitcap_engine_tags, vitcap_engine_decode_masked,
+ * vitcap_engine_decode_beam_masked, VITCAP_SCORE_MASKED -- runs on the workspace these two calls leave behind; with the same words as
+ * each sequence's vis_mask a removed patch is absent for every row of the model.
+ * VITCAP_EINVAL, naming the cause in vitcap_last_error(): a null or misaligned patch_mask, tag_visible > 0 (the tag rows' prefill is
+ * unmasked), use_graph != 0. */
+int vitcap_engine_encode_patches(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                 void* workspace, size_t workspace_bytes, const uint32_t* patch_mask, void* stream);
+int vitcap_engine_prefill_patches(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                  const uint32_t* patch_mask, void* stream);
 /* vitcap_engine_decode / vitcap_engine_generate with tokens handed in by the caller: caption prefixes (score_forced = 0) and the
  * score of given captions (score_forced = 1) under the same [MASK]-probe procedure generate uses.  The rule is that of
  * vitcap_greedy_step_forced / vitcap_sample_step_forced, applied at every step.

@@ -184,6 +184,7 @@ _SIGS = {
     'vitcap_cls_rows': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
     'vitcap_attn_dense_fwd': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     'vitcap_attn_dense_fwd_rows': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp]),
+    'vitcap_attn_dense_fwd_keys': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp]),
     'vitcap_attn_dense_fwd_train': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32,
                                               C.c_int, C.c_int, vp]),
     'vitcap_attn_dense_bwd': (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -261,6 +262,8 @@ _SIGS = {
     'vitcap_engine_generate': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, vp, vp, vp, vp]),
     'vitcap_engine_encode': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp]),
     'vitcap_engine_prefill': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp]),
+    'vitcap_engine_encode_patches': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, vp]),
+    'vitcap_engine_prefill_patches': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, vp]),
     'vitcap_engine_decode': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, vp, vp, vp]),
     'vitcap_engine_decode_forced': (C.c_int, [vp, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp]),
     'vitcap_engine_generate_forced': (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(GenOpts), vp, C.c_size_t, vp, C.c_int,

@@ -55,12 +55,28 @@ constexpr int DENSE_MINW = 3;            // waves per SIMD the dense kernel is c
 //   block ahead of their MFMAs (16 fewer live registers) instead of all four blocks in front of the softmax.  The anatomy figures came from six timing ablations with wrong results by
 //   construction (no QK^T MFMAs, no exp2 / convert arithmetic, no P.V / row-sum MFMAs, no per-tile barrier, no LDS-DMA after the first
 //   two tiles, no V reads).
-template <bool DROP>
-__global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+//
+// KEYMASK (vitcap_attn_dense_fwd_keys; DROP = false, causal_from = mask_from = 0, lse = nullptr): image b reads row b of key_mask
+// ([B][mask_words] words, the layout of vitcap_attn_text_grid_masked shifted by bit0): key k is visible to every query row of the
+// image iff bit (k + bit0) & 31 of word (k + bit0) >> 5 is set; bits past the last key are ignored.  Lane l of every wave keeps word l
+// of the row in one register (host: S + bit0 <= 2048), so a tile's 64 bits are three v_readlane and scalar shifts away.  A hidden
+// key's score becomes -inf before the running maximum on all three key paths (64-key tiles, the peeled tail tile, the left-over
+// keys).  A tile without a visible key is neither staged nor multiplied, and a hidden left-over key is not loaded: the loop walks
+// the set bits of a wave-uniform bitmap of live tiles, so the ring sees a shorter sequence of tiles and its wait counts and
+// barriers are those of the plain loop over that sequence.  Skipping changes no bit, by the argument above attn_decode_kernel:
+// a hidden key that is not skipped gives p = exp2(fma(-inf, c, -m)) = 0, bf16(0) = 0, the row maximum does not move (every live
+// tile has a finite score for every query row, the mask being per image), and acc + 0 . v = acc for finite v.  With no visible key
+// at all the row sum is 0 and the rows are written as zeros (the normaliser is guarded).
+// The mask is not KEYMASK = false's business: those instances have no use of the three arguments and are the kernel as shipped.
+// It is compiled for two waves per SIMD: at the 168 registers of three waves the in-loop select spills 30 registers, and every
+// reload in the loop waits on vmcnt(0), i.e. for the tile that has just been requested.
+template <bool DROP, bool KEYMASK = false>
+__global__ __launch_bounds__(256, KEYMASK ? 2 : DENSE_MINW) void attn_dense_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                      float* __restrict__ lse, int S, int B, int ld_rows, float c_log2,
                                                                      uint32_t drop_seed, uint32_t drop_thr, float drop_scale,
                                                                      int causal_from, int mask_from, int q_lo, int q_rows, int rev,
-                                                                     const uint32_t* __restrict__ drop_salt) {
+                                                                     const uint32_t* __restrict__ drop_salt,
+                                                                     const uint32_t* __restrict__ key_mask, int mask_words, int bit0) {
   __shared__ __attribute__((aligned(1024))) char smem[NSTG * STG_B];   // [stage][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,6 +116,31 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
   // to caption queries q >= key; they all sit in the masked tail tile (host checks causal_from >= nfull * KT)
   const bool tail_tile = rem > 8 || (causal_from > 0 && rem > 0);   // many left-overs: one masked MFMA tile
   const int ntiles = nfull + (tail_tile ? 1 : 0);
+
+  // ---- KEYMASK: lane l holds word l of the image's mask row with the bits of positions >= S + bit0 cleared (so the tail tile's
+  // rows past the sequence and any garbage behind the last key are hidden keys like the others); km_live bit t = tile t (the
+  // tail tile included) has a visible key, the same value in every wave of the workgroup
+  uint32_t km_words = 0, km_live = 0, km_lo = 0, km_hi = 0;
+  if (KEYMASK) {
+    const int nbits = S + bit0 - lane * 32;                        // mask positions of this word that lie inside the row
+    if (nbits > 0) km_words = key_mask[(size_t)b * mask_words + lane];
+    if (nbits < 32) km_words = nbits > 0 ? km_words & ((1u << nbits) - 1u) : 0u;
+    // tile t = lane's keys sit at positions 64 t + bit0 .. + 63: words 2t, 2t + 1 and bit 0 of word 2t + 2
+    const uint32_t w0 = (uint32_t)__shfl((int)km_words, (2 * lane) & 63, 64), w1 = (uint32_t)__shfl((int)km_words, (2 * lane + 1) & 63, 64);
+    const uint32_t w2 = (uint32_t)__shfl((int)km_words, (2 * lane + 2) & 63, 64);
+    const bool any = bit0 ? ((w0 >> 1) | w1 | (lane < 31 ? (w2 & 1u) : 0u)) != 0u : (w0 | w1) != 0u;
+    km_live = (uint32_t)__builtin_amdgcn_ballot_w64(lane < ntiles && lane < 32 && any);
+  }
+  // wave-uniform reads of the register row: the two words of tile t_'s keys, and one key's bit
+#define KM_TILE_WORDS(t_)                                                                                       \
+  do {                                                                                                          \
+    const uint32_t a_ = (uint32_t)__builtin_amdgcn_readlane((int)km_words, 2 * (t_));                            \
+    const uint32_t b_ = (uint32_t)__builtin_amdgcn_readlane((int)km_words, 2 * (t_) + 1);                        \
+    const uint32_t c_ = (t_) < 31 ? (uint32_t)__builtin_amdgcn_readlane((int)km_words, (2 * (t_) + 2) & 63) : 0u; \
+    km_lo = bit0 ? (a_ >> 1) | (b_ << 31) : a_;                                                                 \
+    km_hi = bit0 ? (b_ >> 1) | (c_ << 31) : b_;                                                                 \
+  } while (0)
+#define KM_KEY_VISIBLE(k_) ((((uint32_t)__builtin_amdgcn_readlane((int)km_words, ((k_) + bit0) >> 5) >> (((k_) + bit0) & 31)) & 1u) != 0u)
 
   // ---- staging: each wave moves rows [8w, 8w+8) and [32+8w, 32+8w+8) of the K and of the V tile (4 LDS-DMA pieces of 1 KiB);
   // lane l lands at LDS byte 16 l of the piece = row l>>3, physical chunk l&7, so it FETCHES logical chunk (l&7) ^ swz(row)
@@ -158,7 +199,7 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
   const bool left = active && !tail_tile && key0 < S;
   bf16x8 lk[4];
   bf16x4 lv[2][4];
-  if (left) {
+  if (left && (!KEYMASK || KM_KEY_VISIBLE(key0))) {
     const bf16_t* kr = base + (size_t)key0 * QKV_LD + 768 + half * 8;
     const bf16_t* vr = base + (size_t)key0 * QKV_LD + 1536 + 4 * half;
 #pragma unroll
@@ -168,10 +209,26 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
 #pragma unroll
       for (int g = 0; g < 4; ++g) lv[dt][g] = *(const bf16x4*)(vr + dt * 32 + g * 8);
   }
-  if (ntiles > 0) STAGE_TILE(0, 0);
-  if (ntiles > 1) STAGE_TILE(1, 1);
+  // KEYMASK: the ring walks the live tiles only -- kc0 is the tile being multiplied, kc1 the one behind it (-1: none)
+  uint32_t km_rest = km_live;
+  int kc0 = -1, kc1 = -1;
+#define KM_NEXT_TILE(dst_)                                                                                      \
+  do {                                                                                                          \
+    dst_ = km_rest ? __builtin_ctz(km_rest) : -1;                                                               \
+    km_rest &= km_rest - 1u;                                                                                    \
+  } while (0)
+  if (KEYMASK) {
+    KM_NEXT_TILE(kc0);
+    KM_NEXT_TILE(kc1);
+    if (kc0 >= 0) STAGE_TILE(kc0, 0);
+    if (kc1 >= 0) STAGE_TILE(kc1, 1);
+  } else {
+    if (ntiles > 0) STAGE_TILE(0, 0);
+    if (ntiles > 1) STAGE_TILE(1, 1);
+  }
   if (left) {
     for (int key = key0; key < S; ++key) {
+      if (KEYMASK && !KM_KEY_VISIBLE(key)) continue;   // wave-uniform: a hidden left-over key is not loaded
       if (key > key0) {
         const bf16_t* kr = base + (size_t)key * QKV_LD + 768 + half * 8;
         const bf16_t* vr = base + (size_t)key * QKV_LD + 1536 + 4 * half;
@@ -246,6 +303,17 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
           st[kt][r] = vis_ ? st[kt][r] : -INFINITY;                                                             \
         }                                                                                                       \
     }                                                                                                           \
+    if (KEYMASK) { /* km_lo / km_hi: the tile's 64 visibility bits; the lane's key of register r is bit (r&3) + 8 (r>>2) + 4 half of  \
+                      its 32-key block: one bit-field extract and one bit select per score */                   \
+      _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) {                                                        \
+        const uint32_t hw_ = (kt ? km_hi : km_lo) >> (4 * half);                                                \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                        \
+          const uint32_t vm_ = (uint32_t)((int32_t)(hw_ << (31 - ((r & 3) + 8 * (r >> 2)))) >> 31);             \
+          const float s_ = st[kt][r];                                                                           \
+          st[kt][r] = __uint_as_float((__float_as_uint(s_) & vm_) | (0xFF800000u & ~vm_));                      \
+        }                                                                                                       \
+      }                                                                                                         \
+    }                                                                                                           \
     /* running max on the raw scores (scale > 0), integer ceiling in the log2 domain */                         \
     /* 32 scores -> 16 v_max3 / v_max in a tree (max is exact: any order gives the same value) */               \
     float ma_[5], mb_[5];                                                                                       \
@@ -299,28 +367,50 @@ __global__ __launch_bounds__(256, DENSE_MINW) void attn_dense_kernel(const bf16_
   } while (0)
 
   int stg = 0;                       // ring slot of tile t (wave-uniform)
-  for (int t = 0; t < nfull; ++t) {
-    // tile t landed (this wave's 4 pieces; tile t+1's 4 may stay in flight), then for every wave -- and every wave is done with
-    // tile t-1, whose slot the next request is about to overwrite
-    if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t + 2 < ntiles) STAGE_TILE(t + 2, stg == 0 ? 2 : stg - 1);   // (stg + 2) % 3
-    if (active) TILE_COMPUTE(stg, t, false);
-    stg = stg == 2 ? 0 : stg + 1;
-  }
-  if (tail_tile) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (active) TILE_COMPUTE(stg, nfull, true);
+  if (KEYMASK) {
+    // the loop below over the live tiles kc0 -> kc1 -> kc2 (the tail tile is one of them: its rows past the sequence are hidden
+    // keys); one tile in flight behind the current one <=> this wave's last four pieces may stay outstanding
+    while (kc0 >= 0) {
+      if (kc1 >= 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      int kc2;
+      KM_NEXT_TILE(kc2);
+      if (kc2 >= 0) STAGE_TILE(kc2, stg == 0 ? 2 : stg - 1);
+      KM_TILE_WORDS(kc0);
+      if (active) TILE_COMPUTE(stg, kc0, false);
+      stg = stg == 2 ? 0 : stg + 1;
+      kc0 = kc1;
+      kc1 = kc2;
+    }
+  } else {
+    for (int t = 0; t < nfull; ++t) {
+      // tile t landed (this wave's 4 pieces; tile t+1's 4 may stay in flight), then for every wave -- and every wave is done with
+      // tile t-1, whose slot the next request is about to overwrite
+      if (t + 1 < ntiles) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (t + 2 < ntiles) STAGE_TILE(t + 2, stg == 0 ? 2 : stg - 1);   // (stg + 2) % 3
+      if (active) TILE_COMPUTE(stg, t, false);
+      stg = stg == 2 ? 0 : stg + 1;
+    }
+    if (tail_tile) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (active) TILE_COMPUTE(stg, nfull, true);
+    }
   }
 #undef TILE_COMPUTE
 #undef STAGE_TILE
+#undef KM_NEXT_TILE
+#undef KM_KEY_VISIBLE
+#undef KM_TILE_WORDS
 
   // ---- normalise and store: lane holds O[q][dt*32 + 8*g + 4*half + 0..3]; every register of lacc holds the MFMA part of
   // the row sum, l_i the left-over keys' part (one half-wave)
   const float l_tot = lacc[0] + l_i + __shfl_xor(l_i, 32, 64);
-  const float inv = DROP ? drop_scale / l_tot : 1.0f / l_tot;
+  float inv = DROP ? drop_scale / l_tot : 1.0f / l_tot;
+  if (KEYMASK && !(l_tot > 0.f)) inv = 0.f;   // no visible key: the accumulators are still +0, the rows are written as zeros
   const int q = q0 + qi;
   if (lse && q < S && half == 0) lse[((size_t)b * NH + h) * S + q] = m_i + log2f(l_tot);   // log2-domain logsumexp (training)
   if (q < S) {
@@ -966,7 +1056,8 @@ static int attn_decode_groups(const char* who, const void* qkv_step, const void*
 
 
 #define VC_LAUNCH_DENSE(DROP_, grid_, stream_, ...)                                                             \
-  hipLaunchKernelGGL(attn_dense_kernel<DROP_>, grid_, dim3(256), 0, (hipStream_t)(stream_), __VA_ARGS__, vc_tls_walk_rev ? 1 : 0, vc_tls_drop_salt)
+  hipLaunchKernelGGL(attn_dense_kernel<DROP_>, grid_, dim3(256), 0, (hipStream_t)(stream_), __VA_ARGS__, vc_tls_walk_rev ? 1 : 0, vc_tls_drop_salt, \
+                     (const uint32_t*)nullptr, 0, 0)
 
 extern "C" int vitcap_attn_dense_fwd(const void* qkv, void* out, int B, int S, float scale, void* stream) {
   VC_REQUIRE(qkv && out && B > 0 && S > 0, "attn_dense: bad arguments");
@@ -985,6 +1076,24 @@ extern "C" int vitcap_attn_dense_fwd_rows(const void* qkv, void* out, int B, int
   dim3 grid(((q_rows + 127) / 128) * NH * B);
   VC_LAUNCH_DENSE(false, grid, stream, (const bf16_t*)qkv, (bf16_t*)out, (float*)nullptr, S, B, S, c, 0u, 0u, 1.0f, 0, 0, 0, q_rows);
   VC_LAUNCH_CHECK("attn_dense_rows");
+  return VITCAP_OK;
+}
+
+extern "C" int vitcap_attn_dense_fwd_keys(const void* qkv, void* out, int B, int S, int q_rows, float scale, const uint32_t* key_mask,
+                                          int mask_words, int bit0, void* stream) {
+  VC_REQUIRE(qkv && out && B > 0 && S > 0 && q_rows >= 1 && q_rows <= S, "attn_dense_keys: bad arguments");
+  VC_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0, "attn_dense_keys: misaligned");
+  VC_REQUIRE(key_mask && ((uintptr_t)key_mask & 3) == 0, "attn_dense_keys: key_mask is null or not 4-byte aligned");
+  VC_REQUIRE(bit0 == 0 || bit0 == 1, "attn_dense_keys: bit0 must be 0 or 1, got %d", bit0);
+  VC_REQUIRE(S + bit0 <= 2048, "attn_dense_keys: S + bit0 = %d exceeds the 2048 mask positions one wave holds", S + bit0);
+  VC_REQUIRE(mask_words >= (S + bit0 + 31) / 32, "attn_dense_keys: mask_words %d < %d words for S=%d, bit0=%d", mask_words,
+             (S + bit0 + 31) / 32, S, bit0);
+  const float c = scale * 1.4426950408889634f;
+  dim3 grid(((q_rows + 127) / 128) * NH * B);
+  constexpr auto kernel = attn_dense_kernel<false, true>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, (float*)nullptr, S, B, S, c, 0u, 0u,
+                     1.0f, 0, 0, 0, q_rows, vc_tls_walk_rev ? 1 : 0, vc_tls_drop_salt, key_mask, mask_words, bit0);
+  VC_LAUNCH_CHECK("attn_dense_keys");
   return VITCAP_OK;
 }
 

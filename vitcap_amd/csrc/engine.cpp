@@ -210,6 +210,9 @@ struct Enq {
   int forced = -1;
   // region captions (vitcap_engine_decode_masked): the caller's device array [NS][MASK_WORDS], read in place by the attention launches
   const uint32_t* vis_mask = nullptr;
+  // patch removal (vitcap_engine_encode_patches / _prefill_patches): the caller's device array [B][MASK_WORDS] in cache order, row 0 =
+  // the first image THIS context covers; every dense attention launch of the encoder (bit0 = 1) and of the prefill (bit0 = 0) reads it
+  const uint32_t* patch_mask = nullptr;
 
   Enq(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, void* s, Phase ph)
       : e(e), w(e->w), o(o), lo(lo), ws(ws), B(B), s(s),
@@ -227,7 +230,8 @@ struct Enq {
   }
   Enq(const Enq&) = delete;
   // the same call seen by another chain of it: other images and / or another stream
-  Enq view(const Layout& lv, int Bv, void* sv) const { return Enq(*this, lv, Bv, sv); }
+  // first_image: the view's first image within this context (a part reads its own images' rows of patch_mask)
+  Enq view(const Layout& lv, int Bv, void* sv, int first_image = 0) const { return Enq(*this, lv, Bv, sv, first_image); }
   Enq on(void* sv) const { return view(lo, B, sv); }
 
   template <class T = char>
@@ -319,6 +323,13 @@ struct Enq {
   // have_ln1: `h` already holds norm1(x_in) (written by the previous block's fc2, below).  next: the block that consumes this one's
   // output on the same chain, or null -- its norm1 then rides in this block's fc2 (-> h); norm2 always rides in proj.  Each fused
   // LayerNorm is the separate vitcap_layernorm_fwd launch's arithmetic on the same fp32 rows (vitcap_gemm_desc.ln_*).
+  // The dense attention of the encoder blocks (bit0 = 1: encoder key k is cache key k + 1) and of the prefill's visual rows (bit0 = 0):
+  // the shipped launch, or under patch removal the KEYMASK instance on this context's rows of the mask.
+  int attn_dense(const void* qkv, void* out, int S, int q_rows, int bit0) const {
+    if (patch_mask) return vitcap_attn_dense_fwd_keys(qkv, out, B, S, q_rows, 0.125f, patch_mask, MASK_WORDS, bit0, s);
+    return q_rows == S ? vitcap_attn_dense_fwd(qkv, out, B, S, 0.125f, s) : vitcap_attn_dense_fwd_rows(qkv, out, B, S, q_rows, 0.125f, s);
+  }
+
   int vit_block(const vitcap_vit_block_w& bw, const float* x_in, float* x, void* h, void* qkv, void* mlp, bool have_ln1 = false,
                 const vitcap_vit_block_w* next = nullptr) const {
     const int M = B * NV;
@@ -327,7 +338,7 @@ struct Enq {
     if (!have_ln1) { CK(vitcap_layernorm_fwd(x_in, D, bw.n1_g, bw.n1_b, 1e-6f, h, nullptr, M, D, s)); zz(); }
     CK(gemm(h, D, bw.qkv_w, bw.qkv_b, nullptr, 0, qkv, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
     zz();
-    CK(vitcap_attn_dense_fwd(qkv, h, B, NV, 0.125f, s));
+    CK(attn_dense(qkv, h, NV, NV, 1));
     zz();
     // proj reads h (the attention output) as A and its norm2 writes h: a row block's A rows are read by its own three tiles only
     CK(gemm_ln(h, D, bw.proj_w, bw.proj_b, x_in, x, M, D, bw.n2_g, bw.n2_b, 1e-6f, h, nullptr));      // GEMM, LayerNorm: two flips = none
@@ -352,7 +363,7 @@ struct Enq {
     CK(gemm(h, D, (const char*)bw.qkv_w + (size_t)D * D * 2, bw.qkv_b + D, nullptr, 0, (char*)qkv + (size_t)D * 2, 3 * D, M, 2 * D, D,
             VITCAP_ACT_NONE, VITCAP_OUT_BF16));                                         // K | V of every row
     CK(gemm(h, RS, bw.qkv_w, bw.qkv_b, nullptr, 0, qkv, NV * 3 * D, B, D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));   // Q of the CLS rows
-    CK(vitcap_attn_dense_fwd_rows(qkv, h, B, NV, 1, 0.125f, s));
+    CK(attn_dense(qkv, h, NV, 1, 1));
     CK(gemm(h, RS, bw.proj_w, bw.proj_b, x, RS, x, RS, B, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32));
     CK(vitcap_layernorm_fwd(x, RS, bw.n2_g, bw.n2_b, 1e-6f, cls_h, nullptr, B, D, s));
     CK(gemm(cls_h, D, bw.fc1_w, bw.fc1_b, nullptr, 0, mlp, 4 * D, B, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16));
@@ -476,7 +487,7 @@ struct Enq {
       CK(gemm(vis_b, D, lw.qkv_w, lw.qkv_b, nullptr, 0, dq, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
       zz();
       if (lo.vt[l]) CK(vitcap_attn_beam_vt(dq, ws + lo.vt[l], B, SV, s));
-      CK(vitcap_attn_dense_fwd(dq, ws + lo.h, B, SV, 0.125f, s));
+      CK(attn_dense(dq, ws + lo.h, SV, SV, 0));
       zz();
       // BertSelfOutput / BertOutput: dense + residual, then LayerNorm (post-LN)
       CK(gemm_ln(ws + lo.h, D, lw.ao_w, lw.ao_b, vis_f, ws + lo.dtmp, M, D, lw.ao_g, lw.ao_beta, 1e-12f, ws + lo.da_b, p<float>(lo.da_f)));
@@ -521,7 +532,7 @@ struct Enq {
     for (int i = 0; i <= np; ++i) i0[i] = (int)((long long)B * i / np);
     Layout lv[4];
     for (int i = 0; i < np; ++i) lv[i] = lo.from_image(i0[i]);
-    auto part = [&](int i) { return view(lv[i], i0[i + 1] - i0[i], i == 0 ? s : (void*)e->part[i - 1]); };
+    auto part = [&](int i) { return view(lv[i], i0[i + 1] - i0[i], i == 0 ? s : (void*)e->part[i - 1], i0[i]); };
     for (int i = 0; i < np; ++i) {
       if (i > 0) CK(ev_wait(part(i).s, e->ev_pfork, "encode: split", "fork"));
       CK(part(i).encode_part((const char*)image + (size_t)i0[i] * img_bytes, image_is_bf16, false));
@@ -786,8 +797,9 @@ struct Enq {
   }
 
  private:
-  Enq(const Enq& q, const Layout& lv, int Bv, void* sv)
-      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced), vis_mask(q.vis_mask) {}
+  Enq(const Enq& q, const Layout& lv, int Bv, void* sv, int first_image)
+      : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced), vis_mask(q.vis_mask),
+        patch_mask(q.patch_mask ? q.patch_mask + (size_t)first_image * MASK_WORDS : nullptr) {}
 };
 
 vitcap_gen_opts opts_or_default(const vitcap_gen_opts* opts) { return opts ? *opts : default_opts(); }
@@ -997,6 +1009,39 @@ extern "C" int vitcap_engine_prefill(vitcap_engine* e, int B, const vitcap_gen_o
   CK(enter(e, B, o, workspace, workspace_bytes, lo));
   std::lock_guard<std::mutex> lk(e->mu);
   return Enq(e, B, o, lo, (char*)workspace, s, Enq::ENCODE).prefill();
+}
+
+// patch removal: the options a removed patch cannot be honoured under, and the mask pointer, before anything is enqueued
+static int check_patches(const char* who, const vitcap_gen_opts& o, const uint32_t* patch_mask) {
+  if (!patch_mask) { vitcap_set_error("%s: patch_mask is null", who); return VITCAP_EINVAL; }
+  if (((uintptr_t)patch_mask & 3) != 0) { vitcap_set_error("%s: patch_mask is not 4-byte aligned", who); return VITCAP_EINVAL; }
+  if (o.tag_visible > 0) { vitcap_set_error("%s: tag_visible > 0 is not supported under patch removal (the tag rows' prefill is unmasked)", who); return VITCAP_EINVAL; }
+  if (o.use_graph != 0) { vitcap_set_error("%s: use_graph = 1 is not supported under patch removal (a captured loop would freeze this call's mask)", who); return VITCAP_EINVAL; }
+  return VITCAP_OK;
+}
+
+extern "C" int vitcap_engine_encode_patches(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                            void* workspace, size_t workspace_bytes, const uint32_t* patch_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Layout lo;
+  CK(check_patches("encode_patches", o, patch_mask));      // by name, before the workspace these options would size is looked at
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  Enq q(e, B, o, lo, (char*)workspace, s, Enq::ENCODE);
+  q.patch_mask = patch_mask;
+  return q.encode(image, image_is_bf16);
+}
+
+extern "C" int vitcap_engine_prefill_patches(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
+                                             const uint32_t* patch_mask, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  Layout lo;
+  CK(check_patches("prefill_patches", o, patch_mask));      // by name, before the workspace these options would size is looked at
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  std::lock_guard<std::mutex> lk(e->mu);
+  Enq q(e, B, o, lo, (char*)workspace, s, Enq::ENCODE);
+  q.patch_mask = patch_mask;
+  return q.prefill();
 }
 
 extern "C" int vitcap_engine_decode(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,

@@ -96,6 +96,12 @@ class _Pending(object):
         return self.ids, self.lp
 
 
+class _PatchEncoded(tuple):
+    """self._encoded[slot] after a patch-removed encoding (ImageCaptioning.tag_patches / caption_patches / ...): the usual (opts, B)
+    plus `words`, the packed presence rows (B, 19) on the device.  Any later encoding on the slot stores a plain tuple again."""
+    words = None
+
+
 class ImageCaptioning(nn.Module):
     """ViT-B/16-384 + tag head + 4-layer BERT caption decoder, greedy decode on MI355X."""
 
@@ -465,6 +471,7 @@ class ImageCaptioning(nn.Module):
         else:
             if slot not in self._encoded:
                 raise RuntimeError('no encoded images on slot %r (call run / generate / score on it first)' % (slot,))
+            self._refuse_patch_slot('run(image=None)', slot)
             o_last, B = self._encoded[slot]
             if opts.max_length != o_last.max_length or o_last.tag_visible > 0:
                 raise ValueError('the last call on slot %r ran other options (max_length / tags)' % (slot,))
@@ -678,6 +685,7 @@ class ImageCaptioning(nn.Module):
         else:
             if slot not in self._encoded:
                 raise RuntimeError('%s: no encoded images on slot %r (call run / generate / score on it first)' % (who, slot))
+            self._refuse_patch_slot(who, slot)
             o_last, B = self._encoded[slot]
             o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
             o.seqs_per_image = o_last.seqs_per_image      # the workspace of that call, as it was laid out
@@ -1059,6 +1067,150 @@ class ImageCaptioning(nn.Module):
         -> (ids (B, keep, L), logprobs (B, keep), region ids (B, R, keep, L), region logprobs (B, R, keep))."""
         return self._caption_regions_beam('caption_with_regions_beam', image, regions, num_beams, num_keep_best, length_penalty, keep_cls,
                                           slot, over, True)
+
+    # ---- patch removal: tags, captions and scores of an image with patches taken out of EVERY attention row of the model
+    # (vitcap_engine_encode_patches / vitcap_engine_prefill_patches, then the `_masked` calls with the same words)
+    def _refuse_patch_slot(self, who, slot):
+        """The `*_encoded` calls carry no presence mask: on a slot that holds a patch-removed encoding they would let the caption
+        rows see the removed patches' rows."""
+        if isinstance(self._encoded.get(slot), _PatchEncoded):
+            raise RuntimeError('%s: slot %r holds a patch-removed encoding (tag_patches / caption_patches / score_patches / caption_crops); '
+                               'this call carries no presence mask, so the removed patches would be visible to it -- encode the images '
+                               'again, or use the *_patches calls' % (who, slot))
+
+    def refuse_patches(self, who, over=None):
+        """Patch removal exists for the greedy loop and the one-pass scorer without visible tags and without a hipGraph: anything else
+        is refused by the option's name, before the GPU is touched."""
+        te = dict(self.test_extra_input)
+        te.update(over or {})
+        if te.get('use_cbs', False):
+            raise NotImplementedError('%s: patch removal is not built for use_cbs' % who)
+        if int(te.get('num_beams', 1) or 1) > 1:
+            raise NotImplementedError('%s: patch removal is not built for num_beams > 1 (got %s): forced tokens and searches under '
+                                      'beams are not built for it' % (who, te['num_beams']))
+        if int(te.get('tag_visible', 0) or 0) > 0:
+            raise NotImplementedError('%s: patch removal is not built for tag_visible > 0 (got %s): the tag rows\' prefill is unmasked'
+                                      % (who, te['tag_visible']))
+        if te.get('use_graph', False):
+            raise NotImplementedError('%s: patch removal is not built for use_graph: a captured loop would freeze this call\'s mask' % who)
+        if te.get('do_sample', False):
+            raise NotImplementedError('%s: patch removal writes greedy captions; do_sample is not built for it' % who)
+
+    def _patch_options(self, who, over):
+        self.refuse_patches(who, over)
+        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
+        return self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+
+    def _encode_patches(self, image, words, o, slot):
+        """Encoder and prefill of `image` under the packed presence rows `words` (B, 19) -> (workspace, bytes, words on the device)."""
+        dev, B = self._check_image(image), image.shape[0]
+        if tuple(words.shape) != (B, 19):
+            raise ValueError('the packed presence mask must be (%d, 19), got %s' % (B, tuple(words.shape)))
+        # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
+        words = words.to(device=dev, dtype=torch.int32).contiguous()
+        ws, need = self._workspace(B, dev, slot, o)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        wp, mp = C.c_void_p(ws.data_ptr()), C.c_void_p(words.data_ptr())
+        check(lib.vitcap_engine_encode_patches(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
+                                               wp, need, mp, s), 'engine_encode_patches')
+        check(lib.vitcap_engine_prefill_patches(self._engine, B, C.byref(o), wp, need, mp, s), 'engine_prefill_patches')
+        enc = _PatchEncoded((o, B))
+        enc.words = words
+        self._encoded[slot] = enc
+        self._last = (slot, o, B)
+        return ws, need, words
+
+    def _tags_of_slot(self, o, B, ws, slot):
+        """(tag_logits (B, 30522), tag_topk (B, 50), tag_prob (B, 50), tag_len (B,)) of the encoding on `slot`."""
+        dev = ws.device
+        logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev)
+        topk = torch.empty((B, 50), dtype=torch.int64, device=dev)
+        check(lib.vitcap_engine_tags(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), C.c_void_p(logits.data_ptr()),
+                                     C.c_void_p(topk.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'engine_tags')
+        return (logits, topk, self.tap('tag_prob', B, (B, 50), slot=slot, opts=o),
+                self.tap('tag_len', B, (B,), dtype=torch.int64, slot=slot, opts=o))
+
+    def tag_patches(self, image, present, slot=0, **over):
+        """The concept tagger on the images without their absent patches: `present` is a (B, 24, 24) or (B, 576) bool (row-major
+        patch grid; the two cls keys are always present), and an absent patch is removed as a key from every attention row of all
+        12 + 4 ViT blocks -- the reference's additive ViT mask with -10000 in that column (modeling_bert.py:458-478).  Runs the encoder
+        (and the prefill) only and leaves the slot encoded for the other *_patches calls.
+        -> (tag_logits (B, 30522), tag_topk (B, 50), tag_prob (B, 50), tag_len (B,))."""
+        from .patches import pack_present
+        o = self._patch_options('tag_patches', over)
+        words = pack_present(present, image.shape[0])
+        ws, _, _ = self._encode_patches(image, words, o, slot)
+        return self._tags_of_slot(o, image.shape[0], ws, slot)
+
+    def caption_patches(self, image, present, want_tags=False, want_token_logprobs=False, slot=0, **over):
+        """The greedy caption of the images without their absent patches (`present` as tag_patches takes it): the encoder, the
+        decoder's visual rows and the caption rows all run without those keys, which is the reference with the column at -10000 in the
+        ViT mask and at 0 in attention_mask.  With every patch present the result is generate()'s, bit for bit.
+        -> (ids (B, 1, L), logprobs (B, 1)) [+ token_logprobs (B, L)]; with want_tags, self.last_tags = (tag_logits, tag_topk) and
+        self.last_tag_probs = (tag_prob, tag_len).  CBS, beams, visible tags, use_graph and sampling are a NotImplementedError."""
+        from .patches import pack_present
+        o = self._patch_options('caption_patches', over)
+        B = image.shape[0]
+        words = pack_present(present, B)
+        ws, need, words = self._encode_patches(image, words, o, slot)
+        if want_tags:
+            tags = self._tags_of_slot(o, B, ws, slot)
+            self.last_tags, self.last_tag_probs = tags[:2], tags[2:]
+        ids, lp = self._out_buffers(B, o, ws.device)
+        tok_lp = torch.empty((B, o.max_length), dtype=torch.float32, device=ws.device) if want_token_logprobs else None
+        check(lib.vitcap_engine_decode_masked(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, None, 0,
+                                              C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()),
+                                              C.c_void_p(tok_lp.data_ptr()) if want_token_logprobs else None, None,
+                                              C.c_void_p(words.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              'engine_decode_masked')
+        return (ids, lp, tok_lp) if want_token_logprobs else (ids, lp)
+
+    def score_patches(self, image, caption_ids, present, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
+        """score(one_pass=True) of GIVEN captions on the images without their absent patches: encoder and prefill under `present`
+        (one row per image), then the one-pass scorer with the same words hidden from every caption of the image (VITCAP_SCORE_MASKED).
+        -> (logprob (rows,), token_logprobs (rows, L)); with return_ids also the ids."""
+        from .patches import pack_present
+        K = int(seqs_per_image)
+        B = image.shape[0]
+        self.refuse_patches('score_patches', over)
+        words = pack_present(present, B)
+        o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, dict(over, use_graph=False))
+        _, _, words = self._encode_patches(image, words, o, slot)
+        return self._score_one_pass(None, B, o, cap, lt, K, slot, self._packed[2], return_ids, vis=words.repeat_interleave(K, 0))
+
+    def caption_crops(self, image, regions, slot=0, **over):
+        """Tags and greedy caption of every region of every image SEEN ALONE: each (image, region) pair is encoded as an image of its
+        own with every patch outside the region removed (caption_patches with the region as `present`).  regions: as caption_regions
+        takes them.  The pairs are encoded in passes of up to patches.MAX_CROPS; each pass gathers its own images.
+        -> (ids (B, R, L), logprobs (B, R), tag_topk (B, R, 50), tag_prob (B, R, 50))."""
+        from .patches import MAX_CROPS, crop_masks
+        self.refuse_patches('caption_crops', over)
+        B = image.shape[0]
+        present, _ = crop_masks(regions, B)                   # (B, R, 24, 24)
+        R = present.shape[1]
+        self._check_image(image)
+        pair_b = torch.arange(B).repeat_interleave(R)
+        pair_r = torch.arange(R).repeat(B)
+        out = [[], [], [], []]
+        for p0 in range(0, B * R, MAX_CROPS):
+            pb, pr = pair_b[p0:p0 + MAX_CROPS], pair_r[p0:p0 + MAX_CROPS]
+            ids, lp = self.caption_patches(image.index_select(0, pb.to(image.device)), present[pb, pr], want_tags=True, slot=slot, **over)
+            for dst, x in zip(out, (ids[:, 0], lp[:, 0], self.last_tags[1], self.last_tag_probs[0])):
+                dst.append(x)
+        ids, lp, topk, prob = (torch.cat(x, 0) for x in out)
+        return ids.view(B, R, -1), lp.view(B, R), topk.view(B, R, 50), prob.view(B, R, 50)
+
+    def caption_with_crops(self, image, regions, slot=0, **over):
+        """The whole-image greedy caption and tags, then caption_crops().
+        -> (ids (B, 1, L), logprobs (B, 1), tag_topk (B, 50), tag_prob (B, 50), crop ids (B, R, L), crop logprobs (B, R),
+            crop tag_topk (B, R, 50), crop tag_prob (B, R, 50))."""
+        from .patches import crop_masks
+        self.refuse_patches('caption_with_crops', over)
+        B = image.shape[0]
+        crop_masks(regions, B)                                # the refusals, before the GPU is touched
+        ids, lp = self.caption_patches(image, torch.ones((B, 24, 24), dtype=torch.bool), want_tags=True, slot=slot, **over)
+        topk, prob = self.last_tags[1], self.last_tag_probs[0]
+        return (ids, lp, topk, prob) + self.caption_crops(image, regions, slot=slot, **over)
 
     def generate_cbs(self, image, fsm, num_constraints, num_beams=1, min_constraints_to_satisfy=2, slot=0, **over):
         """Constrained beam search: ViTCAP.generate(use_cbs=True, fsm=fsm, num_constraints=..., min_constraints_to_satisfy=...)

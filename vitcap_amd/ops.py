@@ -137,6 +137,20 @@ def attn_dense(qkv, B, S, scale=0.125):
     return out
 
 
+def attn_dense_keys(qkv, B, S, key_mask, bit0=0, q_rows=None, scale=0.125, out=None):
+    """attn_dense with keys removed per image: key_mask is cuda int32 / uint32 (B, mask_words); key k of image b is visible iff bit
+    (k + bit0) & 31 of word (k + bit0) >> 5 of row b is set (occlusion.pack_visible's layout; bit0 = 1 reads a decoder-order mask
+    for the encoder, whose key k is the cache's key k + 1).  Only the first q_rows query rows are wanted (default: all)."""
+    _dev_bf16(qkv)
+    assert qkv.shape == (B * S, 2304)
+    assert key_mask.is_cuda and key_mask.is_contiguous() and key_mask.dim() == 2 and key_mask.shape[0] == B and key_mask.element_size() == 4
+    if out is None:
+        out = torch.empty((B * S, 768), device=qkv.device, dtype=torch.bfloat16)
+    check(lib.vitcap_attn_dense_fwd_keys(_p(qkv), _p(out), B, S, S if q_rows is None else q_rows, scale, _p(key_mask),
+                                         key_mask.shape[1], bit0, _stream()), 'attn_dense_keys')
+    return out
+
+
 def attn_dense_train(qkv, B, S, scale=0.125, ld_rows=None, out=None, p_drop=0.0, drop_seed=0, causal_from=0, mask_from=0,
                      q_range=None):
     """forward that also returns the log2-domain logsumexp (B,12,S) needed by attn_dense_bwd; ld_rows = rows per image
