@@ -624,6 +624,27 @@ int vitcap_attn_text_grid_masked(const void* qkv_text, const void* vis_qkv, cons
 int vitcap_attn_probe_maps(const void* qkv_text, const void* vis_qkv, const int64_t* caption_ids, float* out, int n_images,
                            int caps_per_image, int S_vis, int max_len, int per_head, int eos, const int32_t* eos_extra, float scale,
                            void* stream);
+/* Self-attention probabilities of one ViT block, written out (csrc/attn_self_maps.hip): the `attn` of timm's Attention.forward after
+ * its softmax (vision_transformer.py:179-183), which vitcap_attn_dense_fwd forms and consumes inside its key loop.
+ *   qkv      bf16 [B * S][2304], the layout vitcap_attn_dense_fwd reads.
+ *   out      fp32 [B][H'][S][S], H' = 12 with per_head and 1 without (the mean over the heads); row q, column k holds
+ *            softmax_k(q . k * scale).  Query rows 0..q_rows-1 of every image are computed against all S keys; rows q_rows..S-1 are
+ *            written as exact zeros.
+ *   softmax  scores from the same bf16 q / k by MFMA, log2 domain, m = ceil(max * c), p = exp2(s * c - m) in fp32, the row is
+ *            p / sum(p); head mean: the 12 heads are added in the order 0..11 by one lane and multiplied by 1/12 -- no atomics, the
+ *            same bits on every run.
+ * One workgroup per (16-query tile, image).  1 <= S <= 640, 1 <= q_rows <= S, 1 <= B <= 65535, per_head 0 or 1, pointers non-null and
+ * aligned (qkv 16 bytes, out 4); anything else is refused (VITCAP_EINVAL, the argument named) with `out` untouched. */
+int vitcap_attn_self_maps(const void* qkv, float* out, int B, int S, int q_rows, float scale, int per_head, void* stream);
+/* One step of attention rollout (Abnar & Zuidema 2020) on a few row vectors: the row-vector form of A~ = r I + (1 - r) A, where A is
+ * a block's head-mean `attn` (vision_transformer.py:179-183) and r I stands for the block's residual connection (x + attn(norm1(x)),
+ * vision_transformer.py:241-247).
+ *   v_in, v_out  fp32 [n_img][rows][S];  A fp32 [n_img][S][S]
+ *   v_out[b][r][k] = residual * v_in[b][r][k] + (1 - residual) * sum_j v_in[b][r][j] * A[b][j][k]
+ * with j ascending, fp32 multiply-adds in plain vector code: the same bits on every run.  residual = 1 returns v_in bit for bit.
+ * 1 <= rows <= 64, 1 <= S <= 640, 1 <= n_img <= 65535, residual in [0, 1], pointers non-null, 4-byte aligned, v_out not overlapping
+ * v_in; anything else is refused (VITCAP_EINVAL, the argument named) with v_out untouched. */
+int vitcap_rollout_step(const float* v_in, const float* A, float* v_out, int n_img, int rows, int S, float residual, void* stream);
 
 /* small data movers used by the engine and exposed for tests */
 int vitcap_assemble_visual(const float* hidden, const float* tag_hidden, float* vis_f32, void* vis_bf16,
@@ -796,6 +817,23 @@ int vitcap_engine_encode_patches(vitcap_engine* e, const void* image, int image_
                                  void* workspace, size_t workspace_bytes, const uint32_t* patch_mask, void* stream);
 int vitcap_engine_prefill_patches(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,
                                   const uint32_t* patch_mask, void* stream);
+/* vitcap_engine_encode that also writes out the encoder's attention: after the attention launch of every selected ViT block,
+ * vitcap_attn_self_maps runs on that block's qkv buffer (the reference's `attn`, vision_transformer.py:179-183, of the 12 blocks and
+ * the 4 tag blocks TIMMVitSplitEncoder.forward walks, modeling_bert.py:458-478), before the next block overwrites it.
+ *   block_mask  bits 0..11 = encoder.blocks[0..11], bits 12..15 = encoder.tag_blocks[0..3]
+ *   maps        device fp32 [n_sel][B][H'][577][577], the selected blocks in ascending bit order; H' = 12 with per_head, else 1
+ *               (the head mean).  maps_bytes: the size of that buffer.
+ * The last tag block is computed for its CLS query only (the pooler reads tag_hidden[:, 0], modeling_bert.py:1424): its slot holds
+ * row 0 and zeros below, also when the engine runs that block in full.  The call runs the launches of vitcap_engine_encode as ONE
+ * part on `stream` with the tag branch serial, whatever vitcap_gen_opts.encode_parts says, and leaves the workspace that
+ * vitcap_engine_encode leaves, bit for bit.  Where that call cuts the batch into parts it runs their prefill too, and so does this
+ * one; there every buffer a later call reads is still vitcap_engine_encode's bit for bit, and the one difference is dead scratch: the
+ * compact cls rows of the last tag block's MLP, which each part keeps at its own base.
+ * VITCAP_EINVAL, naming the cause in vitcap_last_error(), before anything is enqueued: a zero block_mask or bits above 15, per_head
+ * outside {0, 1}, null or misaligned maps, maps_bytes too small, use_graph != 0, tag_visible > 0. */
+int vitcap_engine_encode_maps(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                              void* workspace, size_t workspace_bytes, uint32_t block_mask, int per_head, float* maps,
+                              size_t maps_bytes, void* stream);
 /* vitcap_engine_decode / vitcap_engine_generate with tokens handed in by the caller: caption prefixes (score_forced = 0) and the
  * score of given captions (score_forced = 1) under the same [MASK]-probe procedure generate uses.  The rule is that of
  * vitcap_greedy_step_forced / vitcap_sample_step_forced, applied at every step.

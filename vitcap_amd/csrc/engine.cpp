@@ -213,6 +213,13 @@ struct Enq {
   // patch removal (vitcap_engine_encode_patches / _prefill_patches): the caller's device array [B][MASK_WORDS] in cache order, row 0 =
   // the first image THIS context covers; every dense attention launch of the encoder (bit0 = 1) and of the prefill (bit0 = 0) reads it
   const uint32_t* patch_mask = nullptr;
+  // encoder attention written out (vitcap_engine_encode_maps): the selection and the caller's device array; null = a plain call
+  struct BlockMaps {
+    float* out;              // [n_sel][B][H'][NV][NV], the selected blocks in ascending bit order
+    uint32_t mask;           // bits 0..11 blocks[0..11], 12..15 tag_blocks[0..3]
+    int per_head;
+  };
+  const BlockMaps* block_maps = nullptr;
 
   Enq(vitcap_engine* e, int B, const vitcap_gen_opts& o, const Layout& lo, char* ws, void* s, Phase ph)
       : e(e), w(e->w), o(o), lo(lo), ws(ws), B(B), s(s),
@@ -330,6 +337,17 @@ struct Enq {
     return q_rows == S ? vitcap_attn_dense_fwd(qkv, out, B, S, 0.125f, s) : vitcap_attn_dense_fwd_rows(qkv, out, B, S, q_rows, 0.125f, s);
   }
 
+  // vitcap_engine_encode_maps: the block's attention probabilities from the qkv buffer its attention launch has just read, into the
+  // block's slot of the caller's array (nothing if the block is not selected).  q_rows < NV: the last tag block, CLS query only.
+  int emit_block_maps(const vitcap_vit_block_w& bw, const void* qkv, int q_rows) const {
+    const bool tag = &bw >= w.tag_blocks && &bw < w.tag_blocks + 4;
+    const int bit = tag ? 12 + (int)(&bw - w.tag_blocks) : (int)(&bw - w.blocks);
+    if (!(block_maps->mask >> bit & 1)) return VITCAP_OK;
+    const int slot = __builtin_popcount(block_maps->mask & ((1u << bit) - 1));
+    float* out = block_maps->out + (size_t)slot * B * (block_maps->per_head ? 12 : 1) * NV * NV;
+    return vitcap_attn_self_maps(qkv, out, B, NV, q_rows, 0.125f, block_maps->per_head, s);
+  }
+
   int vit_block(const vitcap_vit_block_w& bw, const float* x_in, float* x, void* h, void* qkv, void* mlp, bool have_ln1 = false,
                 const vitcap_vit_block_w* next = nullptr) const {
     const int M = B * NV;
@@ -339,6 +357,7 @@ struct Enq {
     CK(gemm(h, D, bw.qkv_w, bw.qkv_b, nullptr, 0, qkv, 3 * D, M, 3 * D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));
     zz();
     CK(attn_dense(qkv, h, NV, NV, 1));
+    if (block_maps) CK(emit_block_maps(bw, qkv, &bw == &w.tag_blocks[3] ? 1 : NV));      // the last tag block run in full: its CLS row only, as cls_only
     zz();
     // proj reads h (the attention output) as A and its norm2 writes h: a row block's A rows are read by its own three tiles only
     CK(gemm_ln(h, D, bw.proj_w, bw.proj_b, x_in, x, M, D, bw.n2_g, bw.n2_b, 1e-6f, h, nullptr));      // GEMM, LayerNorm: two flips = none
@@ -364,6 +383,7 @@ struct Enq {
             VITCAP_ACT_NONE, VITCAP_OUT_BF16));                                         // K | V of every row
     CK(gemm(h, RS, bw.qkv_w, bw.qkv_b, nullptr, 0, qkv, NV * 3 * D, B, D, D, VITCAP_ACT_NONE, VITCAP_OUT_BF16));   // Q of the CLS rows
     CK(attn_dense(qkv, h, NV, 1, 1));
+    if (block_maps) CK(emit_block_maps(bw, qkv, 1));
     CK(gemm(h, RS, bw.proj_w, bw.proj_b, x, RS, x, RS, B, D, D, VITCAP_ACT_NONE, VITCAP_OUT_F32));
     CK(vitcap_layernorm_fwd(x, RS, bw.n2_g, bw.n2_b, 1e-6f, cls_h, nullptr, B, D, s));
     CK(gemm(cls_h, D, bw.fc1_w, bw.fc1_b, nullptr, 0, mlp, 4 * D, B, 4 * D, D, VITCAP_ACT_GELU_ERF, VITCAP_OUT_BF16));
@@ -799,7 +819,7 @@ struct Enq {
  private:
   Enq(const Enq& q, const Layout& lv, int Bv, void* sv, int first_image)
       : e(q.e), w(q.w), o(q.o), lo(lv), ws(q.ws), B(Bv), s(sv), live(q.live), owner(false), forced(q.forced), vis_mask(q.vis_mask),
-        patch_mask(q.patch_mask ? q.patch_mask + (size_t)first_image * MASK_WORDS : nullptr) {}
+        patch_mask(q.patch_mask ? q.patch_mask + (size_t)first_image * MASK_WORDS : nullptr) {}      // block_maps stays null: vitcap_engine_encode_maps runs no views (its slots are laid out for the whole batch)
 };
 
 vitcap_gen_opts opts_or_default(const vitcap_gen_opts* opts) { return opts ? *opts : default_opts(); }
@@ -1042,6 +1062,37 @@ extern "C" int vitcap_engine_prefill_patches(vitcap_engine* e, int B, const vitc
   Enq q(e, B, o, lo, (char*)workspace, s, Enq::ENCODE);
   q.patch_mask = patch_mask;
   return q.prefill();
+}
+
+// Encoder attention written out: vitcap_engine_encode as one part on the caller's stream with the tag branch serial, plus one
+// vitcap_attn_self_maps launch behind the attention of every selected block (Enq::emit_block_maps).
+extern "C" int vitcap_engine_encode_maps(vitcap_engine* e, const void* image, int image_is_bf16, int B, const vitcap_gen_opts* opts,
+                                         void* workspace, size_t workspace_bytes, uint32_t block_mask, int per_head, float* maps,
+                                         size_t maps_bytes, void* s) {
+  const vitcap_gen_opts o = opts_or_default(opts);
+  const char* who = "encode_maps";
+  if (block_mask == 0 || (block_mask >> 16) != 0) { vitcap_set_error("%s: block_mask must select at least one of bits 0..15 (got 0x%x)", who, block_mask); return VITCAP_EINVAL; }
+  if (per_head != 0 && per_head != 1) { vitcap_set_error("%s: per_head must be 0 or 1 (got %d)", who, per_head); return VITCAP_EINVAL; }
+  if (!maps) { vitcap_set_error("%s: maps is null", who); return VITCAP_EINVAL; }
+  if (((uintptr_t)maps & 3) != 0) { vitcap_set_error("%s: maps is not 4-byte aligned", who); return VITCAP_EINVAL; }
+  if (o.use_graph != 0) { vitcap_set_error("%s: use_graph = 1 is not supported (the maps are written by this call's own launches, not by a captured loop)", who); return VITCAP_EINVAL; }
+  if (o.tag_visible > 0) { vitcap_set_error("%s: tag_visible > 0 is not supported (the rollout has no path for the tag rows)", who); return VITCAP_EINVAL; }
+  if (B > 0) {
+    const size_t need = (size_t)__builtin_popcount(block_mask) * B * (per_head ? 12 : 1) * NV * NV * sizeof(float);
+    if (maps_bytes < need) { vitcap_set_error("%s: maps_bytes %zu < required %zu bytes", who, maps_bytes, need); return VITCAP_EINVAL; }
+  }
+  Layout lo;
+  CK(enter(e, B, o, workspace, workspace_bytes, lo));
+  if (!image) { vitcap_set_error("%s: null image", who); return VITCAP_EINVAL; }
+  std::lock_guard<std::mutex> lk(e->mu);
+  Enq q(e, B, o, lo, (char*)workspace, s, Enq::ENCODE);
+  const Enq::BlockMaps bm{maps, block_mask, per_head};
+  q.block_maps = &bm;
+  if (e->timing) e->timing_this_step = false;      // timing samples whole steps of the plain calls
+  CK(q.encode_part(image, image_is_bf16, false));
+  // where vitcap_engine_encode cuts the batch into parts it runs their prefill too (vitcap_engine_prefill then has nothing to do)
+  if (q.encode_parts() >= 2) CK(q.prefill_part());
+  return VITCAP_OK;
 }
 
 extern "C" int vitcap_engine_decode(vitcap_engine* e, int B, const vitcap_gen_opts* opts, void* workspace, size_t workspace_bytes,

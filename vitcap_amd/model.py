@@ -1212,6 +1212,169 @@ class ImageCaptioning(nn.Module):
         topk, prob = self.last_tags[1], self.last_tag_probs[0]
         return (ids, lp, topk, prob) + self.caption_crops(image, regions, slot=slot, **over)
 
+    # ---- encoder attention rollout: the ViT blocks' attention written out (vitcap_engine_encode_maps) and composed over the model's
+    # graph (vitcap_amd.rollout.rollout_rows), for the tag head's CLS and for every word of a caption
+    def refuse_rollout(self, who, over=None):
+        """The encoder's attention is written out by a plain greedy / one-pass pass without visible tags and without a hipGraph:
+        anything else is refused by the option's name, before the GPU is touched."""
+        te = dict(self.test_extra_input)
+        te.update(over or {})
+        if te.get('use_cbs', False):
+            raise NotImplementedError('%s: the encoder rollout is not built for use_cbs' % who)
+        if int(te.get('num_beams', 1) or 1) > 1:
+            raise NotImplementedError('%s: the encoder rollout is not built for num_beams > 1 (got %s)' % (who, te['num_beams']))
+        if int(te.get('tag_visible', 0) or 0) > 0:
+            raise NotImplementedError('%s: the encoder rollout is not built for tag_visible > 0 (got %s): it has no path for the tag rows'
+                                      % (who, te['tag_visible']))
+        if te.get('do_sample', False):
+            raise NotImplementedError('%s: the encoder rollout explains greedy or given captions; do_sample is not built for it' % who)
+        if te.get('use_graph', False):
+            raise NotImplementedError('%s: the encoder rollout is not built for use_graph: the maps are written by the call\'s own '
+                                      'launches' % who)
+
+    def _rollout_options(self, who, slot, over):
+        """The refusals, then -> the validated options of a greedy pass without a hipGraph."""
+        self.refuse_rollout(who, over)
+        self._refuse_patch_slot(who, slot)
+        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
+        return self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+
+    def _encode_maps(self, image, o, slot, mask, per_head):
+        """vitcap_engine_encode_maps + vitcap_engine_prefill of `image` on `slot` -> (maps (n_sel, B, [12,] 577, 577), workspace,
+        bytes).  The slot is left encoded, as by run()."""
+        dev, B = self._check_image(image), image.shape[0]
+        n_sel = bin(mask).count('1')
+        maps = torch.empty((n_sel, B) + ((12,) if per_head else ()) + (577, 577), dtype=torch.float32, device=dev)
+        ws, need = self._workspace(B, dev, slot, o)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        wp = C.c_void_p(ws.data_ptr())
+        check(lib.vitcap_engine_encode_maps(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
+                                            wp, need, mask, int(bool(per_head)), C.c_void_p(maps.data_ptr()),
+                                            maps.numel() * 4, s), 'engine_encode_maps')
+        check(lib.vitcap_engine_prefill(self._engine, B, C.byref(o), wp, need, s), 'engine_prefill')
+        self._encoded[slot] = (o, B)
+        self._last = (slot, o, B)
+        return maps, ws, need
+
+    @staticmethod
+    def _image_chunks(image, n_sel, per_head):
+        from . import rollout as R
+        n = R.images_per_call(n_sel, per_head, R.MAX_CALL_BYTES)
+        return [image[i:i + n] for i in range(0, image.shape[0], n)]
+
+    def encoder_attention(self, image, blocks=None, per_head=False, slot=0, **over):
+        """The attention matrices of the ViT blocks: the reference's `attn` of Attention.forward after its softmax
+        (vision_transformer.py:179-183), written out by the encoder pass itself (vitcap_engine_encode_maps).  blocks: None (all 16)
+        or ints 0..15 / names 'blocks.3', 'tag_blocks.0' (12..15 are the tag blocks).
+        -> (maps fp32 (n_sel, B, 577, 577), the mean over the 12 heads, or with per_head (n_sel, B, 12, 577, 577); the names of the
+        selected blocks, ascending).  Rows and columns are the encoder's tokens [cls | 576 patches]; the last tag block holds its cls
+        row only (the pooler reads nothing else), zeros below.  The images are cut into chunks so that one engine call's buffer stays
+        at or below 1 GiB (head mean, all blocks: 21.3 MB per image; per head: 256 MB).  There is no *_encoded form: the matrices are
+        not kept on the workspace."""
+        from . import rollout as R
+        mask, names = R.parse_blocks(blocks)
+        o = self._rollout_options('encoder_attention', slot, over)
+        parts = [self._encode_maps(img, o, slot, mask, per_head)[0] for img in self._image_chunks(image, len(names), per_head)]
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, 1)), names
+
+    def tag_rollout(self, image, residual=0.5, slot=0, **over):
+        """Where the concept tagger looked: attention rollout (vitcap_amd.rollout) of the token the tag head's pooler reads --
+        tag_hidden[:, 0], modeling_bert.py:1424 -- back through tag blocks 3..0 and blocks 7..0 to the image patches.  Rollout is a
+        model of information flow through attention alone (head-mean attention mixed with `residual` of the identity per block); the
+        MLPs and value vectors play no part in it.
+        -> (patches (B, 24, 24), cls_mass (B,), tag_ids (B, 50), tag_prob (B, 50), tag_len (B,)): patches.sum + cls_mass = 1 per image;
+        the tags are those of the same encoder pass.  No *_encoded form: the matrices are not kept on the workspace."""
+        from . import rollout as R
+        r = R.check_residual(residual)
+        o = self._rollout_options('tag_rollout', slot, over)
+        out = []
+        for img in self._image_chunks(image, R.N_BLOCKS, False):
+            A, ws, _ = self._encode_maps(img, o, slot, R.ALL_BLOCKS, False)
+            _, topk, prob, tlen = self._tags_of_slot(o, img.shape[0], ws, slot)
+            w = torch.zeros((img.shape[0], 1, R.N_VIS), dtype=torch.float32, device=A.device)
+            w[..., 0] = 1.0
+            grid, cls = R.patch_grid(R.rollout_rows(A, w, r)[:, 0])
+            out.append((grid, cls, topk, prob, tlen))
+        return tuple(torch.cat(x, 0) for x in zip(*out))
+
+    def _rollout_chunk(self, img, o, cap, lt, K, lmask, nl, r, slot, want_tag=False):
+        """One chunk of rollout_maps: encoder with maps, prefill, the maps form of the one-pass scorer on the same workspace, the
+        rollout of every probe row.  cap None: the chunk's own greedy captions (K = 1), decoded first.  want_tag: the tag head's map
+        (tag_rollout's, w = e_0) from the same matrices.
+        -> (lp, tok_lp, patches, cls_mass, text_mass[, ids, caption logprobs][, tag patches (B, 24, 24), tag cls_mass (B,)])."""
+        from . import rollout as R
+        B, Lm = img.shape[0], o.max_length
+        A, ws, need = self._encode_maps(img, o, slot, R.ALL_BLOCKS, False)
+        own = ()
+        if cap is None:
+            ids, glp = self._out_buffers(B, o, A.device)
+            lt = torch.empty((B,), dtype=torch.int64, device=A.device)
+            check(lib.vitcap_engine_decode(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, C.c_void_p(ids.data_ptr()),
+                                           C.c_void_p(glp.data_ptr()), C.c_void_p(lt.data_ptr()),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'engine_decode')
+            cap, own = ids.view(B, Lm), (ids, glp)
+        lp, tok_lp, _, maps = self._score_one_pass(None, B, o, cap, lt, K, slot, A.device, False, maps=(False, lmask))
+        m = maps.view(B, K, Lm, 4, maps.shape[-1]).sum(3) * (1.0 / nl)      # unselected layers are zeros; NOT renormalised
+        text = m[..., R.N_VIS:].sum(-1)
+        v = torch.stack([R.rollout_rows(A, m[:, k, :, :R.N_VIS].contiguous(), r) for k in range(K)], 1)      # (B, K, L, 577)
+        grid, cls = R.patch_grid(v.view(B * K, Lm, R.N_ENC))
+        if want_tag:
+            w = torch.zeros((B, 1, R.N_VIS), dtype=torch.float32, device=A.device)
+            w[..., 0] = 1.0
+            own = own + R.patch_grid(R.rollout_rows(A, w, r)[:, 0])
+        return (lp, tok_lp, grid, cls, text.reshape(B * K, Lm)) + own
+
+    def rollout_maps(self, image, caption_ids, seqs_per_image=1, layers=(0, 1, 2, 3), residual=0.5, slot=0, last_tok=None, **over):
+        """Where each word of GIVEN captions looked, on the image's patches: the head-mean probe row of attention_maps() over the 578
+        visual tokens, averaged over the selected decoder layers and NOT renormalised, carried back through the encoder by attention
+        rollout (vitcap_amd.rollout.rollout_rows: the caption's visual tokens through blocks 11..8, the tag-branch cls through the tag
+        blocks, both through blocks 7..0).  Inputs and refusals as score(one_pass=True); one encoder pass per chunk of images.
+        What the maps are: a model of information flow through attention alone.  The decoder's own visual-to-visual mixing (its 4
+        layers also update the visual rows) is not rolled; with layers=(0,) the visual keys are the raw encoder outputs and nothing
+        is left out.
+        -> (logprobs (rows,), token_logprobs (rows, L), patches (rows, L, 24, 24), cls_mass (rows, L), text_mass (rows, L)), the
+        scores those of score(one_pass=True); patches.sum + cls_mass + text_mass = 1 at every live position, dead positions are 0.
+        No *_encoded form: the matrices are not kept on the workspace."""
+        from . import rollout as R
+        r, K, lmask = R.check_residual(residual), int(seqs_per_image), self._layer_mask(layers)
+        nl = bin(lmask).count('1')
+        self.refuse_rollout('rollout_maps', over)
+        self._refuse_patch_slot('rollout_maps', slot)
+        over.pop('use_graph', None)
+        B = image.shape[0]
+        o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
+        o.use_graph = 0
+        out, i = [], 0
+        for img in self._image_chunks(image, R.N_BLOCKS, False):
+            n = img.shape[0]
+            out.append(self._rollout_chunk(img, o, cap[i * K:(i + n) * K], None if lt is None else lt[i * K:(i + n) * K], K, lmask, nl,
+                                           r, slot))
+            i += n
+        return tuple(torch.cat(x, 0) for x in zip(*out))
+
+    def caption_with_rollout(self, image, layers=(0, 1, 2, 3), residual=0.5, slot=0, want_tag=False, **over):
+        """Greedy captions and where each of their words looked on the image's patches: per chunk of images the encoder with its
+        attention written out, the prefill, the greedy loop, then rollout_maps' pass on the loop's own output (the token chosen at the
+        last position handed over as last_tok).  -> (ids (B, 1, L), logprobs (B, 1), patches (B, L, 24, 24), cls_mass (B, L),
+        text_mass (B, L)); the maps are rollout_maps' (see there for what they are).  want_tag: tag_rollout's map of the same encoder
+        pass behind them, (B, 24, 24) and its cls_mass (B,)."""
+        from . import rollout as R
+        r, lmask = R.check_residual(residual), self._layer_mask(layers)
+        o = self._rollout_options('caption_with_rollout', slot, over)
+        nl, chunks = bin(lmask).count('1'), self._image_chunks(image, R.N_BLOCKS, False)
+        if len(chunks) == 1:
+            _, _, grid, cls, text, ids, lp, *tag = self._rollout_chunk(image, o, None, None, 1, lmask, nl, r, slot, want_tag)
+            return (ids, lp, grid, cls, text) + tuple(tag)
+        # more images than one engine call's maps buffer holds: the captions are those of ONE generate() over the whole batch (so
+        # that they do not depend on the chunking), then every chunk is encoded again with its attention written out
+        ids, lp, last = self.run(image, o, slot=slot, want_last=True)
+        out, i = [], 0
+        for img in chunks:
+            n = img.shape[0]
+            out.append(self._rollout_chunk(img, o, ids[i:i + n, 0], last[i:i + n], 1, lmask, nl, r, slot, want_tag)[2:])
+            i += n
+        return (ids, lp) + tuple(torch.cat(x, 0) for x in zip(*out))
+
     def generate_cbs(self, image, fsm, num_constraints, num_beams=1, min_constraints_to_satisfy=2, slot=0, **over):
         """Constrained beam search: ViTCAP.generate(use_cbs=True, fsm=fsm, num_constraints=..., min_constraints_to_satisfy=...)
         (modeling_bert.py:1035-1057 -> utils_cbs.py:26-443) -> (ids (B, 1, T), logprobs (B, 1)).  Like the reference's output the

@@ -293,6 +293,35 @@ def attn_probe_maps(qkv_text, vis_qkv, caption_ids, n_images, caps_per_image, S_
     return out
 
 
+def attn_self_maps(qkv, B, S, q_rows=None, per_head=False, out=None, scale=0.125):
+    """Self-attention probabilities of one ViT block (vitcap_attn_self_maps): qkv bf16 (B * S, 2304) as attn_dense takes it.
+    -> out fp32 (B, 12, S, S) with per_head, else the head mean (B, S, S); query rows q_rows.. are exact zeros."""
+    _dev_bf16(qkv)
+    q_rows = S if q_rows is None else int(q_rows)
+    shape = (B, 12, S, S) if per_head else (B, S, S)
+    if out is None:
+        out = torch.empty(shape, device=qkv.device, dtype=torch.float32)
+    _dev_f32(out)
+    assert tuple(out.shape) == shape and tuple(qkv.shape) == (B * S, 2304)
+    check(lib.vitcap_attn_self_maps(_p(qkv), _p(out), B, S, q_rows, scale, int(bool(per_head)), _stream()), 'attn_self_maps')
+    return out
+
+
+def rollout_step(v_in, A, residual=0.5, out=None):
+    """One attention-rollout step on row vectors (vitcap_rollout_step): v_in fp32 (n_img, rows, S), A fp32 (n_img, S, S)
+    -> residual * v_in + (1 - residual) * v_in @ A, fp32, summed in ascending order."""
+    _dev_f32(v_in)
+    _dev_f32(A)
+    n_img, rows, S = v_in.shape
+    assert tuple(A.shape) == (n_img, S, S)
+    if out is None:
+        out = torch.empty_like(v_in)
+    _dev_f32(out)
+    assert tuple(out.shape) == tuple(v_in.shape)
+    check(lib.vitcap_rollout_step(_p(v_in), _p(A), _p(out), n_img, rows, S, float(residual), _stream()), 'rollout_step')
+    return out
+
+
 def score_rows(logits, caption_ids, st=None, rows0=0, last_tok=None, V=L.VOCAB, eos=102, eos_extra=(), pad=0):
     """vitcap_score_rows on the probe rows [rows0, rows0 + len(logits)) of caption_ids (n_caps, max_len).  st: the dict of outputs a
     previous chunk's call returned (token_logprobs, ids, last_tok, sum_lp, cnt, logprob); a new one is made when None."""

@@ -257,6 +257,26 @@ class _PredictRun(object):
                 yield key, json.dumps({'tokens': [vocab[i] for i in toks[1:n + 1]], 'layer': 3, 'shape': [n, 24, 24],
                                        'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
 
+    def rollout_rows(self, batches, dev, pred_rows):
+        """cfg.rollout: yields the rows of the rollout TSV, one per image: the tag head's rollout map, then one map per live word of
+        the predicted caption (vitcap_amd.rollout.to_rows) -- ImageCaptioning.caption_with_rollout with the tag map of the same
+        encoder pass (want_tag)."""
+        from .rollout import to_rows
+        model, L = self.model, int(self.pipe.cfg.max_gen_length)
+        vocab = self.pipe.tokenizer.ids_to_tokens
+        eos = set(int(e) for e in (model.test_extra_input.get('eos_token_ids') or [102]))
+
+        def with_rollout(img):
+            ids, lp, grid, _, _, tag, _ = model.caption_with_rollout(img, want_tag=True, gemm_mode=1)
+            return ids, lp, grid, tag
+        for batch, ids_h, lp, (grid, tag) in self.analysed(batches, dev, pred_rows, 'rollout', 'rollout maps', with_rollout):
+            grid_h, tag_h = grid.cpu().numpy(), tag.cpu().numpy()
+            for b, key in enumerate(batch['key']):
+                toks = ids_h[b, 0].tolist()
+                ends = [t for t in range(1, L) if toks[t] in eos]
+                n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
+                yield key, json.dumps(to_rows([vocab[i] for i in toks[1:n + 1]], tag_h[b], grid_h[b, 1:n + 1]))
+
     def alternative_rows(self, batches, dev, pred_rows, k):
         """cfg.alternatives = k: yields the rows of the alternatives TSV, one per image: the key and a JSON list with one record per
         live position of the predicted caption -- word, log-prob, rank, entropy and the k (word, log-prob) alternatives, all of the
@@ -717,6 +737,18 @@ class CaptionUniPipeline(object):
                 self.merge_rank_files(predict_result_file)
                 self.merge_rank_files(attn_file)
             return predict_result_file
+        if self.cfg.rollout:
+            # a second TSV next to the predictions, one row per image: the tag head's rollout map and one per word of the caption
+            ro_file = self.get_rollout_file(predict_result_file)
+            ro_sub = ro_file if self.world == 1 else '{}_{}_{}.tsv'.format(ro_file, self.rank, self.world)
+            pred_rows = []
+            tsv_writer(run.counted(run.rollout_rows(batches, dev, pred_rows)), ro_sub)
+            tsv_writer(iter(pred_rows), sub)
+            run.report()
+            if self.world > 1:
+                self.merge_rank_files(predict_result_file)
+                self.merge_rank_files(ro_file)
+            return predict_result_file
         if self.cfg.alternatives:
             # a second TSV next to the predictions, one row per image: per word of the caption its alternatives, rank and entropy
             alt_file = self.get_alternatives_file(predict_result_file)
@@ -801,6 +833,32 @@ class CaptionUniPipeline(object):
         """<predict file minus .tsv>.crops.tsv: written by predict when the config sets `crops: g`."""
         assert predict_result_file.endswith('.tsv')
         return predict_result_file[:-len('.tsv')] + '.crops.tsv'
+
+    @staticmethod
+    def get_rollout_file(predict_result_file):
+        """<predict file minus .tsv>.rollout.tsv: written by predict when the config sets `rollout: true`."""
+        assert predict_result_file.endswith('.tsv')
+        return predict_result_file[:-len('.tsv')] + '.rollout.tsv'
+
+    def check_rollout(self):
+        """`rollout: true` is refused by name with what the encoder rollout is not built for, before a model is built."""
+        cfg = self.cfg
+        if not cfg.rollout:
+            return
+        if cfg.num_beams not in (None, 1):
+            raise NotImplementedError('rollout: the maps are those of greedy captions; beam search (num_beams=%r) is not built for them'
+                                      % (cfg.num_beams,))
+        if cfg.use_cbs:
+            raise NotImplementedError('rollout: the maps are those of greedy captions; CBS (use_cbs=%r) is not built for them' % (cfg.use_cbs,))
+        if cfg.caption_prefix:
+            raise NotImplementedError('rollout: caption_prefix=%r is not built together with the rollout maps (they are those of free '
+                                      'greedy captions)' % (cfg.caption_prefix,))
+        if int(cfg.tag_visible or 0) > 0:
+            raise NotImplementedError('rollout: visible tag slots (tag_visible=%r) are not built for the rollout maps' % (cfg.tag_visible,))
+        for other in ('attention_maps', 'alternatives', 'occlusion', 'regions', 'crops'):
+            if getattr(cfg, other):
+                raise NotImplementedError('rollout together with %s: one explaining pass per run is built; run the two configurations '
+                                          'one after the other' % other)
 
     def check_crops(self):
         """`crops: g` is refused by name with what patch removal is not built for, before a model is built."""
@@ -926,6 +984,7 @@ class CaptionUniPipeline(object):
         self.check_occlusion()
         self.check_regions()
         self.check_crops()
+        self.check_rollout()
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -946,6 +1005,8 @@ class CaptionUniPipeline(object):
         if have and self.cfg.regions and not op.isfile(self.get_regions_file(predict_result_file)):
             have = False
         if have and self.cfg.crops and not op.isfile(self.get_crops_file(predict_result_file)):
+            have = False
+        if have and self.cfg.rollout and not op.isfile(self.get_rollout_file(predict_result_file)):
             have = False
         if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
