@@ -102,6 +102,46 @@ class _PatchEncoded(tuple):
     words = None
 
 
+def _p(t):
+    """Tensor -> the pointer argument of an engine call; None stays None (an output the call does not want)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(s=None):
+    """The HIP stream argument of an engine call: `s`, or the current stream."""
+    return C.c_void_p((torch.cuda.current_stream() if s is None else s).cuda_stream)
+
+
+# How each generate() option that some call is not built for shows in the merged options (test_extra_input + overrides).
+_OPTION_SET = {'num_beams': lambda v: int(v or 1) > 1, 'use_cbs': bool, 'tag_visible': lambda v: int(v or 0) > 0, 'do_sample': bool,
+               'use_graph': bool, 'repetition_penalty': lambda v: float(v or 1) != 1.0}
+
+# Family of calls -> (why, the options it refuses, in the order they are looked at).  The rows differ for historical reasons (the
+# caption_with_* calls let tag_visible through to their greedy pass, only the one-pass scorer looks at repetition_penalty, ...):
+# tests/test_refusal_matrix_cpu.py pins them as they are.
+_REFUSED = {
+    'forced': ('forced tokens under beam search are not built: the greedy / sampling loop takes them, not', ('num_beams', 'use_cbs')),
+    'visible': ('a visibility mask is not built for', ('num_beams', 'use_cbs', 'tag_visible')),
+    'visible_beam': ('a visibility mask under beam search is not built for', ('use_cbs', 'tag_visible', 'do_sample', 'use_graph')),
+    'one_pass': ('a caption is scored in one pass, not searched or drawn: not built for',
+                 ('num_beams', 'use_cbs', 'repetition_penalty', 'tag_visible', 'do_sample')),
+    'greedy': ('it runs greedy captions only: not built for', ('num_beams', 'use_cbs', 'do_sample')),
+    'regions': ('region captions are greedy, under a visibility mask: not built for', ('do_sample', 'num_beams', 'use_cbs', 'tag_visible')),
+    'patches': ('patch removal (greedy loop and one-pass scorer, this call\'s own mask) is not built for',
+                ('use_cbs', 'num_beams', 'tag_visible', 'use_graph', 'do_sample')),
+    'rollout': ('the encoder rollout (a plain greedy / one-pass pass, the call\'s own launches) is not built for',
+                ('use_cbs', 'num_beams', 'tag_visible', 'do_sample', 'use_graph')),
+}
+
+
+def _refuse_options(who, family, te):
+    """Raises NotImplementedError naming `who`, the option and its value for the first option of `te` the family is not built for."""
+    why, names = _REFUSED[family]
+    for name in names:
+        if _OPTION_SET[name](te.get(name)):
+            raise NotImplementedError('%s: %s %s (got %s=%r)' % (who, why, name, name, te[name]))
+
+
 class ImageCaptioning(nn.Module):
     """ViT-B/16-384 + tag head + 4-layer BERT caption decoder, greedy decode on MI355X."""
 
@@ -156,7 +196,7 @@ class ImageCaptioning(nn.Module):
             dst = w
             for step in f.path[:-1]:
                 dst = dst[step] if isinstance(step, int) else getattr(dst, step)
-            setattr(dst, f.path[-1], C.c_void_p(t.data_ptr()))
+            setattr(dst, f.path[-1], _p(t))
         if self._engine is None:
             h = C.c_void_p()
             check(lib.vitcap_engine_create(C.byref(h)), 'engine_create')
@@ -382,21 +422,46 @@ class ImageCaptioning(nn.Module):
     @staticmethod
     def refuse_forced_search(num_beams, use_cbs):
         """Forced tokens (a caption prefix, a caption to score) exist for the greedy / sampling loop only."""
-        if int(num_beams or 1) > 1 or use_cbs:
-            raise NotImplementedError('prefix_ids / forced tokens need num_beams == 1 and use_cbs off: forced tokens under beam search '
-                                      'are not built (got num_beams=%s, use_cbs=%s)' % (num_beams, bool(use_cbs)))
+        _refuse_options('prefix_ids / forced tokens', 'forced', dict(num_beams=num_beams, use_cbs=use_cbs))
 
-    def refuse_visible(self, who, over=None):
-        """A visibility mask (`visible` / regions) exists for the greedy / sampling loop without visible tags: anything else is
-        refused by the option's name, before the GPU is touched."""
+    def _refuse(self, who, family, over=None):
+        """What a family of calls (_REFUSED) is not built for, looked up in test_extra_input + `over` and refused by the option's
+        name, before the GPU is touched.  -> the merged options."""
         te = dict(self.test_extra_input)
         te.update(over or {})
-        if int(te.get('num_beams', 1) or 1) > 1:
-            raise NotImplementedError('%s: a visibility mask is not built for num_beams > 1 (got %s)' % (who, te['num_beams']))
-        if te.get('use_cbs', False):
-            raise NotImplementedError('%s: a visibility mask is not built for use_cbs' % who)
-        if int(te.get('tag_visible', 0) or 0) > 0:
-            raise NotImplementedError('%s: a visibility mask is not built for tag_visible > 0 (got %s)' % (who, te['tag_visible']))
+        _refuse_options(who, family, te)
+        return te
+
+    def refuse_visible(self, who, over=None):
+        """A visibility mask (`visible` / regions) exists for the greedy / sampling loop without visible tags."""
+        self._refuse(who, 'visible', over)
+
+    def _greedy_options(self, over, no_graph=False, drop=(), **fixed):
+        """The validated options of a call that decides the search itself: greedy unless `fixed` says otherwise, without a hipGraph
+        when asked; `over` gives the rest, whatever it says about the fixed keys (and those of `drop`) is left out."""
+        fixed = dict(dict(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1), **fixed)
+        if no_graph:
+            fixed['use_graph'] = False
+        return self.gen_options(**fixed, **{k: v for k, v in over.items() if k not in fixed and k not in drop})
+
+    def _head(self, image, B, opts, ws, need):
+        """The leading arguments every staged (image None) or whole engine call shares."""
+        return (self._engine,) + (() if image is None else (_p(image), int(image.dtype == torch.bfloat16))) + (B, C.byref(opts), _p(ws), need)
+
+    def _encode_prefill(self, image, opts, ws, need, stream):
+        B = image.shape[0]
+        check(lib.vitcap_engine_encode(*self._head(image, B, opts, ws, need), stream), 'engine_encode')
+        check(lib.vitcap_engine_prefill(*self._head(None, B, opts, ws, need), stream), 'engine_prefill')
+
+    def _decode(self, kind, image, B, opts, ws, need, ids, lp, tail, forced=None, score_forced=0, tok_lp=None, vis=None, stream=None):
+        """One call of the decode family: vitcap_engine_generate[_kind] on `image`, or with image None vitcap_engine_decode[_kind] on
+        the prefill the workspace holds; kind '' | 'forced' | 'masked' | 'beam_masked'.  tail: (last,) of a staged call, (tag_logits,
+        tag_topk) of a whole one, tensors or None.  Every kind but '' takes the forced ids and gives the per-token log-probs."""
+        fn = 'engine_' + ('decode' if image is None else 'generate') + ('_' + kind if kind else '')
+        args = self._head(image, B, opts, ws, need) + ((_p(forced), int(score_forced)) if kind else ()) + (_p(ids), _p(lp)) \
+            + ((_p(tok_lp),) if kind else ()) + tuple(_p(t) for t in tail) + ((_p(vis),) if kind.endswith('masked') else ()) \
+            + (_stream() if stream is None else stream,)
+        check(getattr(lib, 'vitcap_' + fn)(*args), fn)
 
     def run(self, image, opts, want_tags=False, slot=0, want_last=False, forced=None, score_forced=0, want_token_logprobs=False,
             vis=None):
@@ -404,69 +469,16 @@ class ImageCaptioning(nn.Module):
         forced (rows, max_length) int64 / score_forced: vitcap_amd.forced.pack_forced; with want_token_logprobs the per-token
         log-probs (rows, max_length) are returned last.  Either one makes it a vitcap_engine_generate_forced call.
         vis int32 (rows, 19), vitcap_amd.occlusion.pack_visible: visual keys hidden per sequence, a vitcap_engine_generate_masked
-        call (no hipGraph: the call sets use_graph = 0).  With vis, image None decodes on the prefill the last call left on `slot`
-        (vitcap_engine_decode_masked)."""
+        call (no hipGraph: the call sets use_graph = 0).  With vis, image None decodes on the prefill the last call left on `slot`.
+        want_last (or image None) takes the staged path -- vitcap_engine_encode + _prefill, then vitcap_engine_decode[_forced |
+        _masked] -- and returns the token chosen at the last position behind (ids, logprobs)."""
         use_forced = forced is not None or want_token_logprobs
         if use_forced:
             self.refuse_forced_search(opts.num_beams, opts.use_cbs)
         if vis is not None:
-            if opts.num_beams > 1 or opts.use_cbs or opts.tag_visible > 0:
-                raise NotImplementedError('a visibility mask is not built for num_beams > 1 / use_cbs / tag_visible > 0 (got %d, %d, %d)'
-                                          % (opts.num_beams, opts.use_cbs, opts.tag_visible))
+            _refuse_options('run', 'visible', dict(num_beams=opts.num_beams, use_cbs=opts.use_cbs, tag_visible=opts.tag_visible))
             opts.use_graph = 0
-            return self._run_masked(image, opts, vis, want_tags, slot, want_last, forced, score_forced, want_token_logprobs)
-        dev = self._check_image(image)
-        B = image.shape[0]
-        rows = B * opts.seqs_per_image
-        fp = tp = tok_lp = None
-        if forced is not None:
-            if tuple(forced.shape) != (rows, opts.max_length):
-                raise ValueError('forced ids must be (%d, %d), got %s' % (rows, opts.max_length, tuple(forced.shape)))
-            forced = forced.to(device=dev, dtype=torch.int64).contiguous()
-            fp = C.c_void_p(forced.data_ptr())
-        if want_token_logprobs:
-            tok_lp = torch.empty((rows, opts.max_length), dtype=torch.float32, device=dev)
-            tp = C.c_void_p(tok_lp.data_ptr())
-        ws, need = self._workspace(B, dev, slot, opts)
-        ids, lp = self._out_buffers(B, opts, dev)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        wp = C.c_void_p(ws.data_ptr())
-        extra = (tok_lp,) if want_token_logprobs else ()
-        self._encoded[slot] = (opts, B)
-        if want_last:
-            last = torch.empty((rows,), dtype=torch.int64, device=dev)
-            check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                           C.byref(opts), wp, need, s), 'engine_encode')
-            check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
-            if use_forced:
-                check(lib.vitcap_engine_decode_forced(self._engine, B, C.byref(opts), wp, need, fp, int(score_forced),
-                                                      C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tp,
-                                                      C.c_void_p(last.data_ptr()), s), 'engine_decode_forced')
-            else:
-                check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()),
-                                               C.c_void_p(lp.data_ptr()), C.c_void_p(last.data_ptr()), s), 'engine_decode')
-            return (ids, lp, last) + extra
-        tag_logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev) if want_tags else None
-        tag_topk = torch.empty((B, 50), dtype=torch.int64, device=dev) if want_tags else None
-        tl = C.c_void_p(tag_logits.data_ptr()) if want_tags else None
-        tk = C.c_void_p(tag_topk.data_ptr()) if want_tags else None
-        if use_forced:
-            check(lib.vitcap_engine_generate_forced(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                                    C.byref(opts), wp, need, fp, int(score_forced), C.c_void_p(ids.data_ptr()),
-                                                    C.c_void_p(lp.data_ptr()), tp, tl, tk, s), 'engine_generate_forced')
-        else:
-            check(lib.vitcap_engine_generate(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                             C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tl, tk, s),
-                  'engine_generate')
-        if want_tags:
-            self.last_tags = (tag_logits, tag_topk)
-        self._last = (slot, opts, B)
-        return (ids, lp) + extra
-
-    def _run_masked(self, image, opts, vis, want_tags, slot, want_last, forced, score_forced, want_token_logprobs):
-        """run() with a visibility mask: vitcap_engine_generate_masked, or with image None / want_last the staged calls ending in
-        vitcap_engine_decode_masked."""
-        if image is not None:
+        if image is not None or vis is None:
             dev, B = self._check_image(image), image.shape[0]
         else:
             if slot not in self._encoded:
@@ -477,45 +489,35 @@ class ImageCaptioning(nn.Module):
                 raise ValueError('the last call on slot %r ran other options (max_length / tags)' % (slot,))
             dev = self._packed[2]
         rows = B * opts.seqs_per_image
-        if tuple(vis.shape) != (rows, 19):
-            raise ValueError('the packed visibility mask must be (%d, 19), got %s' % (rows, tuple(vis.shape)))
-        # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
-        vis = vis.to(device=dev, dtype=torch.int32).contiguous()
-        fp = tp = tok_lp = None
+        if vis is not None:
+            if tuple(vis.shape) != (rows, 19):
+                raise ValueError('the packed visibility mask must be (%d, 19), got %s' % (rows, tuple(vis.shape)))
+            # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
+            vis = vis.to(device=dev, dtype=torch.int32).contiguous()
+        tok_lp = None
         if forced is not None:
             if tuple(forced.shape) != (rows, opts.max_length):
                 raise ValueError('forced ids must be (%d, %d), got %s' % (rows, opts.max_length, tuple(forced.shape)))
             forced = forced.to(device=dev, dtype=torch.int64).contiguous()
-            fp = C.c_void_p(forced.data_ptr())
         if want_token_logprobs:
             tok_lp = torch.empty((rows, opts.max_length), dtype=torch.float32, device=dev)
-            tp = C.c_void_p(tok_lp.data_ptr())
         ws, need = self._workspace(B, dev, slot, opts, keep=image is None)
         ids, lp = self._out_buffers(B, opts, dev)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        wp, vp = C.c_void_p(ws.data_ptr()), C.c_void_p(vis.data_ptr())
         extra = (tok_lp,) if want_token_logprobs else ()
+        kind = 'masked' if vis is not None else 'forced' if use_forced else ''
+        self._encoded[slot] = (opts, B)
         if image is None or want_last:
+            # staged: the encoder and the prefill (unless the slot holds them), then the decode loop on their own
             last = torch.empty((rows,), dtype=torch.int64, device=dev) if want_last else None
             if image is not None:
-                check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                               C.byref(opts), wp, need, s), 'engine_encode')
-                check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
-            check(lib.vitcap_engine_decode_masked(self._engine, B, C.byref(opts), wp, need, fp, int(score_forced),
-                                                  C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()), tp,
-                                                  C.c_void_p(last.data_ptr()) if want_last else None, vp, s), 'engine_decode_masked')
-            self._encoded[slot] = (opts, B)
+                self._encode_prefill(image, opts, ws, need, _stream())
+            self._decode(kind, None, B, opts, ws, need, ids, lp, (last,), forced, score_forced, tok_lp, vis)
             return ((ids, lp, last) if want_last else (ids, lp)) + extra
-        tag_logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev) if want_tags else None
-        tag_topk = torch.empty((B, 50), dtype=torch.int64, device=dev) if want_tags else None
-        tl = C.c_void_p(tag_logits.data_ptr()) if want_tags else None
-        tk = C.c_void_p(tag_topk.data_ptr()) if want_tags else None
-        check(lib.vitcap_engine_generate_masked(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B,
-                                                C.byref(opts), wp, need, fp, int(score_forced), C.c_void_p(ids.data_ptr()),
-                                                C.c_void_p(lp.data_ptr()), tp, tl, tk, vp, s), 'engine_generate_masked')
+        tags = (torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev),
+                torch.empty((B, 50), dtype=torch.int64, device=dev)) if want_tags else (None, None)
+        self._decode(kind, image, B, opts, ws, need, ids, lp, tags, forced, score_forced, tok_lp, vis)
         if want_tags:
-            self.last_tags = (tag_logits, tag_topk)
-        self._encoded[slot] = (opts, B)
+            self.last_tags = tags
         self._last = (slot, opts, B)
         return (ids, lp) + extra
 
@@ -595,24 +597,10 @@ class ImageCaptioning(nn.Module):
         """Host-side checks of the one-pass scorer, before anything touches the GPU: the engine's refusals by option name
         (NotImplementedError), then pack_forced's checks of the captions.  -> (opts, caption ids (rows, L), last_tok or None)."""
         from .forced import pack_forced
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if int(te.get('num_beams', 1) or 1) > 1:
-            raise NotImplementedError('one_pass scoring needs num_beams == 1 (got %s): a caption is scored, not searched' % te['num_beams'])
-        if te.get('use_cbs', False):
-            raise NotImplementedError('one_pass scoring does not run use_cbs')
-        if float(te.get('repetition_penalty', 1) or 1) != 1.0:
-            raise NotImplementedError('one_pass scoring is not built for repetition_penalty != 1 (got %s): the stepwise path scores the '
-                                      'penalised row' % te['repetition_penalty'])
-        if int(te.get('tag_visible', 0) or 0) > 0:
-            raise NotImplementedError('one_pass scoring is not built for tag_visible > 0 (got %s)' % te['tag_visible'])
-        if te.get('do_sample', False):
-            raise NotImplementedError('one_pass scoring does not run do_sample: nothing is drawn')
+        self._refuse('one_pass scoring', 'one_pass', over)
         if not 1 <= K <= 32:
             raise NotImplementedError('one_pass scoring takes seqs_per_image 1..32 (got %d)' % K)
-        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
-            over.pop(k, None)
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+        o = self._greedy_options(over)
         rows = int(B) * K
         pack_forced(caption_ids=caption_ids, rows=rows, max_length=o.max_length, last_tok=last_tok)      # the refusals only
         cap = torch.as_tensor(caption_ids).to(torch.int64).reshape(rows, o.max_length)
@@ -669,8 +657,7 @@ class ImageCaptioning(nn.Module):
             vis = vis.to(device=dev, dtype=torch.int32).contiguous()
             assert tuple(vis.shape) == (rows, 19)
             req.kind, req.vis_mask = L.SCORE_MASKED, vis.data_ptr()
-        check(lib.vitcap_engine_score_req(self._engine, C.byref(req), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-              'engine_score_req')
+        check(lib.vitcap_engine_score_req(self._engine, C.byref(req), _stream()), 'engine_score_req')
         if image is not None:
             self._encoded[slot] = (o, B)
         return (lp, tok_lp, ids) + extra if extra or return_ids else (lp, tok_lp)
@@ -695,18 +682,11 @@ class ImageCaptioning(nn.Module):
             then(B)
         return image, B, o, cap, lt, (self._check_image(image) if image is not None else self._packed[2])
 
-    def _greedy_caption(self, who, what, image, slot, over):
-        """The opening of the caption_with_* calls: greedy captions only, then generate() through the staged path.  Takes the search
-        options out of `over`.  -> (opts, ids, logprobs, last_tok)."""
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if int(te.get('num_beams', 1) or 1) > 1 or te.get('use_cbs', False) or te.get('do_sample', False):
-            raise NotImplementedError('%s runs greedy captions only (got num_beams=%s, use_cbs=%s, do_sample=%s): %s under beam search, '
-                                      'CBS or sampling are not built'
-                                      % (who, te.get('num_beams', 1), bool(te.get('use_cbs', False)), bool(te.get('do_sample', False)), what))
-        for k in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best'):
-            over.pop(k, None)
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, **over)
+    def _greedy_caption(self, who, image, slot, over):
+        """The opening of the caption_with_* calls: greedy captions only, then generate() through the staged path.
+        -> (opts, ids, logprobs, last_tok)."""
+        self._refuse(who, 'greedy', over)
+        o = self._greedy_options(over)
         return (o,) + self.run(image, o, slot=slot, want_last=True)
 
     def score_encoded(self, caption_ids, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
@@ -753,7 +733,7 @@ class ImageCaptioning(nn.Module):
         """Greedy captions and where the model looked for each of their words: generate() through the staged path, then
         attention_maps_encoded() on its own output (the token chosen at the last position handed over as last_tok).
         -> (ids (B, 1, L), logprobs (B, 1), maps)."""
-        o, ids, lp, last = self._greedy_caption('caption_with_maps', 'attention maps', image, slot, over)
+        o, ids, lp, last = self._greedy_caption('caption_with_maps', image, slot, over)
         _, _, maps = self.attention_maps_encoded(ids.view(image.shape[0], o.max_length), 1, per_head=per_head, layers=layers, slot=slot,
                                                  last_tok=last, **over)
         return ids, lp, maps
@@ -790,7 +770,7 @@ class ImageCaptioning(nn.Module):
         log-probs of the caption's words (B, L) come last."""
         from .alternatives import check_k
         k = check_k(k)
-        o, ids, lp, last = self._greedy_caption('caption_with_alternatives', 'alternatives', image, slot, over)
+        o, ids, lp, last = self._greedy_caption('caption_with_alternatives', image, slot, over)
         _, tok_lp, alts = self.alternatives_encoded(ids.view(image.shape[0], o.max_length), 1, k=k, slot=slot, last_tok=last, **over)
         return (ids, lp, alts, tok_lp) if want_token_logprobs else (ids, lp, alts)
 
@@ -883,7 +863,7 @@ class ImageCaptioning(nn.Module):
         drop (B, L, gh, gw))."""
         from .occlusion import check_window
         check_window(window, stride)
-        o, ids, lp, last = self._greedy_caption('caption_with_occlusion', 'occlusion maps', image, slot, over)
+        o, ids, lp, last = self._greedy_caption('caption_with_occlusion', image, slot, over)
         _, _, drop = self.occlusion_maps_encoded(ids.view(image.shape[0], o.max_length), window, stride, keep_cls, keep_only, slot=slot,
                                                  last_tok=last, **over)
         return ids, lp, drop
@@ -901,11 +881,7 @@ class ImageCaptioning(nn.Module):
     def _caption_regions(self, who, image, regions, keep_cls, slot, over):
         from .occlusion import pack_visible
         from .regions import MAX_REGIONS, region_masks
-        te = dict(self.test_extra_input)
-        te.update(over)
-        if te.get('do_sample', False):
-            raise NotImplementedError('%s writes greedy captions; do_sample is not built for it' % who)
-        self.refuse_visible(who, over)
+        self._refuse(who, 'regions', over)
         if image is not None:
             B = image.shape[0]
         else:
@@ -914,8 +890,7 @@ class ImageCaptioning(nn.Module):
             B = self._encoded[slot][1]
         masks, _ = region_masks(regions, B, keep_cls)                  # (B, R, 578)
         R = masks.shape[1]
-        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
-        o = self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+        o = self._greedy_options(over, no_graph=True)
         all_ids, all_lp = [], []
         for r0 in range(0, R, MAX_REGIONS):
             n = min(MAX_REGIONS, R - r0)
@@ -952,7 +927,7 @@ class ImageCaptioning(nn.Module):
         from .regions import region_masks
         self.refuse_visible('caption_with_regions', over)
         region_masks(regions, image.shape[0], keep_cls)      # the refusals, before the GPU is touched
-        o, ids, lp, _ = self._greedy_caption('caption_with_regions', 'region captions', image, slot, over)
+        o, ids, lp, _ = self._greedy_caption('caption_with_regions', image, slot, over)
         rids, rlp = self.caption_regions_encoded(regions, keep_cls=keep_cls, slot=slot, **over)
         return ids, lp, rids, rlp
 
@@ -977,29 +952,19 @@ class ImageCaptioning(nn.Module):
     # ---- region captions under beam search (vitcap_engine_*_beam_masked): one mask row per image, all its beams see the same part
     def refuse_visible_beam(self, who, num_beams, over=None):
         """What a visibility mask under beam search is not built for, refused by the option's name before the GPU is touched."""
-        te = dict(self.test_extra_input)
-        te.update(over or {})
         if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 2 <= int(num_beams) <= 8:
             raise NotImplementedError('%s: a visibility mask under beam search needs num_beams 2..8 (got num_beams=%r; one beam is '
                                       'generate(visible=) / caption_regions)' % (who, num_beams))
-        if te.get('use_cbs', False):
-            raise NotImplementedError('%s: a visibility mask under beam search is not built for use_cbs' % who)
-        if int(te.get('tag_visible', 0) or 0) > 0:
-            raise NotImplementedError('%s: a visibility mask under beam search is not built for tag_visible > 0 (got %s)'
-                                      % (who, te['tag_visible']))
-        if te.get('do_sample', False):
-            raise NotImplementedError('%s: a visibility mask under beam search is not built for do_sample (beam sampling)' % who)
-        if te.get('use_graph', False):
-            raise NotImplementedError('%s: a visibility mask is not built for use_graph (a captured loop would freeze the mask pointer)' % who)
-        for k in ('prefix_ids', 'forced_ids', 'want_token_logprobs'):
+        te = self._refuse(who, 'visible_beam', over)
+        for k in self._FORCED_KEYS:
             if te.get(k) is not None and te.get(k) is not False:
                 raise NotImplementedError('%s: %s -- forced tokens under beam search are not built' % (who, k))
 
+    _FORCED_KEYS = ('prefix_ids', 'forced_ids', 'want_token_logprobs')
+
     def _beam_masked_options(self, num_beams, length_penalty, num_keep_best, over):
-        over = {k: v for k, v in over.items() if k not in ('num_beams', 'length_penalty', 'num_keep_best', 'num_return_sequences',
-                                                           'do_sample', 'use_graph', 'prefix_ids', 'forced_ids', 'want_token_logprobs')}
-        return self.gen_options(num_beams=int(num_beams), length_penalty=float(length_penalty), num_keep_best=int(num_keep_best),
-                                num_return_sequences=1, do_sample=False, use_graph=False, **over)
+        return self._greedy_options(over, no_graph=True, drop=self._FORCED_KEYS, num_beams=int(num_beams),
+                                    length_penalty=float(length_penalty), num_keep_best=int(num_keep_best))
 
     def _run_beam_masked(self, image, opts, vis_list, slot, whole=False):
         """The images are encoded and prefilled once under the beam options `opts`; then, with `whole`, one plain beam decode, and one
@@ -1012,29 +977,17 @@ class ImageCaptioning(nn.Module):
         # read in place by the enqueued kernels: allocated and released on this stream, so the blocks are not reused before them
         vis_list = [v.to(device=dev, dtype=torch.int32).contiguous() for v in vis_list]
         ws, need = self._workspace(B, dev, slot, opts)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        wp, ip, bf = C.c_void_p(ws.data_ptr()), C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16)
         self._encoded[slot] = (opts, B)
         self._last = (slot, opts, B)
-        out = []
         if len(vis_list) == 1 and not whole:
             ids, lp = self._out_buffers(B, opts, dev)
-            check(lib.vitcap_engine_generate_beam_masked(self._engine, ip, bf, B, C.byref(opts), wp, need, None, 0, C.c_void_p(ids.data_ptr()),
-                                                         C.c_void_p(lp.data_ptr()), None, None, None, C.c_void_p(vis_list[0].data_ptr()), s),
-                  'engine_generate_beam_masked')
+            self._decode('beam_masked', image, B, opts, ws, need, ids, lp, (None, None), vis=vis_list[0])
             return [(ids, lp)]
-        check(lib.vitcap_engine_encode(self._engine, ip, bf, B, C.byref(opts), wp, need, s), 'engine_encode')
-        check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, s), 'engine_prefill')
-        if whole:
+        self._encode_prefill(image, opts, ws, need, _stream())
+        out = []
+        for v in ([None] if whole else []) + vis_list:      # None: the plain beam decode of the whole image
             ids, lp = self._out_buffers(B, opts, dev)
-            check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()),
-                                           None, s), 'engine_decode')
-            out.append((ids, lp))
-        for v in vis_list:
-            ids, lp = self._out_buffers(B, opts, dev)
-            check(lib.vitcap_engine_decode_beam_masked(self._engine, B, C.byref(opts), wp, need, None, 0, C.c_void_p(ids.data_ptr()),
-                                                       C.c_void_p(lp.data_ptr()), None, None, C.c_void_p(v.data_ptr()), s),
-                  'engine_decode_beam_masked')
+            self._decode('' if v is None else 'beam_masked', None, B, opts, ws, need, ids, lp, (None,), vis=v)
             out.append((ids, lp))
         return out
 
@@ -1081,25 +1034,7 @@ class ImageCaptioning(nn.Module):
     def refuse_patches(self, who, over=None):
         """Patch removal exists for the greedy loop and the one-pass scorer without visible tags and without a hipGraph: anything else
         is refused by the option's name, before the GPU is touched."""
-        te = dict(self.test_extra_input)
-        te.update(over or {})
-        if te.get('use_cbs', False):
-            raise NotImplementedError('%s: patch removal is not built for use_cbs' % who)
-        if int(te.get('num_beams', 1) or 1) > 1:
-            raise NotImplementedError('%s: patch removal is not built for num_beams > 1 (got %s): forced tokens and searches under '
-                                      'beams are not built for it' % (who, te['num_beams']))
-        if int(te.get('tag_visible', 0) or 0) > 0:
-            raise NotImplementedError('%s: patch removal is not built for tag_visible > 0 (got %s): the tag rows\' prefill is unmasked'
-                                      % (who, te['tag_visible']))
-        if te.get('use_graph', False):
-            raise NotImplementedError('%s: patch removal is not built for use_graph: a captured loop would freeze this call\'s mask' % who)
-        if te.get('do_sample', False):
-            raise NotImplementedError('%s: patch removal writes greedy captions; do_sample is not built for it' % who)
-
-    def _patch_options(self, who, over):
-        self.refuse_patches(who, over)
-        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
-        return self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+        self._refuse(who, 'patches', over)
 
     def _encode_patches(self, image, words, o, slot):
         """Encoder and prefill of `image` under the packed presence rows `words` (B, 19) -> (workspace, bytes, words on the device)."""
@@ -1109,11 +1044,8 @@ class ImageCaptioning(nn.Module):
         # read in place by the enqueued kernels: allocated and released on this stream, so the block is not reused before them
         words = words.to(device=dev, dtype=torch.int32).contiguous()
         ws, need = self._workspace(B, dev, slot, o)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        wp, mp = C.c_void_p(ws.data_ptr()), C.c_void_p(words.data_ptr())
-        check(lib.vitcap_engine_encode_patches(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
-                                               wp, need, mp, s), 'engine_encode_patches')
-        check(lib.vitcap_engine_prefill_patches(self._engine, B, C.byref(o), wp, need, mp, s), 'engine_prefill_patches')
+        check(lib.vitcap_engine_encode_patches(*self._head(image, B, o, ws, need), _p(words), _stream()), 'engine_encode_patches')
+        check(lib.vitcap_engine_prefill_patches(*self._head(None, B, o, ws, need), _p(words), _stream()), 'engine_prefill_patches')
         enc = _PatchEncoded((o, B))
         enc.words = words
         self._encoded[slot] = enc
@@ -1125,8 +1057,7 @@ class ImageCaptioning(nn.Module):
         dev = ws.device
         logits = torch.empty((B, L.VOCAB), dtype=torch.float32, device=dev)
         topk = torch.empty((B, 50), dtype=torch.int64, device=dev)
-        check(lib.vitcap_engine_tags(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), C.c_void_p(logits.data_ptr()),
-                                     C.c_void_p(topk.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'engine_tags')
+        check(lib.vitcap_engine_tags(self._engine, B, C.byref(o), _p(ws), _p(logits), _p(topk), _stream()), 'engine_tags')
         return (logits, topk, self.tap('tag_prob', B, (B, 50), slot=slot, opts=o),
                 self.tap('tag_len', B, (B,), dtype=torch.int64, slot=slot, opts=o))
 
@@ -1137,7 +1068,8 @@ class ImageCaptioning(nn.Module):
         (and the prefill) only and leaves the slot encoded for the other *_patches calls.
         -> (tag_logits (B, 30522), tag_topk (B, 50), tag_prob (B, 50), tag_len (B,))."""
         from .patches import pack_present
-        o = self._patch_options('tag_patches', over)
+        self.refuse_patches('tag_patches', over)
+        o = self._greedy_options(over, no_graph=True)
         words = pack_present(present, image.shape[0])
         ws, _, _ = self._encode_patches(image, words, o, slot)
         return self._tags_of_slot(o, image.shape[0], ws, slot)
@@ -1149,7 +1081,8 @@ class ImageCaptioning(nn.Module):
         -> (ids (B, 1, L), logprobs (B, 1)) [+ token_logprobs (B, L)]; with want_tags, self.last_tags = (tag_logits, tag_topk) and
         self.last_tag_probs = (tag_prob, tag_len).  CBS, beams, visible tags, use_graph and sampling are a NotImplementedError."""
         from .patches import pack_present
-        o = self._patch_options('caption_patches', over)
+        self.refuse_patches('caption_patches', over)
+        o = self._greedy_options(over, no_graph=True)
         B = image.shape[0]
         words = pack_present(present, B)
         ws, need, words = self._encode_patches(image, words, o, slot)
@@ -1158,11 +1091,7 @@ class ImageCaptioning(nn.Module):
             self.last_tags, self.last_tag_probs = tags[:2], tags[2:]
         ids, lp = self._out_buffers(B, o, ws.device)
         tok_lp = torch.empty((B, o.max_length), dtype=torch.float32, device=ws.device) if want_token_logprobs else None
-        check(lib.vitcap_engine_decode_masked(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, None, 0,
-                                              C.c_void_p(ids.data_ptr()), C.c_void_p(lp.data_ptr()),
-                                              C.c_void_p(tok_lp.data_ptr()) if want_token_logprobs else None, None,
-                                              C.c_void_p(words.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-              'engine_decode_masked')
+        self._decode('masked', None, B, o, ws, need, ids, lp, (None,), tok_lp=tok_lp, vis=words)
         return (ids, lp, tok_lp) if want_token_logprobs else (ids, lp)
 
     def score_patches(self, image, caption_ids, present, seqs_per_image=1, slot=0, return_ids=False, last_tok=None, **over):
@@ -1217,27 +1146,13 @@ class ImageCaptioning(nn.Module):
     def refuse_rollout(self, who, over=None):
         """The encoder's attention is written out by a plain greedy / one-pass pass without visible tags and without a hipGraph:
         anything else is refused by the option's name, before the GPU is touched."""
-        te = dict(self.test_extra_input)
-        te.update(over or {})
-        if te.get('use_cbs', False):
-            raise NotImplementedError('%s: the encoder rollout is not built for use_cbs' % who)
-        if int(te.get('num_beams', 1) or 1) > 1:
-            raise NotImplementedError('%s: the encoder rollout is not built for num_beams > 1 (got %s)' % (who, te['num_beams']))
-        if int(te.get('tag_visible', 0) or 0) > 0:
-            raise NotImplementedError('%s: the encoder rollout is not built for tag_visible > 0 (got %s): it has no path for the tag rows'
-                                      % (who, te['tag_visible']))
-        if te.get('do_sample', False):
-            raise NotImplementedError('%s: the encoder rollout explains greedy or given captions; do_sample is not built for it' % who)
-        if te.get('use_graph', False):
-            raise NotImplementedError('%s: the encoder rollout is not built for use_graph: the maps are written by the call\'s own '
-                                      'launches' % who)
+        self._refuse(who, 'rollout', over)
 
     def _rollout_options(self, who, slot, over):
         """The refusals, then -> the validated options of a greedy pass without a hipGraph."""
         self.refuse_rollout(who, over)
         self._refuse_patch_slot(who, slot)
-        over = {k: v for k, v in over.items() if k not in ('num_beams', 'do_sample', 'num_return_sequences', 'num_keep_best', 'use_graph')}
-        return self.gen_options(num_beams=1, do_sample=False, num_return_sequences=1, num_keep_best=1, use_graph=False, **over)
+        return self._greedy_options(over, no_graph=True)
 
     def _encode_maps(self, image, o, slot, mask, per_head):
         """vitcap_engine_encode_maps + vitcap_engine_prefill of `image` on `slot` -> (maps (n_sel, B, [12,] 577, 577), workspace,
@@ -1246,12 +1161,9 @@ class ImageCaptioning(nn.Module):
         n_sel = bin(mask).count('1')
         maps = torch.empty((n_sel, B) + ((12,) if per_head else ()) + (577, 577), dtype=torch.float32, device=dev)
         ws, need = self._workspace(B, dev, slot, o)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        wp = C.c_void_p(ws.data_ptr())
-        check(lib.vitcap_engine_encode_maps(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16), B, C.byref(o),
-                                            wp, need, mask, int(bool(per_head)), C.c_void_p(maps.data_ptr()),
-                                            maps.numel() * 4, s), 'engine_encode_maps')
-        check(lib.vitcap_engine_prefill(self._engine, B, C.byref(o), wp, need, s), 'engine_prefill')
+        check(lib.vitcap_engine_encode_maps(*self._head(image, B, o, ws, need), mask, int(bool(per_head)), _p(maps), maps.numel() * 4,
+                                            _stream()), 'engine_encode_maps')
+        check(lib.vitcap_engine_prefill(*self._head(None, B, o, ws, need), _stream()), 'engine_prefill')
         self._encoded[slot] = (o, B)
         self._last = (slot, o, B)
         return maps, ws, need
@@ -1309,9 +1221,7 @@ class ImageCaptioning(nn.Module):
         if cap is None:
             ids, glp = self._out_buffers(B, o, A.device)
             lt = torch.empty((B,), dtype=torch.int64, device=A.device)
-            check(lib.vitcap_engine_decode(self._engine, B, C.byref(o), C.c_void_p(ws.data_ptr()), need, C.c_void_p(ids.data_ptr()),
-                                           C.c_void_p(glp.data_ptr()), C.c_void_p(lt.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'engine_decode')
+            self._decode('', None, B, o, ws, need, ids, glp, (lt,))
             cap, own = ids.view(B, Lm), (ids, glp)
         lp, tok_lp, _, maps = self._score_one_pass(None, B, o, cap, lt, K, slot, A.device, False, maps=(False, lmask))
         m = maps.view(B, K, Lm, 4, maps.shape[-1]).sum(3) * (1.0 / nl)      # unselected layers are zeros; NOT renormalised
@@ -1340,10 +1250,7 @@ class ImageCaptioning(nn.Module):
         nl = bin(lmask).count('1')
         self.refuse_rollout('rollout_maps', over)
         self._refuse_patch_slot('rollout_maps', slot)
-        over.pop('use_graph', None)
-        B = image.shape[0]
-        o, cap, lt = self._score_inputs(B, caption_ids, K, last_tok, over)
-        o.use_graph = 0
+        o, cap, lt = self._score_inputs(image.shape[0], caption_ids, K, last_tok, dict(over, use_graph=False))
         out, i = [], 0
         for img in self._image_chunks(image, R.N_BLOCKS, False):
             n = img.shape[0]
@@ -1418,22 +1325,17 @@ class ImageCaptioning(nn.Module):
         ready = torch.cuda.Event()
         ready.record(cur)
         image.record_stream(pipe['enc'])
-        wp = C.c_void_p(ws.data_ptr())
         with torch.cuda.stream(pipe['enc']):
             pipe['enc'].wait_event(ready)
             if pipe['done'][slot] is not None:
                 pipe['enc'].wait_event(pipe['done'][slot])         # the slot's previous decode has drained
-            h = C.c_void_p(pipe['enc'].cuda_stream)
-            check(lib.vitcap_engine_encode(self._engine, C.c_void_p(image.data_ptr()), int(image.dtype == torch.bfloat16),
-                                           B, C.byref(opts), wp, need, h), 'engine_encode')
-            check(lib.vitcap_engine_prefill(self._engine, B, C.byref(opts), wp, need, h), 'engine_prefill')
+            self._encode_prefill(image, opts, ws, need, _stream(pipe['enc']))
             filled = torch.cuda.Event()
             filled.record(pipe['enc'])
         with torch.cuda.stream(pipe['dec']):
             pipe['dec'].wait_event(filled)
             ids, lp = self._out_buffers(B, opts, dev)
-            check(lib.vitcap_engine_decode(self._engine, B, C.byref(opts), wp, need, C.c_void_p(ids.data_ptr()),
-                                           C.c_void_p(lp.data_ptr()), None, C.c_void_p(pipe['dec'].cuda_stream)), 'engine_decode')
+            self._decode('', None, B, opts, ws, need, ids, lp, (None,), stream=_stream(pipe['dec']))
             # blocking: a host thread that waits for this batch SLEEPS (hipEventBlockingSync) instead of spinning on a core -- under a
             # CPU quota (the GPU pool gives 16 cores) spinning waiters starve the JPEG decode workers of the loader
             done = torch.cuda.Event(blocking=True)
@@ -1459,7 +1361,7 @@ class ImageCaptioning(nn.Module):
             last = getattr(self, '_last', None)
             opts = last[1] if last is not None and last[0] == slot and last[2] == B else self.gen_options()
         ws, _ = self._workspace(B, self._packed[2], slot, opts)
-        p = lib.vitcap_engine_tap(self._engine, name.encode(), C.c_void_p(ws.data_ptr()), B, C.byref(opts))
+        p = lib.vitcap_engine_tap(self._engine, name.encode(), _p(ws), B, C.byref(opts))
         if not p:
             raise KeyError(name)
         off = p - ws.data_ptr()

@@ -16,7 +16,9 @@ get_raw_model 566-618, predict_output_to_tsv_row 620-630) for what the hot path 
   writes reference-format snapshots; ``ensure_evaluate`` needs the external
   coco-caption tools the reference does not vendor either and is a logged no-op without them.
 """
+import collections
 import copy
+import functools
 import json
 import logging
 import os
@@ -27,9 +29,12 @@ import torch
 
 from . import dist_util as D
 
+from .alternatives import check_k
 from .checkpoint import Checkpointer
 from .config import Config
 from .loader import LOADER_TIMES, prefetched, timed      # LOADER_TIMES: the loader's own dict (tools/input_side_bench.py reads it here)
+from .occlusion import check_window
+from .regions import grid_regions
 
 LAST_PREDICT_STATS = {}     # filled by CaptionUniPipeline.predict: rows, steady-state images/sec of this rank (tools/input_side_bench.py)
 
@@ -130,6 +135,30 @@ class _EngineState(object):
         return torch.nn.modules.module._IncompatibleKeys([], [])
 
 
+# The analysis modes of predict: a config key that, when set, makes predict caption batch by batch through one of
+# ImageCaptioning.caption_with_* and write a second TSV, <predict file minus .tsv><suffix>, one row per image, next to the predictions.
+# check: validates the key's value (ValueError); refuse_tags: `tag_visible` is refused up front (attention_maps refuses a mask that
+# shows tag slots only when the first batch arrives); rows(run, cfg, batches, dev, pred_rows): the second file's rows.  The order is
+# the order of the checks, and a mode is refused together with any mode before it.
+_Mode = collections.namedtuple('_Mode', 'key suffix noun check refuse_tags rows')
+_MODES = (
+    _Mode('attention_maps', '.attn.tsv', 'attention maps', None, False, lambda run, cfg, *a: run.attention_rows(*a)),
+    _Mode('alternatives', '.alt.tsv', 'alternatives', check_k, True, lambda run, cfg, *a: run.alternative_rows(*a, int(cfg.alternatives))),
+    _Mode('occlusion', '.occ.tsv', 'occlusion maps', check_window, True, lambda run, cfg, *a: run.occlusion_rows(*a, int(cfg.occlusion))),
+    _Mode('regions', '.regions.tsv', 'region captions', grid_regions, True,
+          lambda run, cfg, *a: run.region_rows(*a, int(cfg.regions), int(cfg.regions_beams) if cfg.regions_beams else None)),
+    _Mode('crops', '.crops.tsv', 'crop captions', grid_regions, True, lambda run, cfg, *a: run.crop_rows(*a, int(cfg.crops))),
+    _Mode('rollout', '.rollout.tsv', 'rollout maps', None, True, lambda run, cfg, *a: run.rollout_rows(*a)),
+)
+_NOUN = {m.key: m.noun for m in _MODES}
+
+
+def mode_file(predict_result_file, suffix):
+    """<predict file minus .tsv><suffix>: the second file predict writes when the config sets the mode of that suffix."""
+    assert predict_result_file.endswith('.tsv')
+    return predict_result_file[:-len('.tsv')] + suffix
+
+
 class _PredictRun(object):
     """State of one CaptionUniPipeline.predict: the generation options per number of visible tag slots, the count the last
     device-resident mask showed, the batches in flight and the row counter of the steady-state figure."""
@@ -218,8 +247,8 @@ class _PredictRun(object):
             for entry in self.pending:
                 yield from self.collect(entry)
 
-    def analysed(self, batches, dev, pred_rows, mode, what, caption_with):
-        """The batch loop of the analysis modes (cfg.attention_maps / alternatives / occlusion / regions): the batches strictly one after
+    def analysed(self, batches, dev, pred_rows, mode, caption_with):
+        """The batch loop of the analysis modes (_MODES; `mode` is the key of the one that runs): the batches strictly one after
         the other through `caption_with(image)`, one of ImageCaptioning.caption_with_* (no two-slot overlap; throughput is not a target
         of these modes).  The callers pass gemm_mode = TILES, the GEMM form of the ordinary predict loop, so that the captions and
         their confidences are that loop's, bit for bit.  Yields (batch, ids on the host, logprobs, what caption_with returned behind
@@ -231,11 +260,21 @@ class _PredictRun(object):
                 batch = dict(batch)
                 batch['image'] = batch['image'].to(dev, non_blocking=True).contiguous()
                 if model.check_text_inputs(batch, L) != 0:
-                    raise NotImplementedError('%s: visible tag slots (tag_visible > 0) are not built for the %s' % (mode, what))
+                    raise NotImplementedError('%s: visible tag slots (tag_visible > 0) are not built for the %s' % (mode, _NOUN[mode]))
                 ids, lp, *extras = caption_with(batch['image'])
                 ids_h = ids.cpu()
                 yield batch, ids_h, lp, extras
                 pred_rows.extend(self.pipe.predict_output_to_tsv_row(batch, (ids_h, lp.cpu())))
+
+    def live_words(self, toks):
+        """The live positions of a predicted caption `toks` (its ids as a list) are 1..n, through the first end token (or the last
+        column).  -> (n, the vocabulary entries of those positions)."""
+        L = int(self.pipe.cfg.max_gen_length)
+        eos = set(int(e) for e in (self.model.test_extra_input.get('eos_token_ids') or [102]))
+        ends = [t for t in range(1, L) if toks[t] in eos]
+        n = ends[0] if ends else L - 1
+        vocab = self.pipe.tokenizer.ids_to_tokens
+        return n, [vocab[i] for i in toks[1:n + 1]]
 
     def attention_rows(self, batches, dev, pred_rows):
         """cfg.attention_maps: yields the rows of the attention TSV, one per image (about 30 KB each: they are streamed to their
@@ -243,18 +282,14 @@ class _PredictRun(object):
         import base64
         import numpy as np
         from .attnmaps import patch_grid
-        model, L = self.model, int(self.pipe.cfg.max_gen_length)
-        vocab = self.pipe.tokenizer.ids_to_tokens
-        eos = set(int(e) for e in (model.test_extra_input.get('eos_token_ids') or [102]))
-        for batch, ids_h, lp, (maps,) in self.analysed(batches, dev, pred_rows, 'attention_maps', 'attention maps',
+        model = self.model
+        for batch, ids_h, lp, (maps,) in self.analysed(batches, dev, pred_rows, 'attention_maps',
                                                        lambda img: model.caption_with_maps(img, layers=(3,), gemm_mode=1)):
             grids = patch_grid(maps[:, :, 3]).to(torch.float16).cpu().numpy()      # (B, L, 24, 24)
             for b, key in enumerate(batch['key']):
-                toks = ids_h[b, 0].tolist()
-                ends = [t for t in range(1, L) if toks[t] in eos]
-                n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
+                n, words = self.live_words(ids_h[b, 0].tolist())
                 data = np.ascontiguousarray(grids[b, 1:n + 1])
-                yield key, json.dumps({'tokens': [vocab[i] for i in toks[1:n + 1]], 'layer': 3, 'shape': [n, 24, 24],
+                yield key, json.dumps({'tokens': words, 'layer': 3, 'shape': [n, 24, 24],
                                        'dtype': 'float16', 'data': base64.b64encode(data.tobytes()).decode('ascii')})
 
     def rollout_rows(self, batches, dev, pred_rows):
@@ -262,20 +297,16 @@ class _PredictRun(object):
         the predicted caption (vitcap_amd.rollout.to_rows) -- ImageCaptioning.caption_with_rollout with the tag map of the same
         encoder pass (want_tag)."""
         from .rollout import to_rows
-        model, L = self.model, int(self.pipe.cfg.max_gen_length)
-        vocab = self.pipe.tokenizer.ids_to_tokens
-        eos = set(int(e) for e in (model.test_extra_input.get('eos_token_ids') or [102]))
+        model = self.model
 
         def with_rollout(img):
             ids, lp, grid, _, _, tag, _ = model.caption_with_rollout(img, want_tag=True, gemm_mode=1)
             return ids, lp, grid, tag
-        for batch, ids_h, lp, (grid, tag) in self.analysed(batches, dev, pred_rows, 'rollout', 'rollout maps', with_rollout):
+        for batch, ids_h, lp, (grid, tag) in self.analysed(batches, dev, pred_rows, 'rollout', with_rollout):
             grid_h, tag_h = grid.cpu().numpy(), tag.cpu().numpy()
             for b, key in enumerate(batch['key']):
-                toks = ids_h[b, 0].tolist()
-                ends = [t for t in range(1, L) if toks[t] in eos]
-                n = (ends[0] if ends else L - 1)                  # live positions 1..n: up to and including the first end token
-                yield key, json.dumps(to_rows([vocab[i] for i in toks[1:n + 1]], tag_h[b], grid_h[b, 1:n + 1]))
+                n, words = self.live_words(ids_h[b, 0].tolist())
+                yield key, json.dumps(to_rows(words, tag_h[b], grid_h[b, 1:n + 1]))
 
     def alternative_rows(self, batches, dev, pred_rows, k):
         """cfg.alternatives = k: yields the rows of the alternatives TSV, one per image: the key and a JSON list with one record per
@@ -285,7 +316,7 @@ class _PredictRun(object):
         model, L = self.model, int(self.pipe.cfg.max_gen_length)
         vocab = self.pipe.tokenizer.ids_to_tokens
         for batch, ids_h, lp, (alts, tok_lp) in self.analysed(
-                batches, dev, pred_rows, 'alternatives', 'alternatives',
+                batches, dev, pred_rows, 'alternatives',
                 lambda img: model.caption_with_alternatives(img, k=k, want_token_logprobs=True, gemm_mode=1)):
             alts_h, tok_lp_h = type(alts)(*(x.cpu() for x in alts)), tok_lp.cpu()
             for b, key in enumerate(batch['key']):
@@ -304,7 +335,7 @@ class _PredictRun(object):
         from .occlusion import to_rows
         model = self.model
         eos = model.test_extra_input.get('eos_token_ids') or [102]
-        for batch, ids_h, lp, (drop,) in self.analysed(batches, dev, pred_rows, 'occlusion', 'occlusion maps',
+        for batch, ids_h, lp, (drop,) in self.analysed(batches, dev, pred_rows, 'occlusion',
                                                        lambda img: model.caption_with_occlusion(img, window=window, gemm_mode=1)):
             for key, recs in zip(batch['key'], to_rows(ids_h, drop.cpu(), self.pipe.tokenizer, eos=eos)):
                 yield key, json.dumps(recs)
@@ -321,7 +352,7 @@ class _PredictRun(object):
             ids, lp = model.generate(img, gemm_mode=1)
             rids, rlp = model.caption_regions_beam(img, boxes, beams, gemm_mode=1)
             return ids, lp, rids[:, :, 0], rlp[:, :, 0]
-        for batch, ids_h, lp, (rids, rlp) in self.analysed(batches, dev, pred_rows, 'regions', 'region captions',
+        for batch, ids_h, lp, (rids, rlp) in self.analysed(batches, dev, pred_rows, 'regions',
                                                            with_beams if beams else
                                                            lambda img: model.caption_with_regions(img, boxes, gemm_mode=1)):
             for key, recs in zip(batch['key'], to_rows(rids.cpu(), rlp.cpu(), boxes, self.pipe.tokenizer)):
@@ -339,7 +370,7 @@ class _PredictRun(object):
         def with_crops(img):
             ids, lp = model.generate(img, gemm_mode=1)
             return (ids, lp) + tuple(model.caption_crops(img, boxes, gemm_mode=1))
-        for batch, ids_h, lp, (cids, clp, ctopk, cprob) in self.analysed(batches, dev, pred_rows, 'crops', 'crop captions', with_crops):
+        for batch, ids_h, lp, (cids, clp, ctopk, cprob) in self.analysed(batches, dev, pred_rows, 'crops', with_crops):
             for key, recs in zip(batch['key'], to_rows(cids.cpu(), clp.cpu(), ctopk.cpu(), cprob.cpu(), boxes, self.pipe.tokenizer)):
                 yield key, json.dumps(recs)
 
@@ -717,7 +748,7 @@ class CaptionUniPipeline(object):
         model = self.load_test_model(self.get_raw_model(is_train=False), model_file)
         dev = torch.device('cuda', self.local_rank)
         model.pack(dev)
-        sub = predict_result_file if self.world == 1 else '{}_{}_{}.tsv'.format(predict_result_file, self.rank, self.world)
+        sub = self.rank_file(predict_result_file)
         from .tsv import tsv_writer
         run = _PredictRun(self, model)
         # batches queued on the device: capped in IMAGES (24 batches of 64 = 1 536 images = 1.4 GB of bf16 crops; the same count of
@@ -725,168 +756,37 @@ class CaptionUniPipeline(object):
         depth = int(self.cfg.loader_prefetch or os.environ.get('VITCAP_LOADER_PREFETCH', 0)) or max(2, min(24, 1536 // max(1, int(self.cfg.test_batch_size))))
         LOADER_TIMES.clear()
         batches = prefetched(self.iter_test_batches(), dev, depth=depth)
-        if self.cfg.attention_maps:
-            # a second TSV next to the predictions, one row per image: the last decoder layer's head-mean patch maps of the live positions
-            attn_file = self.get_attention_file(predict_result_file)
-            attn_sub = attn_file if self.world == 1 else '{}_{}_{}.tsv'.format(attn_file, self.rank, self.world)
-            pred_rows = []           # the small rows are held; the attention rows go to their file as they come
-            tsv_writer(run.counted(run.attention_rows(batches, dev, pred_rows)), attn_sub)
+        mode = next((m for m in _MODES if getattr(self.cfg, m.key)), None)
+        if mode is not None:
+            # a second TSV next to the predictions, one row per image
+            mode_sub = self.rank_file(mode_file(predict_result_file, mode.suffix))
+            pred_rows = []           # the small rows are held; the mode's rows (up to 30 KB each) go to their file as they come
+            tsv_writer(run.counted(mode.rows(run, self.cfg, batches, dev, pred_rows)), mode_sub)
             tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(attn_file)
-            return predict_result_file
-        if self.cfg.rollout:
-            # a second TSV next to the predictions, one row per image: the tag head's rollout map and one per word of the caption
-            ro_file = self.get_rollout_file(predict_result_file)
-            ro_sub = ro_file if self.world == 1 else '{}_{}_{}.tsv'.format(ro_file, self.rank, self.world)
-            pred_rows = []
-            tsv_writer(run.counted(run.rollout_rows(batches, dev, pred_rows)), ro_sub)
-            tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(ro_file)
-            return predict_result_file
-        if self.cfg.alternatives:
-            # a second TSV next to the predictions, one row per image: per word of the caption its alternatives, rank and entropy
-            alt_file = self.get_alternatives_file(predict_result_file)
-            alt_sub = alt_file if self.world == 1 else '{}_{}_{}.tsv'.format(alt_file, self.rank, self.world)
-            pred_rows = []
-            tsv_writer(run.counted(run.alternative_rows(batches, dev, pred_rows, int(self.cfg.alternatives))), alt_sub)
-            tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(alt_file)
-            return predict_result_file
-        if self.cfg.occlusion:
-            # a second TSV next to the predictions, one row per image: per word of the caption its window drops
-            occ_file = self.get_occlusion_file(predict_result_file)
-            occ_sub = occ_file if self.world == 1 else '{}_{}_{}.tsv'.format(occ_file, self.rank, self.world)
-            pred_rows = []
-            tsv_writer(run.counted(run.occlusion_rows(batches, dev, pred_rows, int(self.cfg.occlusion))), occ_sub)
-            tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(occ_file)
-            return predict_result_file
-        if self.cfg.regions:
-            # a second TSV next to the predictions, one row per image: a caption per tile of the g x g tiling
-            reg_file = self.get_regions_file(predict_result_file)
-            reg_sub = reg_file if self.world == 1 else '{}_{}_{}.tsv'.format(reg_file, self.rank, self.world)
-            pred_rows = []
-            tsv_writer(run.counted(run.region_rows(batches, dev, pred_rows, int(self.cfg.regions),
-                                                   int(self.cfg.regions_beams) if self.cfg.regions_beams else None)), reg_sub)
-            tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(reg_file)
-            return predict_result_file
-        if self.cfg.crops:
-            # a second TSV next to the predictions, one row per image: tags and caption per tile of the g x g tiling seen alone
-            crop_file = self.get_crops_file(predict_result_file)
-            crop_sub = crop_file if self.world == 1 else '{}_{}_{}.tsv'.format(crop_file, self.rank, self.world)
-            pred_rows = []
-            tsv_writer(run.counted(run.crop_rows(batches, dev, pred_rows, int(self.cfg.crops))), crop_sub)
-            tsv_writer(iter(pred_rows), sub)
-            run.report()
-            if self.world > 1:
-                self.merge_rank_files(predict_result_file)
-                self.merge_rank_files(crop_file)
-            return predict_result_file
-        tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)              # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
+        else:
+            tsv_writer(run.counted(run.caption_rows(batches, dev)), sub)              # .tsv + .lineidx + .lineidx.8b (tsv_io.py:959-998)
         run.report()
         if self.world > 1:
             self.merge_rank_files(predict_result_file)
+            if mode is not None:
+                self.merge_rank_files(mode_file(predict_result_file, mode.suffix))
         return predict_result_file
 
-    @staticmethod
-    def get_attention_file(predict_result_file):
-        """<predict file minus .tsv>.attn.tsv: written by predict when the config sets `attention_maps`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.attn.tsv'
+    def rank_file(self, f):
+        """The file this rank writes its share of `f` to: `f` itself in a one-process run (merge_rank_files reads the others)."""
+        return f if self.world == 1 else '{}_{}_{}.tsv'.format(f, self.rank, self.world)
 
-    @staticmethod
-    def get_alternatives_file(predict_result_file):
-        """<predict file minus .tsv>.alt.tsv: written by predict when the config sets `alternatives: k`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.alt.tsv'
+    # <predict file minus .tsv>.attn.tsv / .alt.tsv / .occ.tsv / .regions.tsv / .crops.tsv / .rollout.tsv
+    get_attention_file, get_alternatives_file, get_occlusion_file, get_regions_file, get_crops_file, get_rollout_file = (
+        staticmethod(functools.partial(mode_file, suffix=m.suffix)) for m in _MODES)
 
-    @staticmethod
-    def get_occlusion_file(predict_result_file):
-        """<predict file minus .tsv>.occ.tsv: written by predict when the config sets `occlusion: window`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.occ.tsv'
-
-    @staticmethod
-    def get_regions_file(predict_result_file):
-        """<predict file minus .tsv>.regions.tsv: written by predict when the config sets `regions: g`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.regions.tsv'
-
-    @staticmethod
-    def get_crops_file(predict_result_file):
-        """<predict file minus .tsv>.crops.tsv: written by predict when the config sets `crops: g`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.crops.tsv'
-
-    @staticmethod
-    def get_rollout_file(predict_result_file):
-        """<predict file minus .tsv>.rollout.tsv: written by predict when the config sets `rollout: true`."""
-        assert predict_result_file.endswith('.tsv')
-        return predict_result_file[:-len('.tsv')] + '.rollout.tsv'
-
-    def check_rollout(self):
-        """`rollout: true` is refused by name with what the encoder rollout is not built for, before a model is built."""
-        cfg = self.cfg
-        if not cfg.rollout:
-            return
-        if cfg.num_beams not in (None, 1):
-            raise NotImplementedError('rollout: the maps are those of greedy captions; beam search (num_beams=%r) is not built for them'
-                                      % (cfg.num_beams,))
-        if cfg.use_cbs:
-            raise NotImplementedError('rollout: the maps are those of greedy captions; CBS (use_cbs=%r) is not built for them' % (cfg.use_cbs,))
-        if cfg.caption_prefix:
-            raise NotImplementedError('rollout: caption_prefix=%r is not built together with the rollout maps (they are those of free '
-                                      'greedy captions)' % (cfg.caption_prefix,))
-        if int(cfg.tag_visible or 0) > 0:
-            raise NotImplementedError('rollout: visible tag slots (tag_visible=%r) are not built for the rollout maps' % (cfg.tag_visible,))
-        for other in ('attention_maps', 'alternatives', 'occlusion', 'regions', 'crops'):
-            if getattr(cfg, other):
-                raise NotImplementedError('rollout together with %s: one explaining pass per run is built; run the two configurations '
-                                          'one after the other' % other)
-
-    def check_crops(self):
-        """`crops: g` is refused by name with what patch removal is not built for, before a model is built."""
-        from .regions import grid_regions
-        cfg = self.cfg
-        if not cfg.crops:
-            return
-        grid_regions(cfg.crops)
-        if cfg.num_beams not in (None, 1):
-            raise NotImplementedError('crops: the crop captions are greedy; beam search (num_beams=%r) is not built for them' % (cfg.num_beams,))
-        if cfg.use_cbs:
-            raise NotImplementedError('crops: the crop captions are greedy; CBS (use_cbs=%r) is not built for them' % (cfg.use_cbs,))
-        if cfg.caption_prefix:
-            raise NotImplementedError('crops: caption_prefix=%r is not built together with the crop captions (they are free greedy '
-                                      'captions)' % (cfg.caption_prefix,))
-        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (crop_rows)
-            raise NotImplementedError('crops: visible tag slots (tag_visible=%r) are not built under patch removal' % (cfg.tag_visible,))
-        for other in ('attention_maps', 'alternatives', 'occlusion', 'regions'):
-            if getattr(cfg, other):
-                raise NotImplementedError('crops together with %s: one explaining pass per run is built; run the two configurations '
-                                          'one after the other' % other)
-
-    def check_regions(self):
-        """`regions: g` is refused by name with what the region captions are not built for, before a model is built."""
-        from .regions import grid_regions
-        cfg = self.cfg
+    def check_mode(self, key):
+        """A set analysis mode `key` is refused by name with what it is not built for, before a model is built: a bad value
+        (ValueError), beam search, CBS, a caption prefix, visible tag slots, another mode that comes before it in _MODES."""
+        cfg, at = self.cfg, [m.key for m in _MODES].index(key)
+        m = _MODES[at]
         k = cfg.regions_beams
-        if k is not None and k is not False:
+        if key == 'regions' and k is not None and k is not False:
             # the tiles' captions by k-beam search (ImageCaptioning.caption_regions_beam); the main caption stays as configured
             if not cfg.regions:
                 raise ValueError('regions_beams: %r is only valid next to `regions: g` (it sets how the tiles of the g x g tiling are '
@@ -894,67 +794,23 @@ class CaptionUniPipeline(object):
             if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= 8:
                 raise ValueError('regions_beams: the region captions under beam search take 2..8 beams (got %r); leave the key out for '
                                  'greedy region captions' % (k,))
-        if not cfg.regions:
+        if not getattr(cfg, key):
             return
-        grid_regions(cfg.regions)
-        if cfg.num_beams not in (None, 1):
-            raise NotImplementedError('regions: the region captions are greedy; beam search (num_beams=%r) is not built for them'
-                                      % (cfg.num_beams,))
-        if cfg.use_cbs:
-            raise NotImplementedError('regions: the region captions are greedy; CBS (use_cbs=%r) is not built for them' % (cfg.use_cbs,))
-        if cfg.caption_prefix:
-            raise NotImplementedError('regions: caption_prefix=%r is not built together with the region captions (they are free greedy '
-                                      'captions)' % (cfg.caption_prefix,))
-        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (region_rows)
-            raise NotImplementedError('regions: visible tag slots (tag_visible=%r) are not built for the region captions' % (cfg.tag_visible,))
-        for other in ('attention_maps', 'alternatives', 'occlusion'):
-            if getattr(cfg, other):
-                raise NotImplementedError('regions together with %s: one explaining pass per run is built; run the two configurations '
-                                          'one after the other' % other)
+        if m.check is not None:
+            m.check(getattr(cfg, key))
+        # a mask that shows tag slots is refused when the first batch arrives (_PredictRun.analysed)
+        for opt, bad in (('num_beams', cfg.num_beams not in (None, 1)), ('use_cbs', bool(cfg.use_cbs)),
+                         ('caption_prefix', bool(cfg.caption_prefix)), ('tag_visible', m.refuse_tags and int(cfg.tag_visible or 0) > 0)):
+            if bad:
+                raise NotImplementedError('%s: %s=%r is not built for the %s (they are those of free greedy captions without visible tag '
+                                          'slots)' % (key, opt, getattr(cfg, opt), m.noun))
+        for earlier in _MODES[:at]:
+            if getattr(cfg, earlier.key):
+                raise NotImplementedError('%s together with %s: one explaining pass per run is built; run the two configurations one '
+                                          'after the other' % (key, earlier.key))
 
-    def check_occlusion(self):
-        """`occlusion: window` is refused by name with what the occlusion maps are not built for, before a model is built."""
-        from .occlusion import check_window
-        cfg = self.cfg
-        if not cfg.occlusion:
-            return
-        check_window(cfg.occlusion)
-        if cfg.num_beams not in (None, 1):
-            raise NotImplementedError('occlusion: the maps are those of greedy captions; beam search (num_beams=%r) is not built for '
-                                      'them' % (cfg.num_beams,))
-        if cfg.use_cbs:
-            raise NotImplementedError('occlusion: the maps are those of greedy captions; CBS (use_cbs=%r) is not built for them'
-                                      % (cfg.use_cbs,))
-        if cfg.caption_prefix:
-            raise NotImplementedError('occlusion: caption_prefix=%r is not built together with the occlusion maps (they are those of '
-                                      'free greedy captions)' % (cfg.caption_prefix,))
-        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (occlusion_rows)
-            raise NotImplementedError('occlusion: visible tag slots (tag_visible=%r) are not built for the occlusion maps' % (cfg.tag_visible,))
-        if cfg.attention_maps:
-            raise NotImplementedError('occlusion together with attention_maps: one explaining pass per run is built; run the two '
-                                      'configurations one after the other')
-        if cfg.alternatives:
-            raise NotImplementedError('occlusion together with alternatives: one explaining pass per run is built; run the two '
-                                      'configurations one after the other')
-
-    def check_alternatives(self):
-        """`alternatives: k` is refused by name with what the alternatives are not built for, before a model is built."""
-        from .alternatives import check_k
-        cfg = self.cfg
-        if not cfg.alternatives:
-            return
-        check_k(cfg.alternatives)
-        if cfg.num_beams not in (None, 1) or cfg.use_cbs:
-            raise NotImplementedError('alternatives: they are those of greedy captions; beam search (num_beams=%r) and CBS (use_cbs=%r) '
-                                      'are not built for them' % (cfg.num_beams, cfg.use_cbs))
-        if cfg.caption_prefix:
-            raise NotImplementedError('alternatives: caption_prefix=%r is not built together with the alternatives (they are those of '
-                                      'free greedy captions)' % (cfg.caption_prefix,))
-        if int(cfg.tag_visible or 0) > 0:      # a mask that shows tag slots is refused when the first batch arrives (alternative_rows)
-            raise NotImplementedError('alternatives: visible tag slots (tag_visible=%r) are not built for the alternatives' % (cfg.tag_visible,))
-        if cfg.attention_maps:
-            raise NotImplementedError('alternatives together with attention_maps: one explaining pass per run is built; run the two '
-                                      'configurations one after the other')
+    def check_regions(self):
+        return self.check_mode('regions')
 
     def merge_rank_files(self, predict_result_file):
         """Rank 0 concatenates the ranks' files and de-duplicates by key (uni_pipeline.py:816-831); every rank waits for it."""
@@ -974,17 +830,8 @@ class CaptionUniPipeline(object):
 
     def ensure_predict(self, model_file=None):
         check_model_config(self.cfg, training=False)
-        if self.cfg.attention_maps and (self.cfg.num_beams not in (None, 1) or self.cfg.use_cbs):
-            raise NotImplementedError('attention_maps: the maps are those of greedy captions; beam search (num_beams=%r) and CBS '
-                                      '(use_cbs=%r) are not built for them' % (self.cfg.num_beams, self.cfg.use_cbs))
-        if self.cfg.attention_maps and self.cfg.caption_prefix:
-            raise NotImplementedError('attention_maps: caption_prefix=%r is not built together with the attention maps (the maps are '
-                                      'those of free greedy captions)' % (self.cfg.caption_prefix,))
-        self.check_alternatives()
-        self.check_occlusion()
-        self.check_regions()
-        self.check_crops()
-        self.check_rollout()
+        for m in _MODES:
+            self.check_mode(m.key)
         if self.cfg.ignore_predict:
             logging.info('ignore to predict as instructed')
             return None
@@ -995,19 +842,9 @@ class CaptionUniPipeline(object):
         if not op.isfile(model_file) and self.cfg.init_recipe_seed is None:
             logging.info('ignore to run predict since %s does not exist', model_file)
             return predict_result_file
-        have = op.isfile(predict_result_file)
-        if have and self.cfg.attention_maps and not op.isfile(self.get_attention_file(predict_result_file)):
-            have = False             # predictions from a run without the key: both files are written again
-        if have and self.cfg.alternatives and not op.isfile(self.get_alternatives_file(predict_result_file)):
-            have = False
-        if have and self.cfg.occlusion and not op.isfile(self.get_occlusion_file(predict_result_file)):
-            have = False
-        if have and self.cfg.regions and not op.isfile(self.get_regions_file(predict_result_file)):
-            have = False
-        if have and self.cfg.crops and not op.isfile(self.get_crops_file(predict_result_file)):
-            have = False
-        if have and self.cfg.rollout and not op.isfile(self.get_rollout_file(predict_result_file)):
-            have = False
+        # predictions from a run without the mode's key: both files are written again
+        have = op.isfile(predict_result_file) and all(op.isfile(mode_file(predict_result_file, m.suffix))
+                                                      for m in _MODES if getattr(self.cfg, m.key))
         if have and not self.cfg.force_predict:
             logging.info('ignore to do prediction %s', predict_result_file)
             return predict_result_file
