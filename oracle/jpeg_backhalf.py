@@ -5,7 +5,7 @@ The reference decodes JPEGs with cv2.imdecode (src/tools/common.py:23-31, src/da
 libjpeg-turbo with its defaults (JDCT_ISLOW, do_fancy_upsampling, JCS_RGB output).  libjpeg-turbo is a third-party dependency that is
 NOT in /root/reference (Pillow 12.2 bundles its 3.x line here: `PIL.features.version('jpg')`); this file restates its published algorithm:
 
-  jidctint.c  jpeg_idct_islow      dequantise + 8x8 inverse DCT, 13-bit fixed point, two passes, range limit
+  jidctint.c  jpeg_idct_islow      dequantise + 8x8 inverse DCT, 13-bit fixed point, two passes, saturation to 8 bits
   jdsample.c  h2v1_fancy_upsample / h2v2_fancy_upsample   triangle-filter chroma upsampling (3/4, 1/4 weights)
   jdmainct.c  context rows         the rows above the first / below the last real row are copies of that row
   jdcolor.c   ycc_rgb_convert      fixed-point YCbCr -> RGB (SCALEBITS = 16)
@@ -53,9 +53,11 @@ def _idct_1d(i0, i1, i2, i3, i4, i5, i6, i7, shift):
 
 
 def range_limit(x):
-    """sample_range_limit + CENTERJSAMPLE indexed by x & RANGE_MASK (jdmaster.c prepare_range_limit_table)."""
-    v = x & 1023
-    out = np.where(v < 128, v + 128, np.where(v < 512, 255, np.where(v < 896, 0, v - 896)))
+    """Centre (+128) and saturate to [0, 255]: what libjpeg-turbo's SIMD inverse DCT does (saturating packs), i.e. what Pillow returns.
+    jidctint.c's C path indexes sample_range_limit with x & RANGE_MASK (10 bits) instead; the two agree for every sample within
+    [-512, 384) of the centre -- every stream an encoder writes from 8-bit samples -- and differ beyond (a sample 384..767 above the
+    centre reads 0 from the table).  Streams with inflated quantisation tables reach that range (oracle/input_side_cases.py a2x)."""
+    out = np.clip(x + 128, 0, 255)
     return out.astype(np.uint8)
 
 

@@ -274,8 +274,6 @@ NO_DIRECT_GPU_TEST = {
     'vitcap_engine_graph_count': _ENGINE,
     'vitcap_engine_timing_begin': _TIMING, 'vitcap_engine_timing_sample': _TIMING, 'vitcap_engine_timing_end': _TIMING,
     'vitcap_engine_timing_end_ex': _TIMING, 'vitcap_engine_timing_end_kernel': _TIMING,
-    'vitcap_image_preproc': _IMAGEIO, 'vitcap_image_preproc_workspace_bytes': _IMAGEIO, 'vitcap_image_train_preproc': _IMAGEIO,
-    'vitcap_image_train_preproc_workspace_bytes': _IMAGEIO, 'vitcap_jpeg_backhalf_workspace_bytes': _IMAGEIO,
     'vitcap_resample_coeffs': 'host only (no GPU): test_image_transform_cpu.py',
     'vitcap_resized_geometry': 'host only (no GPU): test_image_transform_cpu.py',
 }

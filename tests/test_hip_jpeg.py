@@ -48,7 +48,7 @@ def test_grey_restart_markers_and_extreme_coefficients():
     from vitcap_amd.imageio import jpeg_backhalf
     arr = synth(321, 203, 7)
     datas = [jpeg_bytes(arr[:, :, 0], quality=80), jpeg_bytes(arr, quality=85, optimize=True), jpeg_bytes(arr, quality=2), jpeg_bytes(arr, quality=100)]
-    # saturated content: hard black / white checkerboard at quality 10 overshoots the [0, 255] range inside the IDCT (range-limit table)
+    # saturated content: hard black / white checkerboard at quality 10 overshoots the [0, 255] range inside the IDCT (its saturation to 8 bits)
     chk = ((np.indices((160, 200)).sum(0) // 3) % 2 * 255).astype(np.uint8)
     datas.append(jpeg_bytes(np.stack([chk, 255 - chk, chk], -1), quality=10, subsampling=2))
     try:

@@ -7,14 +7,8 @@ import pytest
 from PIL import Image
 
 from oracle import image_oracle as IO
-
-
-def _img(h, w, seed):
-    g = np.random.default_rng(seed)
-    base = g.integers(0, 256, size=(h // 8 + 2, w // 8 + 2, 3), dtype=np.uint8)
-    big = np.asarray(Image.fromarray(base, 'RGB').resize((w, h), Image.BILINEAR)).copy()
-    noise = g.integers(-20, 21, size=big.shape)
-    return np.clip(big.astype(np.int64) + noise, 0, 255).astype(np.uint8)
+from oracle.input_side_cases import B1_SETTINGS
+from oracle.input_side_cases import smooth as _img
 
 
 @pytest.mark.parametrize('h,w,oh,ow', [(480, 640, 384, 512), (333, 500, 384, 576), (640, 427, 575, 384), (200, 300, 384, 576),
@@ -47,6 +41,29 @@ def test_cabi_weight_tables_and_geometry():
     with pytest.raises(RuntimeError):
         oh = C.c_int()
         check(lib.vitcap_resized_geometry(100, 100, 200, 384, C.byref(oh), C.byref(oh), C.byref(oh), C.byref(oh)), 'geometry')
+
+
+def test_cabi_geometry_at_every_small_size():
+    """vitcap_resized_geometry (resized_dims + py_round_half) against the oracle's torchvision rules for every (h, w) in 1..60 at the small
+    settings of the input-side tables: every residue of the odd short- and long-side difference, both directions of round-half-to-even,
+    and the refusal where the resized image is smaller than the crop."""
+    from vitcap_amd._lib import lib
+    n_refused, dirs = 0, set()
+    for crop, size in B1_SETTINGS + ((24, 16),):
+        for h in range(1, 61):
+            for w in range(1, 61):
+                oh, ow, y0, x0 = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+                rc = lib.vitcap_resized_geometry(h, w, size, crop, C.byref(oh), C.byref(ow), C.byref(y0), C.byref(x0))
+                nh, nw = IO.resized_size(h, w, size)
+                if nh < crop or nw < crop:
+                    assert rc != 0 and b'smaller than' in lib.vitcap_last_error(), (h, w, size, crop)
+                    n_refused += 1
+                    continue
+                assert rc == 0 and (oh.value, ow.value) == (nh, nw) and (y0.value, x0.value) == IO.crop_origin(nh, nw, crop), (h, w, size, crop)
+                for d, o in ((nh - crop, y0.value), (nw - crop, x0.value)):
+                    if d % 2:
+                        dirs.add((d % 4, o - d // 2))
+    assert dirs == {(1, 0), (3, 1)} and n_refused == 3600        # 4k+1 rounds down, 4k+3 up; resize_short 16 < crop 24 is always refused
 
 
 def test_tsv_roundtrip(tmp_path):

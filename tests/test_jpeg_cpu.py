@@ -9,30 +9,10 @@ import pytest
 from PIL import Image
 
 from oracle import jpeg_backhalf as O
+from oracle.input_side_cases import jpeg_bytes, pillow_rgb, synth      # noqa: F401  (shared with the input-side case tables)
 from vitcap_amd import jpegdec as J
 
 SIZES = [(384, 384), (640, 480), (480, 640), (500, 375), (333, 500), (17, 23), (8, 8), (1024, 683), (97, 211)]     # (W, H)
-
-
-def synth(w, h, seed):
-    """Photo-like content: smooth gradients + texture + hard edges (every AC band and the clamps get exercised)."""
-    rng = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    img = np.stack([128 + 100 * np.sin(xx / (7.0 + c) + seed) * np.cos(yy / (11.0 - c)) for c in range(3)], -1)
-    img += rng.randn(h, w, 3) * 25
-    img[h // 3:h // 2, w // 4:w // 2] = rng.randint(0, 2, 3) * 255
-    return np.clip(img, 0, 255).astype(np.uint8)
-
-
-def jpeg_bytes(arr, **kw):
-    b = io.BytesIO()
-    Image.fromarray(arr).save(b, format='JPEG', **kw)
-    return b.getvalue()
-
-
-def pillow_rgb(data):
-    im = Image.open(io.BytesIO(data))
-    return np.asarray(im.convert('RGB') if im.mode != 'RGB' else im)
 
 
 needs_lib = pytest.mark.skipif(J.jpeg_lib() is None, reason='libvitcap_jpeg.so not built')

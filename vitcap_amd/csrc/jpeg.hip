@@ -2,7 +2,7 @@
 // entropy decoder (jpeg_host.cpp) -> dequantisation + 8x8 inverse DCT -> component planes -> chroma upsampling + YCbCr -> RGB -> the
 // uint8 HWC image that vitcap_image_preproc resizes.  It restates libjpeg(-turbo)'s DEFAULT decompression path, which is integer
 // arithmetic end to end, so the pixels are bit-identical to Pillow's decoder (tests/test_hip_jpeg.py):
-//   jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2, range-limit table), jdsample.c h2v1 / h2v2 fancy upsampling with
+//   jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2, samples saturated as its SIMD form does), jdsample.c h2v1 / h2v2 fancy upsampling with
 //   jdmainct.c's replicated context rows at the top / bottom edge, jdcolor.c ycc_rgb_convert (SCALEBITS 16).
 // HBM-bound byte work: 3 B per pixel of coefficients in, 1.5 B of planes out and back in, 3 B of RGB out; a 640 x 480 image is 7 200
 // independent blocks, a batch of 64 half a million threads -- no tiling to speak of, coalescing is what matters (adjacent threads take
@@ -60,10 +60,13 @@ __device__ __forceinline__ void idct_1d(int i0, int i1, int i2, int i3, int i4, 
   o[3] = descale(tmp13 + tmp0, SHIFT); o[4] = descale(tmp13 - tmp0, SHIFT);
 }
 
-// sample_range_limit + CENTERJSAMPLE indexed by (x & RANGE_MASK): jdmaster.c prepare_range_limit_table
+// Centre and saturate, as libjpeg-turbo's SIMD inverse DCT does (saturating packs, then + CENTERJSAMPLE): what Pillow's decoder returns.
+// jidctint.c's C path reads sample_range_limit[x & RANGE_MASK] instead (jdmaster.c prepare_range_limit_table: 10 index bits); the two
+// agree for samples within [-512, 384) of the centre, i.e. for every stream encoded from 8-bit samples, and differ beyond: a stream with
+// inflated quantisation tables puts samples there, and the table's wrap (384..767 above the centre reads 0) is not what Pillow shows.
 __device__ __forceinline__ unsigned range_limit(int x) {
-  const int v = x & 1023;
-  return (unsigned)(v < 128 ? v + 128 : (v < 512 ? 255 : (v < 896 ? 0 : v - 896)));
+  const int v = x + 128;
+  return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
 // one thread per 8x8 block: grid (ceil(max blocks / 256), images).  The 256 blocks of a workgroup are 32 KB of CONTIGUOUS coefficients:
